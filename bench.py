@@ -12,13 +12,25 @@ beams, 2000x2000 map, converged cloud; inputs are resident in H
 timed region.  For N>1 the driver launches one rank per GPU through torch.distributed.run;
 each rank holds a 100 000-particle shard of one filter (weak scaling).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.
-When the run is the plain headline (no --config / --model / size flag) the same line also carries
+Rank 0 prints ONE JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step and the workload's
+config.  A plain run does nothing else: set-up, warm-up, the K timed steps, the outputs (--dump-outputs DIR) and
+the line.
+
+    python bench.py --full ...
+
+adds everything that is measured beside the headline: `roofline` (HIP events on the scoring dispatch), the
+per-kernel breakdown (`kernel_ms_per_step`, an extra pass), `cpu_baseline` / `cpu_baseline_all_cores` (the
+oracle on the host), `host_buffer_path` (N=1), and, when the run is the plain headline (no --config / --model /
+size flag),
   other_configs   N=1: short timed regions of BASELINE configs[2] (beam model), configs[4] (3-D) and
                   configs[0] (the reference's own CPU case), each with its own roofline + cpu_baseline
   strong_scaling  BASELINE configs[3] as worded: 1 000 000 particles TOTAL, 1 000 000 / N per GPU
   exchange_ms     N>1: the sharded step timed once per exchange (mailbox, then torch.distributed = RCCL)
-so that one driver command times every BASELINE configuration.
+so that one command times every BASELINE configuration.
+
+--dump-outputs DIR writes what the last timed step handed its caller (the resampled set and the filter's state)
+as DIR/<name>.npy.  The resampler's random state is put back to its seeded value in front of the timed region,
+so that the same arguments give the same outputs whatever the (time-bounded) warm-up ran.
 """
 import argparse
 import copy
@@ -442,10 +454,87 @@ class Ctx:
                 self.dist.barrier()
 
 
+def roofline_fields(args, e, sc, pf, data, wl, prof, mean_cells):
+    """--full: the scoring kernel's HIP-event time priced against SURVEY 8(d)'s algorithmic bytes, with what the
+    committed PMC passes say binds it (the beam model walks its rays once more to count the cells)."""
+    score = prof["score"]
+    k_ms = score["ms"] / max(score["launches"], 1)
+    if args.model == "beam":
+        e.set_option(1, 1)
+        e.cells_walked(reset=True)
+        pf.restore()
+        sc.updateSensor(pf, data)
+        e.synchronize()
+        mean_cells = e.cells_walked() / (float(wl["n"]) * wl["beams"])
+        e.set_option(1, 0)
+    abytes = algorithmic_bytes(args.model, wl["n"], wl["beams"], mean_cells)
+    achieved = abytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+    ev = pmc_evidence(args.model, args.cloud, k_ms, wl["n"], wl["beams"])
+    # `achieved` is ALGORITHMIC GB/s (SURVEY 8(d): bytes the reference's formulation moves per launch / the
+    # kernel's duration), `frac` its fraction of the HBM peak; `bound` is what the PMC passes show limits the
+    # kernel (valu_issue / l1_access_rate: the LUT working set is L2-resident, see issue_frac / hbm_measured_gbs / bound_is); None = no PMC
+    # pass of this workload is committed, so nothing is claimed
+    roof = {"bound": ev["bound"], "kernel": e.score_kernel_name(), "achieved": achieved,
+            "achieved_is": "algorithmic GB/s", "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": ev["traffic"],
+            "traffic_source": ev["traffic_source"], "kernel_ms": k_ms,
+            "algorithmic_bytes_per_launch": abytes,
+            "launches_timed": int(score["launches"]),
+            # SURVEY 8(d) asks for the fraction against the measured streaming-copy rate as well
+            # (6.29 TB/s, MI355X_MICROARCH.md), the "measured HBM roofline" of north_star
+            "peak_measured_copy": HBM_MEASURED_COPY_GBS,
+            "frac_of_measured_copy": achieved / HBM_MEASURED_COPY_GBS}
+    if ev["bound"] is None:
+        roof["bound_is"] = "unmeasured: no committed PMC pass for this workload (profiles/pmc_traffic.json)"
+    elif "bound_is" in ev:
+        roof["bound_is"] = ev["bound_is"]
+    for k in ("issue_frac", "hbm_measured_gbs"):
+        if k in ev:
+            roof[k] = ev[k]
+    if args.model in ("lf", "gompertz") and k_ms > 0:
+        # what the kernel really gathers per evaluation is a 1- or 2-byte level id (SURVEY 8(d) counts the reference's
+        # 4-byte float): the same launch priced at the bytes it touches, for whoever wants that figure
+        gb = e.lut_entry_bytes() if hasattr(e, "lut_entry_bytes") else 2
+        touched = float(gb) * wl["n"] * wl["beams"] + 40.0 * wl["n"] + 16.0 * wl["beams"]
+        roof["gathered_bytes_per_eval"] = gb
+        roof["achieved_at_gathered_bytes_gbs"] = touched / (k_ms * 1e-3) / 1e9
+    if mean_cells is not None and args.model == "beam":
+        roof["mean_cells_per_ray"] = mean_cells
+    return {"roofline": roof}
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files of one run together
+
+
+def step_outputs(pf, sf):
+    """What a caller of the timed step holds after its last step: the resampled set (x, y, theta, weight per row) and
+    the filter's state.  Host copies, taken after the timed region."""
+    samples = pf.getCurrentSet().samples
+    st = pf.getState() if sf is None else sf.state()
+    state = np.array([st.sample_count, st.leaf_count, st.converged, st.percent_converged, st.total, st.w_slow,
+                      st.w_fast], dtype=np.float64)
+    return {"samples": samples, "filter_state": state}
+
+
+def write_outputs(path, outputs, rank, world):
+    """DIR/<name>.npy, float64; N > 1: every rank its own shard (<name>_rank<r>.npy).  A set too large for the budget
+    is written as a fixed, seeded sample of its rows, their indices beside it (samples_rows)."""
+    out = dict(outputs)
+    samples = out["samples"]
+    keep = (DUMP_LIMIT_BYTES // 2) // (samples.shape[1] * samples.itemsize + 8) // world
+    if samples.shape[0] > keep:
+        rows = np.sort(np.random.default_rng(0).choice(samples.shape[0], keep, replace=False))
+        out["samples"], out["samples_rows"] = samples[rows], rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, (name if world == 1 else "%s_rank%d" % (name, rank)) + ".npy"),
+                np.ascontiguousarray(a, dtype=np.float64))
+
+
 def measure(args, ctx, steps, warmup, prewarm, cpu_budget, all_cores=False, host_path=False, profile_mode=1,
-            exchange=None, compare_exchanges=False, prewarm_s=0.25, repeat=False):
-    """One engine, one workload: W warm-up steps, K timed steps between fences, the scoring kernel's HIP events, the
-    CPU baseline.  Returns the record (rank 0) or None (other ranks)."""
+            exchange=None, compare_exchanges=False, prewarm_s=0.25, repeat=False, full=True, dump_dir=None):
+    """One engine, one workload: W warm-up steps, K timed steps between fences; with `full` also the scoring kernel's
+    HIP events, the per-kernel pass and the CPU baseline.  Returns the record (rank 0) or None (other ranks)."""
     torch, dist, world, rank = ctx.torch, ctx.dist, ctx.world, ctx.rank
     wl = build_workload(args, rank)
     n_global = wl["n"] * world
@@ -459,6 +548,7 @@ def measure(args, ctx, steps, warmup, prewarm, cpu_budget, all_cores=False, host
     with Stage("engine set-up (%s)" % args.model, 300):
         e, m, sc, pf, data, lut = setup_engine(args, wl, ctx.local_rank)
     t_setup = time.perf_counter() - t_setup
+    rng0 = pf.getRngState()  # srand48(42): the timed region starts from it whatever the warm-up drew
     if lut is not None:
         ctx.lut_cache[lut_key] = lut
     if os.environ.get("BPF_BENCH_FUSED") == "0":
@@ -526,7 +616,8 @@ def measure(args, ctx, steps, warmup, prewarm, cpu_budget, all_cores=False, host
     # The event pool is created (16 384 hipEventCreate, tens of ms of host time) BEFORE the warm-up: a pause of that
     # length between the warm-up and the timed region lets the GPU's clocks fall, and a short timed region (the
     # driver's 20 steps) then reads 0.147 ms per step where 300 steps read 0.123.
-    e.profile_enable(profile_mode)  # HIP events attached to the scoring dispatch only
+    # HIP events attached to the scoring dispatch only (the roofline's kernel time): --full runs alone
+    e.profile_enable(profile_mode if full else 0)
     with Stage("warm-up (%s)" % args.model, 300):
         pw_done = 0
         if prewarm > 0:
@@ -544,9 +635,14 @@ def measure(args, ctx, steps, warmup, prewarm, cpu_budget, all_cores=False, host
             step()
         fence()
     e.profile_reset()
+    # the prewarm's step count follows the clock: without this the draws of the timed steps would too
+    pf.setRngState(rng0)
     with Stage("timed region (%s)" % args.model, 600):
         dt = timed(steps)
-    prof = e.profile_get()
+    prof = e.profile_get() if full else None
+    st = pf.getState() if dist is None else sf.state()  # the set the last timed step left (config.resampled_to)
+    if dump_dir is not None:
+        write_outputs(dump_dir, step_outputs(pf, sf), rank, world)
     # sub-records: the same K steps once more (ms_per_step_repeat), so that a one-off stall of the shared host inside a
     # region of a few milliseconds shows as what it is; the record's figures come from the first region
     dt_repeat = None
@@ -555,15 +651,16 @@ def measure(args, ctx, steps, warmup, prewarm, cpu_budget, all_cores=False, host
         with Stage("timed region, repeat (%s)" % args.model, 600):
             dt_repeat = timed(steps)
     # untimed extra pass with every kernel class bracketed, for the per-kernel breakdown
-    e.profile_enable(2)
-    e.profile_reset()
-    n_all = max(1, min(steps, 10))
-    for _ in range(n_all):
-        step()
-    fence()
-    prof_all = e.profile_get()
-    e.profile_enable(0)
-    st = pf.getState() if dist is None else sf.state()
+    prof_all, n_all = {}, 1
+    if full:
+        e.profile_enable(2)
+        e.profile_reset()
+        n_all = max(1, min(steps, 10))
+        for _ in range(n_all):
+            step()
+        fence()
+        prof_all = e.profile_get()
+        e.profile_enable(0)
     ran_with_mailbox = bool(sf is not None and sf.mailbox)  # the exchange `value` was measured with
 
     exchange_ms = None
@@ -602,19 +699,6 @@ def measure(args, ctx, steps, warmup, prewarm, cpu_budget, all_cores=False, host
         e.close()
         return None
 
-    score = prof["score"]
-    k_ms = score["ms"] / max(score["launches"], 1)
-    if args.model == "beam":
-        e.set_option(1, 1)
-        e.cells_walked(reset=True)
-        pf.restore()
-        sc.updateSensor(pf, data)
-        e.synchronize()
-        mean_cells = e.cells_walked() / (float(wl["n"]) * wl["beams"])
-        e.set_option(1, 0)
-    abytes = algorithmic_bytes(args.model, wl["n"], wl["beams"], mean_cells)
-    achieved = abytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-    ev = pmc_evidence(args.model, args.cloud, k_ms, wl["n"], wl["beams"])
     backend_name = None if dist is None else dist.get_backend()
     multi = multi_gpu_fields(backend_name, None if dist is None else dist.get_world_size(), selftest, exchange_ms)
     collective_is = multi.get("collective_is")
@@ -636,42 +720,12 @@ def measure(args, ctx, steps, warmup, prewarm, cpu_budget, all_cores=False, host
                    "shard_exchange": (None if dist is None else (
                        "mailbox (peer stores into IPC-mapped device memory)" if ran_with_mailbox
                        else "collective (%s)" % collective_is))},
-        # `achieved` is ALGORITHMIC GB/s (bytes the reference's formulation moves per launch / the
-        # kernel's duration), `frac` its fraction of the HBM peak; `bound` is what the PMC passes show limits the
-        # kernel (valu_issue / l1_access_rate: the LUT working set is L2-resident, see issue_frac / hbm_measured_gbs / bound_is); None = no PMC
-        # pass of this workload is committed, so nothing is claimed
-        "roofline": {"bound": ev["bound"], "kernel": e.score_kernel_name(), "achieved": achieved,
-                     "achieved_is": "algorithmic GB/s", "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": ev["traffic"],
-                     "traffic_source": ev["traffic_source"], "kernel_ms": k_ms,
-                     "algorithmic_bytes_per_launch": abytes,
-                     "launches_timed": int(score["launches"]),
-                     # SURVEY 8(d) asks for the fraction against the measured streaming-copy rate as well
-                     # (6.29 TB/s, MI355X_MICROARCH.md), the "measured HBM roofline" of north_star
-                     "peak_measured_copy": HBM_MEASURED_COPY_GBS,
-                     "frac_of_measured_copy": achieved / HBM_MEASURED_COPY_GBS},
-        "cpu_baseline": cpu,
-        "cpu_baseline_all_cores": cpu_all,
-        "host_buffer_path": host,
-        "kernel_ms_per_step": {k: v["ms"] / n_all for k, v in prof_all.items() if v["launches"]},
         "setup_s": t_setup,
     }
-    if ev["bound"] is None:
-        line["roofline"]["bound_is"] = "unmeasured: no committed PMC pass for this workload (profiles/pmc_traffic.json)"
-    elif "bound_is" in ev:
-        line["roofline"]["bound_is"] = ev["bound_is"]
-    for k in ("issue_frac", "hbm_measured_gbs"):
-        if k in ev:
-            line["roofline"][k] = ev[k]
-    if args.model in ("lf", "gompertz") and k_ms > 0:
-        # what the kernel really gathers per evaluation is a 1- or 2-byte level id (SURVEY 8(d) counts the reference's
-        # 4-byte float): the same launch priced at the bytes it touches, for whoever wants that figure
-        gb = e.lut_entry_bytes() if hasattr(e, "lut_entry_bytes") else 2
-        touched = float(gb) * wl["n"] * wl["beams"] + 40.0 * wl["n"] + 16.0 * wl["beams"]
-        line["roofline"]["gathered_bytes_per_eval"] = gb
-        line["roofline"]["achieved_at_gathered_bytes_gbs"] = touched / (k_ms * 1e-3) / 1e9
-    if mean_cells is not None and args.model == "beam":
-        line["roofline"]["mean_cells_per_ray"] = mean_cells
+    if full:
+        line.update(roofline_fields(args, e, sc, pf, data, wl, prof, mean_cells))
+        line.update({"cpu_baseline": cpu, "cpu_baseline_all_cores": cpu_all, "host_buffer_path": host,
+                     "kernel_ms_per_step": {k: v["ms"] / n_all for k, v in prof_all.items() if v["launches"]}})
     line.update(multi)
     e.close()
     return line
@@ -799,7 +853,8 @@ def parse_args(argv=None):
                     help="particles per GPU (default 100000; 200000 for cloud3d)")
     ap.add_argument("--beams", type=int, default=1081)
     ap.add_argument("--map-size", type=int, default=2000)
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU baseline work (0 = skip)")
+    ap.add_argument("--cpu-budget", type=float, default=12.0,
+                    help="with --full: seconds of CPU baseline work (0 = skip)")
     ap.add_argument("--prewarm", type=int, default=60,
                     help="untimed steps in front of the --warmup steps that bring the GPU's clocks up: at least this "
                          "many, and at least --prewarm-seconds of them (the clocks take ~40 ms of load to come up: with "
@@ -813,12 +868,18 @@ def parse_args(argv=None):
     ap.add_argument("--lut", default="reference", choices=["reference", "exact-edt"],
                     help="2-D distance LUT: the reference's brushfire (host builder, what OccupancyMap::updateDistancesLUT "
                          "gives; default) or the exact EDT built on the device")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, per-kernel breakdown, CPU baselines, "
+                         "host_buffer_path and the sub-records (--cpu-budget, --extras, --sub-cpu-budget and "
+                         "--host-path only act with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (resampled set, filter state) as DIR/<name>.npy")
     ap.add_argument("--extras", default="auto", choices=["auto", "on", "off"],
-                    help="other_configs / strong_scaling / exchange_ms sub-records in the same line (auto: when the run "
-                         "is the plain headline)")
+                    help="with --full: other_configs / strong_scaling / exchange_ms sub-records in the same line (auto: "
+                         "when the run is the plain headline)")
     ap.add_argument("--sub-cpu-budget", type=float, default=4.0, help="seconds of CPU baseline work per sub-record")
     ap.add_argument("--host-path", default="on", choices=["on", "off"],
-                    help="also time Seam A with host buffers (host_buffer_path; N = 1 only)")
+                    help="with --full: also time Seam A with host buffers (host_buffer_path; N = 1 only)")
     args = ap.parse_args(argv)
     args.strong_total = None
     return args
@@ -826,7 +887,8 @@ def parse_args(argv=None):
 
 def main():
     args = parse_args()
-    extras = args.extras == "on" or (args.extras == "auto" and is_plain_headline(args))
+    full = args.full
+    extras = full and (args.extras == "on" or (args.extras == "auto" and is_plain_headline(args)))
     apply_config_preset(args)
     if args.particles is None:
         args.particles = 200000 if args.model == "cloud3d" else 100000
@@ -889,10 +951,10 @@ def main():
     gc.collect()
     gc.freeze()  # see measure()
 
-    line = measure(args, ctx, args.steps, args.warmup, args.prewarm, args.cpu_budget, all_cores=(world == 1),
-                   host_path=(world == 1 and args.host_path == "on"),
+    line = measure(args, ctx, args.steps, args.warmup, args.prewarm, args.cpu_budget if full else 0,
+                   all_cores=(full and world == 1), host_path=(full and world == 1 and args.host_path == "on"),
                    compare_exchanges=(extras and ctx.dist is not None),
-                   prewarm_s=args.prewarm_seconds)
+                   prewarm_s=args.prewarm_seconds, full=full, dump_dir=args.dump_outputs)
     if extras:
         sub_budget = min(args.sub_cpu_budget, args.cpu_budget)
         if ctx.dist is None:

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -130,6 +131,35 @@ def test_plain_headline_detection_and_sub_records():
     assert set(sub) == {"metric", "value", "ms_per_step", "roofline", "cpu_baseline", "config"}
 
 
+def test_a_plain_run_measures_the_headline_only():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    b = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert b.full and b.dump_outputs == "out"
+
+
+def test_dumped_outputs_are_float64_and_a_fixed_sample_within_the_budget(tmp_path):
+    state = np.arange(7, dtype=np.float64)
+    small = np.arange(4 * 1000, dtype=np.float64).reshape(-1, 4)
+    bench.write_outputs(str(tmp_path / "small"), {"samples": small, "filter_state": state}, 0, 1)
+    assert sorted(os.listdir(tmp_path / "small")) == ["filter_state.npy", "samples.npy"]
+    assert np.array_equal(np.load(tmp_path / "small" / "samples.npy"), small)
+    # a set too large for the budget: the same seeded rows every time, their indices beside them
+    big = np.arange(4 * 1200000, dtype=np.float64).reshape(-1, 4)
+    for k in ("a", "b"):
+        bench.write_outputs(str(tmp_path / k), {"samples": big, "filter_state": state}, 0, 1)
+        names = sorted(os.listdir(tmp_path / k))
+        assert names == ["filter_state.npy", "samples.npy", "samples_rows.npy"]
+        assert sum(os.path.getsize(tmp_path / k / f) for f in names) <= bench.DUMP_LIMIT_BYTES
+        got = {f[:-4]: np.load(tmp_path / k / f) for f in names}
+        assert all(v.dtype == np.float64 for v in got.values())
+        assert np.array_equal(got["samples"], big[got["samples_rows"].astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "a" / "samples_rows.npy"), np.load(tmp_path / "b" / "samples_rows.npy"))
+    # N > 1: one file per rank
+    bench.write_outputs(str(tmp_path / "r"), {"samples": small, "filter_state": state}, 1, 2)
+    assert sorted(os.listdir(tmp_path / "r")) == ["filter_state_rank1.npy", "samples_rank1.npy"]
+
+
 def test_cpu_sample_is_bounded_by_the_budget():
     # headline: one step of the whole set fits 12 s at the oracle's pace; a 4 s budget of the beam model does not
     assert bench.cpu_sample_particles("lf", 100000, 1081, 12.0) == 100000
@@ -214,6 +244,28 @@ def _run(argv, env_extra, timeout=240):
 def test_a_world_size_that_contradicts_gpus_is_refused():
     r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode == 2 and r.stdout == b"" and b"WORLD_SIZE" in r.stderr
+
+
+@pytest.mark.gpu
+def test_a_plain_run_dumps_the_same_outputs_every_time(tmp_path):
+    """Two plain runs with the same arguments: the line carries the headline fields only and the outputs of the last
+    timed step are the same bits, however many steps the time-bounded prewarm ran."""
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "1"]
+    lines = []
+    for k in ("a", "b"):
+        r = _run(argv + ["--dump-outputs", str(tmp_path / k)], {}, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads(r.stdout.decode().strip().splitlines()[-1]))
+    for line in lines:
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"]
+        assert line["dtype"] == "f64" and line["unit"] == "particle-beam evals/s"
+        assert "roofline" not in line and "cpu_baseline" not in line and "other_configs" not in line
+    for name in ("samples", "filter_state"):
+        a, b = (np.load(tmp_path / k / (name + ".npy")) for k in ("a", "b"))
+        assert a.dtype == np.float64 and np.array_equal(a, b), name
+    samples = np.load(tmp_path / "a" / "samples.npy")
+    assert samples.shape == (lines[0]["config"]["resampled_to"], 4)
+    assert np.isfinite(samples).all() and abs(samples[:, 3].sum() - 1.0) < 1e-9
 
 
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="needs a machine WITHOUT a GPU")

@@ -1,7 +1,8 @@
 #!/bin/bash
 # samples the shader clock while the bench loop runs (diagnostic: is the scoring kernel clock / power limited?)
 cd $GRAFT_REPO_ROOT
-python bench.py --steps 20000 --warmup 5 --cpu-budget 0 > gpurun_out/clock_bench.json 2>/dev/null &
+J=$(mktemp --suffix=.json)
+python bench.py --full --steps 20000 --warmup 5 --cpu-budget 0 > $J 2>/dev/null &
 BP=$!
 sleep 8
 for i in $(seq 1 12); do
@@ -11,4 +12,4 @@ for i in $(seq 1 12); do
 done
 wait $BP
 python -c "
-import json; d=json.load(open('gpurun_out/clock_bench.json')); print(d['ms_per_step'], d['roofline']['kernel_ms'])"
+import json, sys; d=json.load(open(sys.argv[1])); print(d['ms_per_step'], d['roofline']['kernel_ms'])" $J

@@ -9,7 +9,7 @@ for round in 1 2; do
   for lib in "$@"; do
     if [ "$lib" = product ]; then unset BPF_LIB; else export BPF_LIB=$PWD/$lib; fi
     name=$(basename $lib .so)
-    python3 bench.py --steps 300 --warmup 50 --cpu-budget 0 --extras off --host-path off $FLAGS > $O/${name}_$round.json 2> $O/${name}_$round.err || exit 1
+    python3 bench.py --full --steps 300 --warmup 50 --cpu-budget 0 --extras off --host-path off $FLAGS > $O/${name}_$round.json 2> $O/${name}_$round.err || exit 1
     python3 - $O/${name}_$round.json $name <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

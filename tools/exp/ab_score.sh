@@ -8,7 +8,7 @@ O=gpurun_out/$TAG; mkdir -p $O
 for round in 1 2; do
   for v in base new; do
     if [ $v = base ]; then export BPF_LIB=$PWD/$BASE; else unset BPF_LIB; fi
-    python3 bench.py --steps 300 --warmup 50 --cpu-budget 0 --extras off --host-path off "$@" > $O/${v}_$round.json 2> $O/${v}_$round.err || exit 1
+    python3 bench.py --full --steps 300 --warmup 50 --cpu-budget 0 --extras off --host-path off "$@" > $O/${v}_$round.json 2> $O/${v}_$round.err || exit 1
     python3 - $O/${v}_$round.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
