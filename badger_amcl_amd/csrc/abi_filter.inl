@@ -242,6 +242,14 @@ int bpf_pf_update_sensor_planar(bpf_engine* e, const double* ranges, const doubl
   }
   SampleSet& s = e->sets[e->cur];
   const int n = e->sample_count;
+  if (ranges != nullptr && angles != nullptr && range_count > 0)
+  {
+    // Node2D keeps latest_scan_data_ for scorePose (BPF_POSE_CHECK_SENSOR_MODEL)
+    e->scan_ranges.assign(ranges, ranges + range_count);
+    e->scan_angles.assign(angles, angles + range_count);
+    e->scan_range_max = range_max;
+    e->have_scan = true;
+  }
   bool forced_zero = false;
   int rc = score_planar(e, s.dev(), n, e->converged, ranges, angles, range_count, range_max, &forced_zero, true);
   if (rc != BPF_OK)
@@ -289,9 +297,41 @@ int bpf_pf_set_random_pose_generator(bpf_engine* e, int mode)
 {
   if (!e)
     return BPF_ERR_INVALID_ARGUMENT;
-  if (mode != BPF_RANDOM_POSE_NONE && mode != BPF_RANDOM_POSE_FREE_SPACE_2D)
+  if (mode != BPF_RANDOM_POSE_NONE && mode != BPF_RANDOM_POSE_FREE_SPACE_2D && mode != BPF_RANDOM_POSE_FREE_SPACE_3D)
     return e->fail(BPF_ERR_INVALID_ARGUMENT, "unknown random pose generator");
   e->random_pose_mode = mode;
+  return BPF_OK;
+}
+
+int bpf_uniform_pose_retries(double g0, double m)
+{
+  if (!(g0 > 0.0 && m < 1.0 && m >= 0.0))
+    return 0;
+  // thr[k] = g0 m^k up to rounding (each product is correctly rounded: at least g0 (m (1 - 2^-53))^k); when even that
+  // lower bound stays above 1.0 at k = 2^30, the loop below would run to its end: say so at once
+  if (m > 0.0 && std::log(g0) + std::ldexp(1.0, 30) * (std::log(m) - 0x1p-52) > 1e-3)
+    return -1;
+  double thr = g0;
+  for (int k = 0; k < (1 << 30); ++k)
+  {
+    if (!(1.0 < thr))
+      return k;
+    thr *= m;
+  }
+  return -1;
+}
+
+int bpf_pf_set_uniform_pose_check(bpf_engine* e, double starting_weight_threshold, double deweight_multiplier,
+                                  int scoring)
+{
+  if (!e)
+    return BPF_ERR_INVALID_ARGUMENT;
+  if (scoring != BPF_POSE_CHECK_AS_REFERENCE && scoring != BPF_POSE_CHECK_SENSOR_MODEL)
+    return e->fail(BPF_ERR_INVALID_ARGUMENT, "unknown pose check scoring");
+  e->pose_check_g0 = starting_weight_threshold;
+  e->pose_check_m = deweight_multiplier;
+  e->pose_check_scoring = scoring;
+  e->pose_retries = bpf_uniform_pose_retries(starting_weight_threshold, deweight_multiplier);
   return BPF_OK;
 }
 

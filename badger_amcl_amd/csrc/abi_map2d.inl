@@ -70,6 +70,7 @@ int bpf_map2d_set(bpf_engine* e, const int32_t* cells, const float* dist_lut, in
   M.lut_tiles = nullptr;
   M.levels = nullptr;
   e->have_map = true;
+  e->have_scan = false;  // a new map clears the scan scorePose uses (node_2d.cpp:217)
   e->have_lut = false;
   e->map_version++;
   if (dist_lut)

@@ -273,10 +273,24 @@ int bpf_pf_init_with_random_poses(bpf_engine* e)
   if (rc != BPF_OK)
     return rc;
   const int n = e->max_samples;
+  // n back-to-back calls of Node::uniformPoseGenerator from element 1, 2 (retries + 1) elements each, or as many as
+  // the scored calls take (BPF_POSE_CHECK_SENSOR_MODEL)
+  uint64_t consumed = (2ull * (uint64_t)fs.retries + 2ull) * (uint64_t)n;
+  if (pose_check_scored(e))
+  {
+    unsigned end = 0;
+    rc = resolve_scored_calls(e, fs, e->rng, 1, n, &end);
+    if (rc != BPF_OK)
+      return rc;
+    fs.accept = e->d_accept.p;
+    consumed = (uint64_t)end - 1ull;
+  }
+  else if (consumed >= 0x7fffffffull)
+    return e->fail(BPF_ERR_CAPACITY, "random pose calls would pass 31-bit stream positions");
   hipLaunchKernelGGL(k_init_free_space, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, e->sets[e->cur].dev(), n,
                      e->rng, e->jump, fs, 1.0 / (double)n);
   HIPCHK(e, hipGetLastError());
-  e->rng = lcg_skip_host(e->rng, 2ull * (uint64_t)n, e->jump);
+  e->rng = lcg_skip_host(e->rng, consumed, e->jump);
   e->spread_init = true;  // uniform over the free space: scored in tile order until a resample says otherwise
   return finish_init(e, n);
 }

@@ -645,7 +645,10 @@ int bpf_shard_begin_resample(bpf_engine* e, uint64_t rng_state48, int leaf_count
   e->shard_w_diff = w_diff;
   e->shard_chain = false;
   e->shard_n_random = 0;
+  e->shard_retries = 0;
   e->shard_rng0 = rng_state48 & ((1ull << 48) - 1);
+  if (e->pose_check_scoring == BPF_POSE_CHECK_SENSOR_MODEL)
+    return e->fail(BPF_ERR_UNSUPPORTED, "BPF_POSE_CHECK_SENSOR_MODEL is not available on the sharded path");
   int count = resample_limit(leaf_count, e->min_samples, e->max_samples, e->pop_err, e->pop_z);
   if (w_diff > 0.0)
   {
@@ -655,6 +658,19 @@ int bpf_shard_begin_resample(bpf_engine* e, uint64_t rng_state48, int leaf_count
       if (count > e->max_samples)
         count = e->max_samples;
       e->shard_n_random = (int)(w_diff * count);
+      if (e->shard_n_random > 0)
+      {
+        FreeSpaceDev fs{};
+        int rc = ensure_free_space(e, &fs);
+        if (rc == BPF_OK && 1ll + (2ll * fs.retries + 2) * e->shard_n_random >= 0x7fffffffll)
+          rc = e->fail(BPF_ERR_CAPACITY, "random pose calls would pass 31-bit stream positions");
+        if (rc != BPF_OK)
+        {
+          e->shard_n_random = 0;
+          return rc;
+        }
+        e->shard_retries = fs.retries;
+      }
     }
     else
     {
@@ -664,7 +680,7 @@ int bpf_shard_begin_resample(bpf_engine* e, uint64_t rng_state48, int leaf_count
         return rc;
       const uint64_t keep = e->rng;
       e->rng = e->shard_rng0;
-      rc = build_draw_chain(e, w_diff, e->max_samples);
+      rc = build_draw_chain(e, w_diff, e->max_samples, fs.retries);
       e->rng = keep;
       if (rc != BPF_OK)
         return rc;
@@ -685,16 +701,16 @@ int bpf_shard_end_resample(bpf_engine* e, int sample_count, uint64_t* rng_state4
   HIPCHK(e, hipSetDevice(e->device));
   uint64_t consumed;
   if (e->resample_model == BPF_RESAMPLE_SYSTEMATIC)
-    consumed = 1ull + 2ull * (uint64_t)e->shard_n_random;
+    consumed = 1ull + (2ull * (uint64_t)e->shard_retries + 2ull) * (uint64_t)e->shard_n_random;
   else if (e->shard_chain)
   {
     if (sample_count > e->max_samples)
       return e->fail(BPF_ERR_INVALID_ARGUMENT, "sample_count beyond the chain");
     HIPCHK(e, e->h_chain_word.reserve(1));
-    HIPCHK(e, hipMemcpyAsync(e->h_chain_word.p, e->d_chain.p + sample_count, sizeof(int), hipMemcpyDeviceToHost,
-                             e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->h_chain_word.p, e->d_chain.p + (sample_count - 1), sizeof(int),
+                             hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    consumed = (uint64_t)((unsigned)e->h_chain_word.p[0] & 0x7fffffffu) - 1ull;
+    consumed = chain_consumed(e->h_chain_word.p[0]);
   }
   else
     consumed = 2ull * (uint64_t)sample_count;
@@ -703,6 +719,7 @@ int bpf_shard_end_resample(bpf_engine* e, int sample_count, uint64_t* rng_state4
     HIPCHK(e, hipMemsetAsync(&e->d_scalars.p->v[1], 0, 2 * sizeof(double), e->stream));
   e->shard_chain = false;
   e->shard_n_random = 0;
+  e->shard_retries = 0;
   return BPF_OK;
 }
 

@@ -291,10 +291,26 @@ struct bpf_engine
   double shard_w_diff = 0.0;        // of the sharded resample in progress (bpf_shard_begin_resample)
   bool shard_chain = false;         // its draw chain is in d_chain
   int shard_n_random = 0;           // systematic: random poses at the head of the new set
+  int shard_retries = 0;            //   and the trials each of their calls rejected
   uint64_t shard_rng0 = 0;
   DevBuf<uint64_t> d_chain_bits;
   DevBuf<int> d_chain_cnt, d_chain_exit, d_chain_entry, d_chain_base, d_chain;
   PinnedBuf<int> h_chain_word;
+  // Node::uniformPoseGenerator's score check (bpf_pf_set_uniform_pose_check): rejected trials per call, the same for
+  // every call in BPF_POSE_CHECK_AS_REFERENCE; -1 = the threshold table does not reach 1.0 within 2^30 trials
+  double pose_check_g0 = 0.0, pose_check_m = 0.0;
+  int pose_check_scoring = BPF_POSE_CHECK_AS_REFERENCE;
+  int pose_retries = 0;
+  // BPF_POSE_CHECK_SENSOR_MODEL: the last scan given to bpf_pf_update_sensor_planar (cleared by bpf_map2d_set, as the
+  // node clears latest_scan_data_, node_2d.cpp:217), the candidate set it scores and the resolved accept positions
+  bool have_scan = false;
+  std::vector<double> scan_ranges, scan_angles;
+  double scan_range_max = 0.0;
+  SampleSet cand;
+  DevBuf<unsigned> d_accept;
+  std::vector<unsigned> h_accept;
+  std::vector<int> h_chain;
+  std::vector<double> h_cand_scores;
 
   // ---- mailbox exchange of the sharded path (kernels_mailbox.hpp, abi_mailbox.inl)
   struct Mailbox

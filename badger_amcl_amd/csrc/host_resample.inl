@@ -154,13 +154,41 @@ int launch_converged(bpf_engine* e)
   return BPF_OK;
 }
 
-// Node2D::updateFreeSpaceIndices (node_2d.cpp:317-337) for the current map and non_free_space_radius, cached
+bool pose_check_scored(const bpf_engine* e);
+
+// Node2D::updateFreeSpaceIndices (node_2d.cpp:317-337) for the current map and non_free_space_radius, cached; or
+// Node3D::updateFreeSpaceIndices (node_3d.cpp:306-318) over the 3-D map's cell bounds.  out->retries = the trials
+// every call of Node::uniformPoseGenerator rejects (bpf_pf_set_uniform_pose_check).
 int ensure_free_space(bpf_engine* e, FreeSpaceDev* out)
 {
-  if (e->random_pose_mode != BPF_RANDOM_POSE_FREE_SPACE_2D)
+  if (e->random_pose_mode != BPF_RANDOM_POSE_FREE_SPACE_2D && e->random_pose_mode != BPF_RANDOM_POSE_FREE_SPACE_3D)
     return e->fail(BPF_ERR_UNSUPPORTED,
                    "w_diff > 0: random pose injection needs a pose generator (bpf_pf_set_random_pose_generator); "
                    "the node's random_pose_fn_ callback (particle_filter.cpp:385-388) cannot be called from here");
+  if (e->pose_check_scoring == BPF_POSE_CHECK_SENSOR_MODEL && e->cloud_configured && e->pose_check_g0 > 0.0 &&
+      e->pose_check_m < 1.0 && e->pose_check_m >= 0.0)
+    return e->fail(BPF_ERR_UNSUPPORTED, "BPF_POSE_CHECK_SENSOR_MODEL scores with the planar models only");
+  if (e->pose_retries < 0 && !pose_check_scored(e))
+    return e->fail(BPF_ERR_CAPACITY, "the uniform pose check's threshold table does not reach the score within "
+                                     "2^30 trials");
+  *out = FreeSpaceDev{};
+  out->retries = pose_check_scored(e) ? 0 : e->pose_retries;
+  if (e->random_pose_mode == BPF_RANDOM_POSE_FREE_SPACE_3D)
+  {
+    if (!e->have_map3d)
+      return e->fail(BPF_ERR_NOT_CONFIGURED, "random 3-D free-space poses need the 3-D map (bpf_map3d_set)");
+    const Map3dDev& M = e->map3;
+    const long long w = (long long)M.max_c[0] - M.min_c[0], h = (long long)M.max_c[1] - M.min_c[1];
+    if (w <= 0 || h <= 0)
+      return e->fail(BPF_ERR_NOT_CONFIGURED, "the 3-D map's cell bounds hold no column to draw random poses from");
+    out->ij = nullptr;
+    out->n = (int)(w * h);  // < (w + 1)(h + 1) = n_pose_indices < 2^30 (bpf_map3d_set)
+    out->min_i = M.min_c[0];
+    out->min_j = M.min_c[1];
+    out->rect_h = (int)h;
+    out->resolution = M.resolution;
+    return BPF_OK;
+  }
   if (!e->have_map || !e->have_lut)
     return e->fail(BPF_ERR_NOT_CONFIGURED, "random free-space poses need the 2-D map and its distance LUT");
   const double radius = e->pm.non_free_radius;
@@ -195,12 +223,177 @@ int ensure_free_space(bpf_engine* e, FreeSpaceDev* out)
   return BPF_OK;
 }
 
-// Where every candidate draw 0 .. max_draws finds its stream elements when w_diff > 0 (kernels_recovery.hpp)
-int build_draw_chain(bpf_engine* e, double w_diff, int max_draws)
+// ---- BPF_POSE_CHECK_SENSOR_MODEL: Node::uniformPoseGenerator with the score its parameter documents -- the weight of
+// the one-sample set {pose, 1.0} after applyModelToSampleSet with set->converged = 0 against the last planar scan.
+// The trial poses are scored on the device in windows (k_candidate_poses, then the planar scoring kernels on the
+// engine's candidate set); this thread runs the reference's loop over those scores, with good_weight *= m as the
+// loop forms it, and the tests of the multinomial chain from the drand48 recurrence.  Every loop here is bounded by
+// the 31-bit stream positions.
+bool pose_check_scored(const bpf_engine* e)
 {
-  const long long positions = 3ll * ((long long)max_draws + 1) + 3;
-  if (positions >= 0x7fffffffll)
+  const double g0 = e->pose_check_g0, m = e->pose_check_m;
+  return e->pose_check_scoring == BPF_POSE_CHECK_SENSOR_MODEL && e->have_scan && g0 > 0.0 && m < 1.0 && m >= 0.0;
+}
+
+constexpr unsigned kPosLimit = 0x7ffffff0u;  // stream positions a resolution may reach
+constexpr int kScoreWindow = 16384;          // trial poses per scoring launch
+
+struct TrialScores
+{
+  bpf_engine* e;
+  FreeSpaceDev F;
+  uint64_t rng0;
+  unsigned stride;
+  unsigned lo = 0, hi = 0;  // positions lo, lo + stride, ... < hi are scored
+
+  // the score of the trial whose pose takes stream elements pos, pos + 1
+  int score(unsigned pos, double* out)
+  {
+    if (pos < lo || pos >= hi)
+    {
+      long long cnt = ((long long)kPosLimit - pos) / stride;
+      if (cnt <= 0)
+        return e->fail(BPF_ERR_CAPACITY, "random pose calls would pass 31-bit stream positions");
+      const int n = (int)std::min<long long>(cnt, kScoreWindow);
+      HIPCHK(e, e->cand.reserve((size_t)n));
+      hipLaunchKernelGGL(k_candidate_poses, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, e->cand.dev(), n, pos,
+                         stride, rng0, e->jump, F);
+      HIPCHK(e, hipGetLastError());
+      // the scoring call resets the engine's per-set caches (partials, CDF hand-over); the candidate set is not the
+      // engine's set, so they are put back
+      const int fp = e->fused_partials, ts = e->tile_sums_n, cr = e->cdf_ready_n, cc = e->cdf_coarse_n;
+      const long long ev = e->evals_last;
+      bool forced_zero = false;
+      int rc = score_planar(e, e->cand.dev(), n, 0, e->scan_ranges.data(), e->scan_angles.data(),
+                            (int)e->scan_ranges.size(), e->scan_range_max, &forced_zero);
+      e->fused_partials = fp;
+      e->tile_sums_n = ts;
+      e->cdf_ready_n = cr;
+      e->cdf_coarse_n = cc;
+      e->evals_last = ev;
+      if (rc != BPF_OK)
+        return rc;
+      e->h_cand_scores.resize((size_t)n);
+      HIPCHK(e, hipMemcpyAsync(e->h_cand_scores.data(), e->cand.w.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
+                               e->stream));
+      HIPCHK(e, hipStreamSynchronize(e->stream));
+      lo = pos;
+      hi = pos + (unsigned)n * stride;
+    }
+    *out = e->h_cand_scores[(pos - lo) / stride];
+    return BPF_OK;
+  }
+
+  // one call of Node::uniformPoseGenerator (node.cpp:847-868) that starts at element p: *accepted = its pose's element
+  int call(unsigned p, unsigned* accepted)
+  {
+    double good = e->pose_check_g0;
+    const double m = e->pose_check_m;
+    unsigned t = p;
+    double sc = 0.0;
+    int rc = score(t, &sc);
+    while (rc == BPF_OK && sc < good)
+    {
+      t += 2;
+      rc = score(t, &sc);
+      good *= m;
+    }
+    *accepted = t;
+    return rc;
+  }
+};
+
+// n back-to-back calls from element `first`: e->h_accept[i] = call i's accepted element, *end = the element after the
+// last call
+int resolve_scored_calls(bpf_engine* e, const FreeSpaceDev& F, uint64_t rng0, unsigned first, int n, unsigned* end)
+{
+  if (e->cloud_configured)
+    return e->fail(BPF_ERR_UNSUPPORTED, "BPF_POSE_CHECK_SENSOR_MODEL scores with the planar models only");
+  TrialScores T{ e, F, rng0, 2 };
+  e->h_accept.resize((size_t)std::max(n, 1));
+  unsigned p = first;
+  for (int i = 0; i < n; ++i)
+  {
+    int rc = T.call(p, &e->h_accept[i]);
+    if (rc != BPF_OK)
+      return rc;
+    p = e->h_accept[i] + 2;
+  }
+  HIPCHK(e, e->d_accept.reserve((size_t)std::max(n, 1)));
+  if (n > 0)
+    H2D_OR_RETURN(h2d_from_host_sync(e, e->d_accept.p, e->h_accept.data(), (size_t)n * sizeof(unsigned)));
+  *end = p;
+  return BPF_OK;
+}
+
+// the multinomial draw chain (kernels_recovery.hpp's convention) for draws 0 .. max_draws - 1 with scored calls
+int resolve_scored_chain(bpf_engine* e, const FreeSpaceDev& F, double w_diff, int max_draws)
+{
+  if (e->cloud_configured)
+    return e->fail(BPF_ERR_UNSUPPORTED, "BPF_POSE_CHECK_SENSOR_MODEL scores with the planar models only");
+  TrialScores T{ e, F, e->rng, 1 };
+  e->h_chain.assign((size_t)max_draws + 1, 0);
+  unsigned q = 1;                                    // the current test
+  unsigned at = 1;                                   // x = element `at`
+  uint64_t x = lcg_skip_host(e->rng, 1, e->jump);
+  for (int m = 0; m < max_draws; ++m)
+  {
+    if (q >= kPosLimit)
+      return e->fail(BPF_ERR_CAPACITY, "draw chain would pass 31-bit stream positions");
+    if (q - at < 64)
+      for (; at < q; ++at)
+        x = (0x5DEECE66Dull * x + 0xBull) & ((1ull << 48) - 1);
+    else
+      x = lcg_skip_host(x, q - at, e->jump);
+    at = q;
+    if (std::ldexp((double)x, -48) < w_diff)
+    {
+      unsigned t = 0;
+      int rc = T.call(q + 1, &t);
+      if (rc != BPF_OK)
+        return rc;
+      e->h_chain[m] = (int)(t | 0x80000000u);
+      q = t + 2;
+    }
+    else
+    {
+      e->h_chain[m] = (int)(q + 1);
+      q += 2;
+    }
+  }
+  HIPCHK(e, e->d_chain.reserve((size_t)max_draws + 1));
+  H2D_OR_RETURN(h2d_from_host_sync(e, e->d_chain.p, e->h_chain.data(), ((size_t)max_draws + 1) * sizeof(int)));
+  return BPF_OK;
+}
+
+// stream elements the draws 0 .. m consumed, from chain[m]: up to r, or up to the second element of the accepted trial
+uint64_t chain_consumed(int chain_word)
+{
+  return (uint64_t)((unsigned)chain_word & 0x7fffffffu) + (chain_word < 0 ? 1ull : 0ull);
+}
+
+// Where every candidate draw 0 .. max_draws finds its stream elements when w_diff > 0 (kernels_recovery.hpp);
+// `retries` = FreeSpaceDev::retries
+int build_draw_chain(bpf_engine* e, double w_diff, int max_draws, int retries)
+{
+  const long long positions = (2ll * retries + 3) * ((long long)max_draws + 1) + 3;
+  if (retries < 0 || positions >= 0x7fffffffll)
     return e->fail(BPF_ERR_CAPACITY, "draw chain would pass 31-bit stream positions");
+  if (retries > 0)
+  {
+    HIPCHK(e, e->d_chain.reserve((size_t)max_draws + 1));
+    ChainArgs C{};
+    C.rng_state = e->rng;
+    C.w_diff = w_diff;
+    C.max_draws = max_draws;
+    C.chain = e->d_chain.p;
+    C.retries = retries;
+    C.jump = e->jump;
+    ProfScope ps(e, BPF_K_DRAW);
+    hipLaunchKernelGGL(k_chain_chase, dim3(1), dim3(64), 0, e->stream, C);
+    HIPCHK(e, hipGetLastError());
+    return BPF_OK;
+  }
   const int n_seg = (int)((positions + kChainSeg - 1) / kChainSeg);
   HIPCHK(e, e->d_chain_bits.reserve((size_t)2 * n_seg));
   HIPCHK(e, e->d_chain_cnt.reserve((size_t)3 * n_seg));
@@ -737,7 +930,8 @@ int resample_multinomial(bpf_engine* e, double w_diff)
     int rcf = ensure_free_space(e, &free_space);
     if (rcf != BPF_OK)
       return rcf;
-    rcf = build_draw_chain(e, w_diff, maxs);
+    rcf = pose_check_scored(e) ? resolve_scored_chain(e, free_space, w_diff, maxs)
+                               : build_draw_chain(e, w_diff, maxs, free_space.retries);
     if (rcf != BPF_OK)
       return rcf;
     chain = e->d_chain.p;
@@ -877,12 +1071,10 @@ int resample_multinomial(bpf_engine* e, double w_diff)
   // the window that found the stop also inserted nothing past it: hist is exactly set b's tree
   if (chain != nullptr)
   {
-    // the stream was consumed up to the element before draw M's test
     HIPCHK(e, e->h_chain_word.reserve(1));
-    HIPCHK(e, hipMemcpyAsync(e->h_chain_word.p, chain + M, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->h_chain_word.p, chain + (M - 1), sizeof(int), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    const unsigned next_test = (unsigned)e->h_chain_word.p[0] & 0x7fffffffu;
-    e->rng = lcg_skip_host(e->rng, (uint64_t)next_test - 1ull, e->jump);
+    e->rng = lcg_skip_host(e->rng, chain_consumed(e->h_chain_word.p[0]), e->jump);
   }
   else
     e->rng = lcg_skip_host(e->rng, 2ull * (uint64_t)M, e->jump);
@@ -900,6 +1092,7 @@ int resample_systematic(bpf_engine* e, double w_diff)
   int count = resample_limit(e->leaf_count, e->min_samples, e->max_samples, e->pop_err, e->pop_z);
   FreeSpaceDev free_space{};
   int num_random = 0;
+  uint64_t random_consumed = 0;  // stream elements of the random pose calls, after the systematic start
   if (w_diff > 0.0)
   {
     // particle_filter.cpp:295-306: room for random poses on top of the systematic ones
@@ -912,6 +1105,19 @@ int resample_systematic(bpf_engine* e, double w_diff)
       int rcf = ensure_free_space(e, &free_space);
       if (rcf != BPF_OK)
         return rcf;
+      if (pose_check_scored(e))
+      {
+        unsigned end = 0;
+        rcf = resolve_scored_calls(e, free_space, e->rng, 2, num_random, &end);
+        if (rcf != BPF_OK)
+          return rcf;
+        free_space.accept = e->d_accept.p;
+        random_consumed = (uint64_t)end - 2ull;
+      }
+      else if (1ll + (2ll * free_space.retries + 2) * num_random >= 0x7fffffffll)
+        return e->fail(BPF_ERR_CAPACITY, "random pose calls would pass 31-bit stream positions");
+      else
+        random_consumed = (2ull * (uint64_t)free_space.retries + 2ull) * (uint64_t)num_random;
     }
   }
   const int num_systematic = count - num_random;
@@ -1001,8 +1207,8 @@ int resample_systematic(bpf_engine* e, double w_diff)
     if (e->seen.first_time(k0, k1, k2))
       e->hist.insert(k0, k1, k2);
   }
-  // :316-324: the random poses took two uniforms each, right after the systematic start
-  e->rng = lcg_skip_host(e->rng, 2ull * (uint64_t)num_random, e->jump);
+  // :316-324: the random pose calls took 2 (retries + 1) uniforms each, right after the systematic start
+  e->rng = lcg_skip_host(e->rng, random_consumed, e->jump);
   e->resample_windows = 1;
   e->sample_count = count;
   return BPF_OK;

@@ -268,15 +268,15 @@ __global__ void k_init_gaussian(ParticlesDev dst, int n, const double* __restric
   dst.w[i] = weight;
 }
 
-// ParticleFilter::initWithPoseFn (particle_filter.cpp:135-163) with pose_fn = Node::randomFreeSpacePose:
-// sample i takes stream elements 2i+1, 2i+2
+// ParticleFilter::initWithPoseFn (particle_filter.cpp:135-163) with pose_fn = Node::uniformPoseGenerator:
+// back-to-back calls from stream element 1 on, sample i from call i's accepted trial (free_space_call_elem)
 __global__ void k_init_free_space(ParticlesDev dst, int n, uint64_t rng_state, LcgJump jump, FreeSpaceDev F,
                                   double weight)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n)
     return;
-  const uint64_t xs = lcg_skip(rng_state, 2ull * (uint64_t)i + 1ull, jump);
+  const uint64_t xs = lcg_skip(rng_state, free_space_call_elem(F, 1, i), jump);
   double x, y, th;
   random_free_space_pose(F, ldexp((double)xs, -48), ldexp((double)lcg_next(xs), -48), &x, &y, &th);
   dst.x[i] = x;

@@ -655,24 +655,50 @@ __device__ __forceinline__ uint64_t lcg_next(uint64_t x)
   return (0x5DEECE66Dull * x + 0xBull) & ((1ull << 48) - 1);
 }
 
-// Node::randomFreeSpacePose (node.cpp:823-845) from two uniforms, with OccupancyMap::convertMapToWorld
-// (occupancy_map.cpp:75-88); free_ij = Node2D::updateFreeSpaceIndices (node_2d.cpp:317-337)
+// Node::randomFreeSpacePose (node.cpp:823-845) from two uniforms.  2-D: free_ij = Node2D::updateFreeSpaceIndices
+// (node_2d.cpp:317-337) with OccupancyMap::convertMapToWorld (occupancy_map.cpp:75-88).  3-D (ij == nullptr): the
+// list of Node3D::updateFreeSpaceIndices (node_3d.cpp:306-318), every column of [min_i, min_i + n / rect_h) x
+// [min_j, min_j + rect_h), i outer and j inner, as rectangle arithmetic, with OctoMap::convertMapToWorld
+// (octomap.cpp:83-95: i * res, j * res).
+// Node::uniformPoseGenerator (node.cpp:847-868) with its score check active rejects the first `retries` trials of
+// every call (the reference's score is always 1.0, include/badger_pf.h): a call that starts at stream element p
+// takes its pose from elements p + 2 retries, p + 2 retries + 1 and consumes 2 (retries + 1) elements.
 struct FreeSpaceDev
 {
   const int2* ij;
   int n;
   int size_x, size_y;
   double origin_x, origin_y, resolution;
+  int min_i, min_j, rect_h;  // 3-D form
+  int retries;
+  const unsigned* accept;    // BPF_POSE_CHECK_SENSOR_MODEL: element of call i's accepted trial (resolved on the host)
 };
+
+// stream element of the accepted trial of call i in a run of calls that starts at element `first`
+__device__ __forceinline__ uint64_t free_space_call_elem(const FreeSpaceDev& F, uint64_t first, uint64_t i)
+{
+  if (F.accept != nullptr)
+    return F.accept[i];
+  return first + (2ull * (uint64_t)F.retries + 2ull) * i + 2ull * (uint64_t)F.retries;
+}
 
 __device__ __forceinline__ void random_free_space_pose(const FreeSpaceDev& F, double r1, double r2, double* x,
                                                        double* y, double* th)
 {
 #pragma clang fp contract(off)
   const unsigned idx = (unsigned)(r1 * F.n);
-  const int2 c = F.ij[idx];
-  *x = F.origin_x + (c.x - F.size_x / 2) * F.resolution;
-  *y = F.origin_y + (c.y - F.size_y / 2) * F.resolution;
+  if (F.ij != nullptr)
+  {
+    const int2 c = F.ij[idx];
+    *x = F.origin_x + (c.x - F.size_x / 2) * F.resolution;
+    *y = F.origin_y + (c.y - F.size_y / 2) * F.resolution;
+  }
+  else
+  {
+    const int i = F.min_i + (int)(idx / (unsigned)F.rect_h), j = F.min_j + (int)(idx % (unsigned)F.rect_h);
+    *x = i * F.resolution;
+    *y = j * F.resolution;
+  }
   *th = r2 * 2 * 3.14159265358979323846 - 3.14159265358979323846;
 }
 
@@ -700,8 +726,8 @@ struct DrawArgs
   unsigned* done_counter;       // device word, 0 between launches
   volatile unsigned* host_done; // pinned host word
   unsigned generation;
-  // w_diff > 0 (kernels_recovery.hpp): position of draw m's test element in the stream, bit 31 = the draw is
-  // a random free-space pose (nullptr: w_diff == 0, draw m tests element 2m+1 and takes r from 2m+2)
+  // w_diff > 0 (kernels_recovery.hpp): stream element draw m reads first (r, or the accepted trial's first
+  // element), bit 31 = the draw is a random free-space pose (nullptr: w_diff == 0, draw m tests element 2m+1 and takes r from 2m+2)
   const int* chain;
   FreeSpaceDev free_space;
   const int* guide;  // CDF guide table from k_scan_final (nullable)
@@ -719,10 +745,10 @@ __device__ __forceinline__ void draw_select_body(const DrawArgs& A)
   if (A.chain != nullptr)
   {
     const int c = A.chain[m];
-    xs = lcg_skip(A.rng_state, (uint64_t)(c & 0x7fffffff) + 1ull, A.jump);
+    xs = lcg_skip(A.rng_state, (uint64_t)(c & 0x7fffffff), A.jump);
     if (c < 0)
     {
-      // :385-388: random_pose_fn_() = Node::randomFreeSpacePose, the next two stream elements
+      // :385-388: random_pose_fn_(), the accepted trial's two stream elements
       const double r1 = ldexp((double)xs, -48), r2 = ldexp((double)lcg_next(xs), -48);
       double x, y, th;
       random_free_space_pose(A.free_space, r1, r2, &x, &y, &th);
@@ -911,8 +937,8 @@ __device__ __forceinline__ bool draw_window_column(const WindowArgs& A, int o, l
   {
     if (m < A.n_random)
     {
-      random = true;  // particle_filter.cpp:316-324: stream elements 2m+2, 2m+3 (element 1 is the start)
-      const uint64_t xs = lcg_skip(A.rng_state, 2ull * (uint64_t)m + 2ull, A.jump);
+      random = true;  // particle_filter.cpp:316-324: calls from element 2 on (element 1 is the start)
+      const uint64_t xs = lcg_skip(A.rng_state, free_space_call_elem(A.free_space, 2, m), A.jump);
       random_free_space_pose(A.free_space, ldexp((double)xs, -48), ldexp((double)lcg_next(xs), -48), &rx, &ry, &rth);
     }
     else
@@ -921,7 +947,7 @@ __device__ __forceinline__ bool draw_window_column(const WindowArgs& A, int o, l
   else if (A.chain != nullptr)
   {
     const int c = A.chain[m];
-    const uint64_t xs = lcg_skip(A.rng_state, (uint64_t)(c & 0x7fffffff) + 1ull, A.jump);
+    const uint64_t xs = lcg_skip(A.rng_state, (uint64_t)(c & 0x7fffffff), A.jump);
     if (c < 0)
     {
       random = true;  // :385-388
@@ -1098,7 +1124,8 @@ struct SystematicArgs
   volatile unsigned* host_done;
   unsigned generation;
   // w_diff > 0 (particle_filter.cpp:295-324): the first n_random samples are random free-space poses from stream
-  // elements 2i+2, 2i+3 (element 1 is the systematic start); targets[] then belongs to samples n_random ..
+  // calls from element 2 on (element 1 is the systematic start; free_space_call_elem); targets[] then belongs to
+  // samples n_random ..
   int n_random;
   uint64_t rng_state;
   LcgJump jump;
@@ -1116,7 +1143,7 @@ __global__ void k_systematic_select(const SystematicArgs A)
     int i = -1;
     if (m < A.n_random)
     {
-      const uint64_t xs = lcg_skip(A.rng_state, 2ull * (uint64_t)m + 2ull, A.jump);
+      const uint64_t xs = lcg_skip(A.rng_state, free_space_call_elem(A.free_space, 2, m), A.jump);
       random_free_space_pose(A.free_space, ldexp((double)xs, -48), ldexp((double)lcg_next(xs), -48), &x, &y, &th);
     }
     else

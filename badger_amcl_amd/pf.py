@@ -21,7 +21,8 @@ from . import _lib
 
 MODEL_BEAM, MODEL_LIKELIHOOD_FIELD, MODEL_LIKELIHOOD_FIELD_PROB, MODEL_LIKELIHOOD_FIELD_GOMPERTZ = 0, 1, 2, 3
 PF_RESAMPLE_MULTINOMIAL, PF_RESAMPLE_SYSTEMATIC = 0, 1
-RANDOM_POSE_NONE, RANDOM_POSE_FREE_SPACE_2D = 0, 1
+RANDOM_POSE_NONE, RANDOM_POSE_FREE_SPACE_2D, RANDOM_POSE_FREE_SPACE_3D = 0, 1, 2
+POSE_CHECK_AS_REFERENCE, POSE_CHECK_SENSOR_MODEL = 0, 1
 OPT_CDF_SERIAL, OPT_COUNT_CELLS, OPT_WINDOW_PATH, OPT_KLD_DEVICE_MIN, OPT_GRADED_SHARES = 0, 1, 2, 3, 4
 OPT_FUSED_RESAMPLE = 5
 OPT_CLOUD_DENSE = 6
@@ -284,8 +285,15 @@ class ParticleFilter:
         self.e.check(self.e.lib.bpf_pf_set_resample_model(self.e.h, model))
 
     def setRandomPoseGenerator(self, mode):
-        """random_pose_fn of the reference's constructor: RANDOM_POSE_FREE_SPACE_2D = Node::randomFreeSpacePose."""
+        """random_pose_fn of the reference's constructor: RANDOM_POSE_FREE_SPACE_2D = Node::randomFreeSpacePose over
+        Node2D's free-space list, RANDOM_POSE_FREE_SPACE_3D over Node3D's (the 3-D map's column rectangle)."""
         self.e.check(self.e.lib.bpf_pf_set_random_pose_generator(self.e.h, int(mode)))
+
+    def setUniformPoseCheck(self, threshold, multiplier, scoring=POSE_CHECK_AS_REFERENCE):
+        """Node::uniformPoseGenerator's score check (uniform_pose_starting_weight_threshold,
+        uniform_pose_deweight_multiplier); see bpf_pf_set_uniform_pose_check in include/badger_pf.h."""
+        self.e.check(self.e.lib.bpf_pf_set_uniform_pose_check(self.e.h, float(threshold), float(multiplier),
+                                                              int(scoring)))
 
     def setPopulationSizeParameters(self, pop_err, pop_z):
         self.e.check(self.e.lib.bpf_pf_set_population_size_parameters(self.e.h, pop_err, pop_z))
@@ -585,3 +593,9 @@ class PointCloudScanner:
         if status.value != 0:
             self.e.check(status.value)
         return total
+
+
+def uniform_pose_retries(threshold, multiplier):
+    """Trials every call of Node::uniformPoseGenerator rejects under POSE_CHECK_AS_REFERENCE (the reference's score
+    is always 1.0); -1 when that would pass 2^30.  Needs no GPU."""
+    return int(_lib.load().bpf_uniform_pose_retries(float(threshold), float(multiplier)))

@@ -274,6 +274,12 @@ class HipShardBackend:
     def max_beams(self):
         return getattr(self.sc, "max_beams", 2)
 
+    def set_random_pose_generator(self, mode):
+        self.pf.setRandomPoseGenerator(mode)
+
+    def set_uniform_pose_check(self, threshold, multiplier, scoring):
+        self.pf.setUniformPoseCheck(threshold, multiplier, scoring)
+
     def state(self):
         return self.pf.getState()
 
@@ -659,6 +665,16 @@ class ShardedFilter:
         self.totals = None
         self._fused_totals = False
         self.leaf_count = leaf_count
+
+    def set_random_pose_generator(self, mode):
+        """random_pose_fn of this rank's engine (pf.RANDOM_POSE_*); every rank sets the same mode.  Every rank
+        resolves the same draw chain, shard 0 writes the random poses."""
+        self.b.set_random_pose_generator(mode)
+
+    def set_uniform_pose_check(self, threshold, multiplier, scoring=0):
+        """Node::uniformPoseGenerator's score check on this rank's engine (pf.ParticleFilter.setUniformPoseCheck);
+        every rank sets the same values.  The sharded resample takes pf.POSE_CHECK_AS_REFERENCE only."""
+        self.b.set_uniform_pose_check(threshold, multiplier, scoring)
 
     def state(self):
         st = self.b.state()

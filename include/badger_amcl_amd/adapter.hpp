@@ -187,9 +187,17 @@ public:
   }
   void setResampleModel(PFResampleModelType m) { e_->check(bpf_pf_set_resample_model(e_->get(), m)); }
   // random_pose_fn of the reference's constructor: true = Node::randomFreeSpacePose on the device (badger_pf.h)
-  void setRandomFreeSpacePoseGenerator(bool on)
+  // three_d: over Node3D::updateFreeSpaceIndices (the 3-D map's column rectangle) instead of Node2D's list
+  void setRandomFreeSpacePoseGenerator(bool on, bool three_d = false)
   {
-    e_->check(bpf_pf_set_random_pose_generator(e_->get(), on ? BPF_RANDOM_POSE_FREE_SPACE_2D : BPF_RANDOM_POSE_NONE));
+    e_->check(bpf_pf_set_random_pose_generator(
+        e_->get(), !on ? BPF_RANDOM_POSE_NONE : three_d ? BPF_RANDOM_POSE_FREE_SPACE_3D : BPF_RANDOM_POSE_FREE_SPACE_2D));
+  }
+  // Node::uniformPoseGenerator's score check (uniform_pose_starting_weight_threshold, uniform_pose_deweight_multiplier)
+  void setUniformPoseCheck(double starting_weight_threshold, double deweight_multiplier,
+                           int scoring = BPF_POSE_CHECK_AS_REFERENCE)
+  {
+    e_->check(bpf_pf_set_uniform_pose_check(e_->get(), starting_weight_threshold, deweight_multiplier, scoring));
   }
   void setPopulationSizeParameters(double pop_err, double pop_z)
   {

@@ -204,13 +204,57 @@ int bpf_pf_update_sensor_planar(bpf_engine* e, const double* ranges, const doubl
  * a uniformly chosen cell of Node2D::updateFreeSpaceIndices (node_2d.cpp:317-337: FREE and further than
  * non_free_space_radius from an obstacle) and a uniform heading.  BPF_RANDOM_POSE_FREE_SPACE_2D evaluates exactly
  * that on the device from the engine's own 2-D map, drawing from the filter's drand48 stream in the reference's
- * order; with BPF_RANDOM_POSE_NONE (default) a resample that needs random poses returns BPF_ERR_UNSUPPORTED. */
+ * order; with BPF_RANDOM_POSE_NONE (default) a resample that needs random poses returns BPF_ERR_UNSUPPORTED.
+ * BPF_RANDOM_POSE_FREE_SPACE_3D is the same over Node3D::updateFreeSpaceIndices (node_3d.cpp:306-318): every
+ * (i, j) column with min_cells[0] <= i < max_cells[0] and min_cells[1] <= j < max_cells[1] of bpf_map3d_set, i outer
+ * and j inner, placed by OctoMap::convertMapToWorld (octomap.cpp:83-95: x = i * resolution, y = j * resolution, no
+ * origin, no half-cell offset).  It needs only the 3-D map.  All three consumers (initWithPoseFn and both
+ * resamplers' recovery draws) use the generator set here, with the score check of bpf_pf_set_uniform_pose_check. */
 enum
 {
   BPF_RANDOM_POSE_NONE = 0,
-  BPF_RANDOM_POSE_FREE_SPACE_2D = 1
+  BPF_RANDOM_POSE_FREE_SPACE_2D = 1,
+  BPF_RANDOM_POSE_FREE_SPACE_3D = 2
 };
 int bpf_pf_set_random_pose_generator(bpf_engine* e, int mode);
+/* The score check of Node::uniformPoseGenerator (node.cpp:847-868), parameters uniform_pose_starting_weight_threshold
+ * (g0) and uniform_pose_deweight_multiplier (m) (cfg/AMCL.cfg:35-36, node.cpp:124-125,255-256):
+ *     p = randomFreeSpacePose();
+ *     if (g0 > 0 && m < 1 && m >= 0)
+ *       while (scorePose(p) < good_weight) { p = randomFreeSpacePose(); good_weight *= m; }
+ * What the reference's score is: Node2D::scorePose (node_2d.cpp:298-316) copies the member PFSample fake_sample_
+ * (node_2d.h:99, a value) into fake_sample_set_->samples, scores that one-sample set and returns
+ * fake_sample_.weight, the untouched member: always 1.0, with or without a scan.  Node3D::scorePose does the same
+ * (node_3d.cpp:286-304, node_3d.h:105).  The loop is therefore a fixed number of rejected trials per call,
+ * K = min{k : !(1.0 < thr[k])} with thr[0] = g0, thr[k + 1] = thr[k] * m (repeated double multiplication), 0 when
+ * the check is inactive (a NaN g0 or m included).  A call that starts at stream element p takes its pose from
+ * elements p + 2K, p + 2K + 1 and consumes 2 (K + 1) elements; a recovery draw of the multinomial resampler then
+ * consumes 2K + 3.
+ *   scoring = BPF_POSE_CHECK_AS_REFERENCE (0): the score is 1.0, as the reference computes it.
+ *   scoring = BPF_POSE_CHECK_SENSOR_MODEL (1): opt-in score-guided recovery, the parameter's documented meaning
+ *             ("a pose with at least this sample weight according to the sensor model"): a trial's score is the
+ *             weight of the one-sample set {pose, 1.0} after applyModelToSampleSet with set->converged = 0 (no beam
+ *             skipping; recalcWeight iff that weight is > 0, planar_scanner.cpp:141-164) against the last scan given
+ *             to bpf_pf_update_sensor_planar (bpf_map2d_set clears it, as the node clears latest_scan_data_,
+ *             node_2d.cpp:217; with no scan every score is 1.0 and the result is AS_REFERENCE's).  The trial poses
+ *             are scored on the device in windows by the planar scoring kernels; the loop runs over those scores.
+ *             Parity-unpinned by construction; an accept decision can differ from a serial evaluation only where a
+ *             score lies within the kernels' rounding (<= 1e-9 relative) of its threshold.  Planar models only: with
+ *             the cloud scanner configured a call that draws random poses returns BPF_ERR_UNSUPPORTED, and so does
+ *             bpf_shard_begin_resample in this mode.
+ * The default is g0 = 0 (check inactive).  A call whose stream use would pass 31-bit positions (2 (K + 1) per random
+ * pose; 2K + 3 per candidate draw of the multinomial chain, for max_samples + 1 draws) returns BPF_ERR_CAPACITY and
+ * leaves the set and the drand48 state untouched; so does every call when K would pass 2^30.  The sharded path
+ * (bpf_shard_begin_resample) uses the same K. */
+enum
+{
+  BPF_POSE_CHECK_AS_REFERENCE = 0,
+  BPF_POSE_CHECK_SENSOR_MODEL = 1
+};
+int bpf_pf_set_uniform_pose_check(bpf_engine* e, double starting_weight_threshold, double deweight_multiplier,
+                                  int scoring);
+/* K of the AS_REFERENCE check above for (g0, m); -1 when it would pass 2^30.  Needs no engine. */
+int bpf_uniform_pose_retries(double starting_weight_threshold, double deweight_multiplier);
 /* Seam B: ParticleFilter::updateResample (particle_filter.cpp:423-471). */
 int bpf_pf_update_resample(bpf_engine* e);
 
@@ -471,7 +515,9 @@ int bpf_kld_feed_dev(bpf_engine* e, const void* window_dev, int stride, int n_ke
  * writes the random free-space poses; *systematic_count_out = resampleLimit(leaf_count), grown by (1 + w_diff)
  * (particle_filter.cpp:295-306), the `count` to pass to bpf_shard_systematic_window_dev, whose first
  * int(w_diff * count) samples are random poses.  end: the drand48 state after `sample_count` samples, and the
- * reset of the averages when w_diff > 0 (:453-455).  Needs bpf_pf_set_random_pose_generator when w_diff > 0. */
+ * reset of the averages when w_diff > 0 (:453-455).  Needs bpf_pf_set_random_pose_generator when w_diff > 0.
+ * The uniform pose check of bpf_pf_set_uniform_pose_check applies in its AS_REFERENCE form; with
+ * BPF_POSE_CHECK_SENSOR_MODEL begin returns BPF_ERR_UNSUPPORTED. */
 int bpf_shard_begin_resample(bpf_engine* e, uint64_t rng_state48, int leaf_count, double* w_diff_out,
                              int* systematic_count_out);
 int bpf_shard_end_resample(bpf_engine* e, int sample_count, uint64_t* rng_state48_out);
