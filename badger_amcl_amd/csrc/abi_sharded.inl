@@ -464,6 +464,7 @@ int shard_stop_block(bpf_engine* e, const long long* window, int stride, int cou
   e->fused_generation = (e->fused_generation % 0x3fffffff) + 1;
   A.generation = e->fused_generation;
   A.debug = getenv("BPF_DEBUG") != nullptr;
+  A.lds_tree = e->fused_lds_tree ? 1 : 0;
   if (draw != nullptr)
   {
     // mailbox mode: the draws of the window and their consumer in one launch (k_shard_resample_block)
@@ -920,6 +921,8 @@ int bpf_set_option(bpf_engine* e, int option, int value)
     e->graded_shares = value != 0;
   else if (option == BPF_OPT_FUSED_RESAMPLE)
     e->fused_resample = value != 0;
+  else if (option == BPF_OPT_FUSED_LDS_TREE)
+    e->fused_lds_tree = value != 0;
   else if (option == BPF_OPT_CLOUD_DENSE)
     e->cloud_dense = value != 0;
   else if (option == BPF_OPT_LUT_HOST)

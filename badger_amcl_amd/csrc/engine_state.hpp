@@ -246,6 +246,7 @@ struct bpf_engine
   DevBuf<unsigned long long> d_tile_slots;  // k_normalize_cdf's look-back slots, [2][256]
   unsigned tile_generation = 0;
   bool fused_resample = true; // BPF_OPT_FUSED_RESAMPLE
+  bool fused_lds_tree = false; // BPF_OPT_FUSED_LDS_TREE: the LDS form of the <= 64-key tree (tests)
   bool lut_exact_edt = false; // BPF_OPT_LUT_EXACT_EDT: implicit LUT builds take the device EDT instead of the reference's brushfire
   bool fused_lds_attr_set = false;
   bool shard_stop_attr_set = false;

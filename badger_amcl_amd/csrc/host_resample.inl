@@ -559,6 +559,7 @@ int resample_block(bpf_engine* e, int window, bool systematic, const double* tar
   e->fused_generation = (e->fused_generation % 0x3fffffff) + 1;
   A.generation = e->fused_generation;
   A.debug = getenv("BPF_DEBUG") != nullptr;
+  A.lds_tree = e->fused_lds_tree ? 1 : 0;
   {
     ProfScope ps(e, BPF_K_DRAW);
     hipLaunchKernelGGL(k_resample_block, dim3(blocks_for(window, kFusedDrawsPerBlock)), dim3(1024), kFusedLds,

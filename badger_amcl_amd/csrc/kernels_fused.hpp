@@ -316,6 +316,7 @@ struct ResampleBlockArgs
   volatile int* result_host;  // pinned: three result words (fused_publish)
   int generation;
   int debug;          // also copy the phase clocks out ([6], [8 ..])
+  int lds_tree;       // 1: the LDS form of the <= 64-key tree (BPF_OPT_FUSED_LDS_TREE)
 };
 
 // which side of node v key i goes to: split axis = largest |delta| between v's key and the first different key f
@@ -360,7 +361,8 @@ __device__ __forceinline__ int wave_incl_scan_int(int v)
 // The histogram tree of the window's distinct keys, level by level (kernels_kld.hpp): per level the earliest waiting
 // key on either side of every node becomes that node's child, the others step down to it.  Thread k holds tree key
 // s_list[k] (a draw index).  ONE_WAVE: at most 64 keys, wave 0 runs alone and LDS order within the wave replaces the
-// block barriers.  Returns the number of levels used (kFusedMaxLevels: gave up).
+// block barriers (BPF_OPT_FUSED_LDS_TREE only: fused_tree_regs grows the same tree in registers).  Returns the number
+// of levels used (kFusedMaxLevels: gave up).
 template <bool ONE_WAVE>
 __device__ __forceinline__ int fused_tree(int my, bool have, const unsigned long long* s_key, int* s_first,
                                           int* s_child, unsigned* s_nodelta)
@@ -419,6 +421,73 @@ __device__ __forceinline__ int fused_tree(int my, bool have, const unsigned long
     else if (!__syncthreads_or(still))
       break;
   }
+  return level;
+}
+
+// The same tree for at most 64 keys in wave 0's registers (the whole wave calls it).  Lane k holds tree key `my` (a
+// draw index, INT_MAX past n_bins) on entry; the keys are first put in draw order, so that "earliest" is "lowest lane"
+// and the root (draw 0) is lane 0.  Per level the lanes that share (node, side) are the node's group mask split by one
+// ballot of the sides; the lowest of them becomes the child and the others step down to it, where the next lowest is
+// the first key routed through the child and the rest is the child's group.  The node's key and its first key come by
+// lane permutes: no LDS traffic and no atomics inside the level loop.  On return `my` is this lane's key in draw order
+// and *nodelta tells whether its creation ended the parent's time as a leaf (fused_tree's s_nodelta bit).  Returns the
+// levels used.
+__device__ __forceinline__ int fused_tree_regs(int& my, int n_bins, const unsigned long long* s_key, bool* nodelta)
+{
+  const int lane = threadIdx.x & 63;
+  const bool have = lane < n_bins;
+  // rank among the keys by the bits of the draw index (< kFusedWindow = 2^12), high to low: `same` = the lanes equal
+  // to this one on the bits above b, those of them with a 0 where this lane has a 1 are smaller
+  static_assert(kFusedWindow <= (1 << 12), "draw indices must fit the rank's 12 bits");
+  unsigned long long same = __builtin_amdgcn_ballot_w64(have);
+  int rank = 0;
+#pragma unroll
+  for (int b = 11; b >= 0; --b)
+  {
+    const bool one = (my >> b) & 1;
+    const unsigned long long bits = __builtin_amdgcn_ballot_w64(one);
+    rank += one ? __popcll(same & ~bits) : 0;
+    same &= one ? bits : ~bits;
+  }
+  // (distinct draw indices: ranks 0 .. n_bins - 1 are a permutation; the empty lanes keep their own places)
+  my = __builtin_amdgcn_ds_permute((have ? rank : lane) << 2, my);
+  const unsigned long long mine = have ? s_key[my] : 0ull;
+  int cur = (have && lane != 0) ? 0 : -1;  // every tree key but the root's waits at the root ...
+  int fst = 1;                              // ... and the earliest of them is lane 1
+  unsigned long long kc = __shfl(mine, 0, 64), kf = __shfl(mine, 1, 64);
+  unsigned long long group = __builtin_amdgcn_ballot_w64(cur >= 0);  // the lanes waiting at this lane's node
+  bool nd = false;
+  int level = 0;
+  for (; level < kFusedMaxLevels; ++level)
+  {
+    const bool wait = cur >= 0;
+    const bool high = wait && fused_side(kc, kf, mine);
+    const unsigned long long highs = __builtin_amdgcn_ballot_w64(high);
+    const unsigned long long match = group & (high ? highs : ~highs);
+    const int child = __builtin_ctzll(match | (1ull << 63));  // (a waiting lane is in its own match set)
+    const unsigned long long rest = match & (match - 1ull);
+    bool still = false;
+    if (wait)
+    {
+      if (child == lane)
+      {
+        nd = fst == lane;
+        cur = -1;
+      }
+      else
+      {
+        cur = child;
+        fst = __builtin_ctzll(rest);  // rest holds this lane at least
+        group = rest;
+        still = true;
+      }
+    }
+    kc = __shfl(mine, cur < 0 ? lane : cur, 64);
+    kf = __shfl(mine, fst, 64);
+    if (__builtin_amdgcn_ballot_w64(still) == 0)
+      break;
+  }
+  *nodelta = nd;
   return level;
 }
 
@@ -513,7 +582,7 @@ __device__ __forceinline__ void fused_publish(volatile int* result_host, int gen
 // and the first draw m with m + 1 > resampleLimit(leaves so far) ends the set (particle_filter.cpp:411-417).  Leaves
 // S.leaf / S.bins / S.levels behind; *M_out = samples of the new set, *status_out = BPF_FUSED_*.
 __device__ __forceinline__ void fused_stop_rule(FusedStatics& S, const FusedLdsMap& L, int window, int systematic,
-                                                int max_samples, const bool (&act)[kFusedPerThread],
+                                                int max_samples, bool lds_tree, const bool (&act)[kFusedPerThread],
                                                 const unsigned long long (&pk)[kFusedPerThread], int* M_out,
                                                 int* status_out)
 {
@@ -571,9 +640,12 @@ __device__ __forceinline__ void fused_stop_rule(FusedStatics& S, const FusedLdsM
       }
     }
     __syncthreads();
-    for (int s = tid; s < 2 * W; s += 1024)
-      L.hash[s] = INT_MAX;
-    __syncthreads();
+    if (S.count > 64 || lds_tree)  // (the LDS trees' children live in the table; the register tree needs no LDS)
+    {
+      for (int s = tid; s < 2 * W; s += 1024)
+        L.hash[s] = INT_MAX;
+      __syncthreads();
+    }
   }
   const int n_bins = S.count;
   BPF_FUSED_STAMP(4);
@@ -583,7 +655,46 @@ __device__ __forceinline__ void fused_stop_rule(FusedStatics& S, const FusedLdsM
   {
     const bool have = tid < n_bins;
     const int my = have ? S.list[tid] : INT_MAX;
-    if (n_bins <= 64)
+    if (n_bins <= 64 && !lds_tree)
+    {
+      if (wave == 0)
+      {
+        // The stop rule straight from the tree keys in draw order (see the LDS form below): lane k's stretch of draws
+        // with constant leaf count runs from its key's first draw mk to the next lane's; leaves so far = the nodelta-
+        // free keys of lanes 0 .. k, bins so far = k + 1.
+        int mk = my;
+        bool nd;
+        const int lv = fused_tree_regs(mk, n_bins, L.key, &nd);
+        const unsigned long long upto = lane == 63 ? ~0ull : (2ull << lane) - 1ull;
+        const int leaf_k = __popcll(__builtin_amdgcn_ballot_w64(have && !nd) & upto);
+        const int bins_k = lane + 1;
+        const int nxt = __shfl(mk, min(lane + 1, 63), 64);
+        const int next_k = (lane + 1 < n_bins) ? nxt : window;
+        int cand = INT_MAX;
+        if (have && !systematic)
+        {
+          const int first_over = max(mk, S.limit[min(leaf_k, kFusedMaxBins)]);
+          if (first_over < next_k)
+            cand = first_over + 1;
+        }
+        // (a lane's candidate lies inside its own stretch and the stretches increase with the lane: the lowest lane
+        // with one holds the smallest)
+        const unsigned long long with = __builtin_amdgcn_ballot_w64(cand != INT_MAX);
+        cand = with ? __builtin_amdgcn_readlane(cand, __builtin_ctzll(with)) : INT_MAX;
+        const int M1 = (cand == INT_MAX ? window : cand) - 1;  // the last draw of the new set
+        if (have && mk <= M1 && M1 < next_k)
+        {
+          S.leaf = leaf_k;
+          S.bins = bins_k;
+        }
+        if (tid == 0)
+        {
+          S.levels = lv;
+          S.stop = cand;
+        }
+      }
+    }
+    else if (n_bins <= 64)
     {
       if (wave == 0)
       {
@@ -904,7 +1015,7 @@ __global__ __launch_bounds__(1024) void k_resample_block(const ResampleBlockArgs
   BPF_FUSED_STAMP(3);
 
   int M, status;
-  fused_stop_rule(S, L, A.window, A.systematic, A.max_samples, act, pk, &M, &status);
+  fused_stop_rule(S, L, A.window, A.systematic, A.max_samples, A.lds_tree != 0, act, pk, &M, &status);
   // The host needs (M, leaf count, bin count, status) and nothing of what follows: it gets them now and spends its
   // turn-around (its bookkeeping, the next launches, which the stream orders behind this one) while the block writes
   // the weights and counts the converged samples.
@@ -1003,6 +1114,7 @@ struct ShardStopArgs
   volatile int* result_host;  // pinned: three result words (fused_publish)
   int generation;
   int debug;
+  int lds_tree;             // 1: the LDS form of the <= 64-key tree (BPF_OPT_FUSED_LDS_TREE)
 };
 
 constexpr int BPF_FUSED_EXCHANGE = 5;  // the window did not arrive (mailbox time-out): nothing was written
@@ -1077,7 +1189,7 @@ __device__ __forceinline__ void shard_stop_body(const ShardStopArgs& A, FusedSta
   BPF_FUSED_STAMP(3);
 
   int M, status;
-  fused_stop_rule(S, L, A.count, A.systematic, A.max_samples, act, pk, &M, &status);
+  fused_stop_rule(S, L, A.count, A.systematic, A.max_samples, A.lds_tree != 0, act, pk, &M, &status);
   if (tid == 0 && !A.debug)
     fused_publish(out, A.generation, M, S.leaf, S.bins, status, S.levels);  // (the host's turn-around runs beside the tail)
 

@@ -313,6 +313,9 @@ enum
                                * promise that no buffer it passes is ever freed and allocated again at the same address
                                * while the engine lives (a stale pin reads old pages or faults).  Registered buffers
                                * (bpf_host_buffer_register) are always direct. */
+  BPF_OPT_FUSED_LDS_TREE = 16, /* default 0: the single-block resample grows a histogram tree of at most 64 keys in wave 0's
+                               * registers (cross-lane ballots, no LDS traffic inside the level loop); 1 = the LDS form
+                               * with atomics (a reference for tests).  Same tree, same results. */
   BPF_OPT_FUSED_RESAMPLE = 5  /* default 1: normalisation + CDF in one launch, and a resample whose candidate stream
                                * fits 4096 draws as one single-block launch (draws, KLD stop rule, weights,
                                * updateConverged); 0 = the separate launches with the host's ordered replay.
