@@ -67,6 +67,8 @@ SIGNATURES = {
     "bpf_pf_set_random_pose_generator": (C.c_int, [_vp, C.c_int]),
     "bpf_pf_set_uniform_pose_check": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int]),
     "bpf_uniform_pose_retries": (C.c_int, [C.c_double, C.c_double]),
+    "bpf_pf_set_kld_count": (C.c_int, [_vp, C.c_int]),
+    "bpf_pf_get_kld_count": (C.c_int, [_vp, _ip]),
     "bpf_pf_update_resample": (C.c_int, [_vp]),
     "bpf_set_option": (C.c_int, [_vp, C.c_int, C.c_int]),
     "bpf_get_cells_walked": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),

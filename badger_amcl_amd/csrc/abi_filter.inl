@@ -335,6 +335,32 @@ int bpf_pf_set_uniform_pose_check(bpf_engine* e, double starting_weight_threshol
   return BPF_OK;
 }
 
+int bpf_pf_set_kld_count(bpf_engine* e, int mode)
+{
+  if (!e)
+    return BPF_ERR_INVALID_ARGUMENT;
+  if (mode != BPF_KLD_COUNT_LEAVES && mode != BPF_KLD_COUNT_BINS)
+    return e->fail(BPF_ERR_INVALID_ARGUMENT, "unknown KLD count mode");
+  if (mode == e->kld_count_mode)
+    return BPF_OK;
+  e->kld_count_mode = mode;
+  if (e->have_pf && e->sample_count > 0)
+  {
+    // the current set's count was taken in the other mode: computed again when it is needed (bpf_pf_set_samples, -1)
+    e->leaf_count = e->bin_count = -1;
+    e->tree_pending = true;
+  }
+  return BPF_OK;
+}
+
+int bpf_pf_get_kld_count(const bpf_engine* e, int* mode_out)
+{
+  if (!e || !mode_out)
+    return BPF_ERR_INVALID_ARGUMENT;
+  *mode_out = e->kld_count_mode;
+  return BPF_OK;
+}
+
 int bpf_pf_update_resample(bpf_engine* e)
 {
   if (!e)
@@ -381,8 +407,13 @@ int bpf_pf_update_resample(bpf_engine* e)
   SampleSet& b = e->sets[e->cur ^ 1];
   e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
   e->cur ^= 1;
-  e->leaf_count = e->kld_device_used ? e->kld_leaf : e->hist.leaf_count();
-  e->bin_count = e->kld_device_used ? e->kld_bins : e->hist.bin_count();
+  if (kld_bins(e))
+    e->leaf_count = e->bin_count = e->kld_device_used ? e->kld_bins : e->kld_host_bins;
+  else
+  {
+    e->leaf_count = e->kld_device_used ? e->kld_leaf : e->hist.leaf_count();
+    e->bin_count = e->kld_device_used ? e->kld_bins : e->hist.bin_count();
+  }
   if (e->fused_used)
   {
     // k_resample_block already wrote the weights and counted the converged particles
@@ -414,7 +445,8 @@ int bpf_pf_update_resample(bpf_engine* e)
   // miss flag was copied? read it with the next fetch; report asynchronously via last_status
   e->last_status = BPF_OK;
   e->set_epoch++;
-  e->hist_matches_set = !e->kld_device_used;  // the device tree leaves no host histogram behind
+  // the device tree leaves no host histogram behind, nor does the host replay in BINS mode
+  e->hist_matches_set = !e->kld_device_used && !kld_bins(e);
   return BPF_OK;
 }
 

@@ -213,6 +213,8 @@ int build_set_tree(bpf_engine* e, int n)
     bins = e->hist.bin_count();
     e->hist_matches_set = true;
   }
+  if (kld_bins(e))
+    leaf = bins;
   e->leaf_count = leaf;
   e->bin_count = bins;
   return BPF_OK;

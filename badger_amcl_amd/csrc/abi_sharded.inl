@@ -437,11 +437,13 @@ int shard_stop_block(bpf_engine* e, const long long* window, int stride, int cou
       return rc;
   }
   HIPCHK(e, e->h_fused.reserve(32));
-  if (!e->shard_stop_attr_set)
+  const bool bins = kld_bins(e);  // BPF_KLD_COUNT_BINS: the stop rule on the distinct-key count
+  bool& stop_attr_set = bins ? e->shard_stop_bins_attr_set : e->shard_stop_attr_set;
+  if (!stop_attr_set)
   {
-    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(k_shard_stop_block),
+    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(bins ? k_shard_stop_block_bins : k_shard_stop_block),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds));
-    e->shard_stop_attr_set = true;
+    stop_attr_set = true;
   }
   SampleSet& b = e->sets[e->cur ^ 1];
   ShardStopArgs A{};
@@ -468,23 +470,26 @@ int shard_stop_block(bpf_engine* e, const long long* window, int stride, int cou
   if (draw != nullptr)
   {
     // mailbox mode: the draws of the window and their consumer in one launch (k_shard_resample_block)
-    if (!e->shard_resample_attr_set)
+    bool& resample_attr_set = bins ? e->shard_resample_bins_attr_set : e->shard_resample_attr_set;
+    if (!resample_attr_set)
     {
-      HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(k_shard_resample_block),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds));
-      e->shard_resample_attr_set = true;
+      HIPCHK(e, hipFuncSetAttribute(
+                    reinterpret_cast<const void*>(bins ? k_shard_resample_block_bins : k_shard_resample_block),
+                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds));
+      resample_attr_set = true;
     }
     ShardResampleArgs R{};
     R.W = *draw;
     R.S = A;
     ProfScope ps(e, BPF_K_DRAW);
-    hipLaunchKernelGGL(k_shard_resample_block, dim3(blocks_for(count, kFusedDrawsPerBlock)), dim3(1024), kFusedLds,
-                       e->stream, R);
+    hipLaunchKernelGGL(bins ? k_shard_resample_block_bins : k_shard_resample_block,
+                       dim3(blocks_for(count, kFusedDrawsPerBlock)), dim3(1024), kFusedLds, e->stream, R);
   }
   else
   {
     ProfScope ps(e, BPF_K_FINALIZE);
-    hipLaunchKernelGGL(k_shard_stop_block, dim3(1), dim3(1024), kFusedLds, e->stream, A);
+    hipLaunchKernelGGL(bins ? k_shard_stop_block_bins : k_shard_stop_block, dim3(1), dim3(1024), kFusedLds, e->stream,
+                       A);
   }
   HIPCHK(e, hipGetLastError());
   int r5[5] = { 0, 0, 0, 0, 0 };
@@ -563,8 +568,7 @@ int bpf_kld_reset(bpf_engine* e)
 {
   if (!e)
     return BPF_ERR_INVALID_ARGUMENT;
-  e->hist.clear();
-  e->seen.reset((size_t)std::min(std::max(e->max_samples, 1024), 1 << 20));
+  kld_host_reset(e, std::min(std::max(e->max_samples, 1024), 1 << 20));
   return BPF_OK;
 }
 
@@ -582,9 +586,8 @@ int bpf_kld_feed(bpf_engine* e, const void* keys, int keys_are_int64, int stride
     int k[3];
     for (int d = 0; d < 3; ++d)
       k[d] = keys_are_int64 ? (int)k64[(size_t)d * stride + q] : k32[(size_t)d * stride + q];
-    if (e->seen.first_time(k[0], k[1], k[2]))
-      e->hist.insert(k[0], k[1], k[2]);
-    const int lc = e->hist.leaf_count();
+    kld_host_insert(e, k[0], k[1], k[2]);
+    const int lc = kld_host_k(e);
     if (lc != cached_leaf)
     {
       cached_leaf = lc;
@@ -841,8 +844,7 @@ int bpf_kld_insert(bpf_engine* e, const void* keys, int keys_are_int64, int stri
     int k[3];
     for (int d = 0; d < 3; ++d)
       k[d] = keys_are_int64 ? (int)k64[(size_t)d * stride + q] : k32[(size_t)d * stride + q];
-    if (e->seen.first_time(k[0], k[1], k[2]))
-      e->hist.insert(k[0], k[1], k[2]);
+    kld_host_insert(e, k[0], k[1], k[2]);
   }
   return BPF_OK;
 }
@@ -899,9 +901,9 @@ int bpf_kld_leaf_count(bpf_engine* e, int* leaf_count_out, int* bin_count_out)
   if (!e)
     return BPF_ERR_INVALID_ARGUMENT;
   if (leaf_count_out)
-    *leaf_count_out = e->hist.leaf_count();
+    *leaf_count_out = kld_host_k(e);
   if (bin_count_out)
-    *bin_count_out = e->hist.bin_count();
+    *bin_count_out = kld_bins(e) ? e->kld_host_bins : e->hist.bin_count();
   return BPF_OK;
 }
 

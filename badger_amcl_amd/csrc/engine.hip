@@ -23,6 +23,7 @@
 #include "kernels_motion.hpp"
 #include "kernels_kld.hpp"
 #include "kernels_kld2.hpp"
+#include "kernels_kld_bins.hpp"
 #include "kernels_recovery.hpp"
 #include "kernels_pf.hpp"
 #include "kernels_fused.hpp"

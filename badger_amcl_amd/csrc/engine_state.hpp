@@ -365,6 +365,9 @@ struct bpf_engine
   int kld_device_min = 8192;  // draws left after the first window from which the device tree takes over
   bool kld_device_used = false;
   int kld_leaf = 0, kld_bins = 0;
+  int kld_count_mode = BPF_KLD_COUNT_LEAVES;  // bpf_pf_set_kld_count: what the stop rule's k counts
+  int kld_host_bins = 0;  // BINS mode: distinct keys the host replay has seen (e->seen first occurrences)
+  bool resample_bins_attr_set = false, shard_stop_bins_attr_set = false, shard_resample_bins_attr_set = false;
   DevBuf<unsigned long long> d_kld_hkey;
   DevBuf<int> d_kld_htmin, d_kld_slot, d_kld_cur, d_kld_first, d_kld_child, d_kld_flags, d_kld_limit;
   DevBuf<int2> d_kld_delta, d_kld_tiles, d_kld_counts;
@@ -380,7 +383,7 @@ struct bpf_engine
   const void* kld_clean_key = nullptr;
   const void* kld_clean_tmin = nullptr;
   size_t kld_clean_cap = 0;
-  int kld_last_form = 0;        // diagnostics: 2 = LDS pieces, 1 = level loop, 3 = persistent
+  int kld_last_form = 0;        // diagnostics: 2 = LDS pieces, 1 = level loop, 3 = persistent, 4 = bin count
   PinnedBuf<int> h_kld;
   std::vector<int> kld_limit_host;
   double kld_limit_key[4] = { -1, -1, -1, -1 };  // pop_err, pop_z, min_samples, max_samples of the cached table

@@ -1,5 +1,42 @@
 // Host half of normalisation and resampling: CDF, updateConverged, free-space list and draw chain (recovery),
 // KLD stop rule (device tree and ordered host replay), multinomial and systematic resamplers.
+// BPF_KLD_COUNT_BINS: the stop rule's k is the number of distinct histogram keys (bpf_pf_set_kld_count)
+bool kld_bins(const bpf_engine* e)
+{
+  return e->kld_count_mode == BPF_KLD_COUNT_BINS;
+}
+
+// a new ordered replay (e->seen, and the histogram tree or the distinct-key count)
+void kld_host_reset(bpf_engine* e, int expected)
+{
+  e->hist.clear();
+  e->seen.reset((size_t)expected);
+  e->kld_host_bins = 0;
+}
+
+// one key of an ordered replay: a first occurrence enters the histogram tree (LEAVES: e->seen is a cache in front of
+// the tree, which folds repeats itself) or only the count (BINS: the set's answer must be exact)
+bool kld_host_insert(bpf_engine* e, int x, int y, int t)
+{
+  if (kld_bins(e))
+  {
+    if (!e->seen.first_time_exact(x, y, t))
+      return false;
+    ++e->kld_host_bins;
+    return true;
+  }
+  if (!e->seen.first_time(x, y, t))
+    return false;
+  e->hist.insert(x, y, t);
+  return true;
+}
+
+// the stop rule's k for the keys the replay has seen
+int kld_host_k(const bpf_engine* e)
+{
+  return kld_bins(e) ? e->kld_host_bins : e->hist.leaf_count();
+}
+
 int fetch_scalars(bpf_engine* e)
 {
   HIPCHK(e, hipMemcpyAsync(e->h_scalars.p, e->d_scalars.p, sizeof(FilterScalars), hipMemcpyDeviceToHost, e->stream));
@@ -526,11 +563,13 @@ int resample_block(bpf_engine* e, int window, bool systematic, const double* tar
       return rc;
   }
   HIPCHK(e, e->h_fused.reserve(32));
-  if (!e->fused_lds_attr_set)
+  const bool bins = kld_bins(e);
+  bool& attr_set = bins ? e->resample_bins_attr_set : e->fused_lds_attr_set;
+  if (!attr_set)
   {
-    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(k_resample_block),
+    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(bins ? k_resample_block_bins : k_resample_block),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds));
-    e->fused_lds_attr_set = true;
+    attr_set = true;
   }
   int rcj = ensure_fused_jump(e);
   if (rcj != BPF_OK)
@@ -562,8 +601,8 @@ int resample_block(bpf_engine* e, int window, bool systematic, const double* tar
   A.lds_tree = e->fused_lds_tree ? 1 : 0;
   {
     ProfScope ps(e, BPF_K_DRAW);
-    hipLaunchKernelGGL(k_resample_block, dim3(blocks_for(window, kFusedDrawsPerBlock)), dim3(1024), kFusedLds,
-                       e->stream, A);
+    hipLaunchKernelGGL(bins ? k_resample_block_bins : k_resample_block, dim3(blocks_for(window, kFusedDrawsPerBlock)),
+                       dim3(1024), kFusedLds, e->stream, A);
   }
   HIPCHK(e, hipGetLastError());
   // the block publishes its result words in pinned memory (a ~25 us kernel)
@@ -595,6 +634,89 @@ int resample_block(bpf_engine* e, int window, bool systematic, const double* tar
   return BPF_OK;
 }
 
+// BINS mode: the stop rule over the whole stream [0, n) with k = distinct keys so far (kernels_kld_bins.hpp): the key
+// hash, then one look-back prefix count of the first occurrences with the stop test, and the result in pinned memory.
+// Same outputs as kld_tree_on_device below, with *leaf_out = *bins_out.
+int kld_bins_on_device(bpf_engine* e, int n, bool* handled, int* stop_out, int* leaf_out, int* bins_out,
+                       bool whole_stream)
+{
+  unsigned table = 1024;
+  while (table < 2u * (unsigned)n)
+    table <<= 1;
+  constexpr int kResultAt = 4 + 256;  // the pinned result words sit where the pieces form keeps its own
+  const int tiles = blocks_for(n, kKldTile);
+  HIPCHK(e, e->d_kld_hkey.reserve(table));
+  HIPCHK(e, e->d_kld_htmin.reserve(table));
+  HIPCHK(e, e->d_kld_slot.reserve((size_t)n));
+  HIPCHK(e, e->d_kld_counts.reserve((size_t)n));
+  HIPCHK(e, e->d_kld_flags.reserve(4));
+  HIPCHK(e, e->h_kld.reserve(kResultAt + 16));
+  if (e->d_kld2_slots.cap < (size_t)tiles)
+  {
+    HIPCHK(e, e->d_kld2_slots.reserve((size_t)std::max(tiles, 1024)));
+    HIPCHK(e, hipMemsetAsync(e->d_kld2_slots.p, 0, e->d_kld2_slots.cap * sizeof(unsigned long long), e->stream));
+  }
+  KldArgs K{};
+  K.keys = e->d_keys.p;
+  K.n = n;
+  K.h_key = e->d_kld_hkey.p;
+  K.h_tmin = e->d_kld_htmin.p;
+  K.h_mask = table - 1;
+  K.slot = e->d_kld_slot.p;
+  K.flags = e->d_kld_flags.p;
+  K.limit = e->d_kld_limit.p;
+  int* counts = reinterpret_cast<int*>(e->d_kld_counts.p);
+  e->kld_clean_table = 0;  // (the pieces form's start state is gone)
+  e->kld_last_form = 4;
+  e->kld_generation = (e->kld_generation % 0x3fffffff) + 1;
+  const int generation = e->kld_generation;
+  ProfScope ps(e, BPF_K_DRAW);
+  hipLaunchKernelGGL(k_kld_clear, dim3(std::min(1024, blocks_for((int)table, 256))), dim3(256), 0, e->stream, K, table,
+                     4, 0);
+  hipLaunchKernelGGL(k_kld_hash, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, K);
+  hipLaunchKernelGGL(k_kld_bins_scan, dim3(tiles), dim3(256), 0, e->stream, K, e->d_kld2_slots.p, (unsigned)generation,
+                     counts, K.flags + 3);
+  hipLaunchKernelGGL(k_kld_bins_result, dim3(1), dim3(64), 0, e->stream, K, (const int*)counts,
+                     (const int*)(K.flags + 3), whole_stream ? 1 : 0, e->h_kld.p + kResultAt, generation);
+  HIPCHK(e, hipGetLastError());
+  volatile unsigned long long* words = reinterpret_cast<volatile unsigned long long*>(e->h_kld.p + kResultAt);
+  int res[5] = { 0, 0, 0, 0, 0 };
+  auto all_there = [&]() {
+    for (int k = 1; k < 5; ++k)
+    {
+      const unsigned long long w = __atomic_load_n(const_cast<unsigned long long*>(words + k), __ATOMIC_ACQUIRE);
+      if ((unsigned)(w >> 32) != (unsigned)generation)
+        return false;
+      res[k] = (int)(unsigned)w;
+    }
+    return true;
+  };
+  const auto t0 = std::chrono::steady_clock::now();
+  bool seen = false;
+  for (unsigned spins = 0; !seen; ++spins)
+  {
+    seen = all_there();
+    if (!seen && (spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100))
+      break;
+    if (!seen)
+      __builtin_ia32_pause();
+  }
+  if (!seen)
+  {
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (!all_there())
+      return e->fail(BPF_ERR_HIP, "k_kld_bins_result did not publish its result");
+  }
+  if (getenv("BPF_DEBUG"))
+    fprintf(stderr, "[kld bins] n %d key range %d stop %d bins %d status %d\n", n, res[1], res[2], res[3], res[4]);
+  if (res[1] != 0 || res[4] != 0)
+    return BPF_OK;  // a key outside the packing range, or a look-back that timed out: not handled (host replay)
+  *stop_out = res[2];
+  *leaf_out = *bins_out = res[3];
+  *handled = true;
+  return BPF_OK;
+}
+
 // The KLD stop rule for the whole candidate stream [0, maxs) on the device (kernels_kld.hpp), keys in
 // e->d_keys (AoS): grows the histogram tree level by level and scans the leaf count.
 // Returns BPF_OK with *stop_out = stop count (or -1: no stop), *leaf_out / *bins_out at the final count;
@@ -610,6 +732,8 @@ int kld_tree_on_device(bpf_engine* e, int maxs, bool* handled, int* stop_out, in
   int rcl = ensure_limit_table(e, n);
   if (rcl != BPF_OK)
     return rcl;
+  if (kld_bins(e))
+    return kld_bins_on_device(e, n, handled, stop_out, leaf_out, bins_out, whole_stream);
   unsigned table = 1024;
   while (table < 2u * (unsigned)n)
     table <<= 1;
@@ -960,8 +1084,7 @@ int resample_multinomial(bpf_engine* e, double w_diff)
   HIPCHK(e, e->d_keys.reserve((size_t)maxs * 3));
   HIPCHK(e, e->d_src_index.reserve((size_t)maxs));
   HIPCHK(e, e->h_keys.reserve((size_t)maxs * 3));
-  e->hist.clear();
-  e->seen.reset((size_t)std::min(maxs, 1 << 20));
+  kld_host_reset(e, std::min(maxs, 1 << 20));
   int m0 = 0, stop = -1;
   int window = std::max(1024, std::min(e->window_hint, maxs));
   e->resample_windows = 0;
@@ -1047,10 +1170,9 @@ int resample_multinomial(bpf_engine* e, double w_diff)
       const int o = m - m0;
       const int k[3] = { k_stride ? keys[o] : keys[3 * o], k_stride ? keys[k_stride + o] : keys[3 * o + 1],
                          k_stride ? keys[2 * k_stride + o] : keys[3 * o + 2] };
-      if (e->seen.first_time(k[0], k[1], k[2]))
+      if (kld_host_insert(e, k[0], k[1], k[2]))
       {
-        e->hist.insert(k[0], k[1], k[2]);
-        const int lc = e->hist.leaf_count();
+        const int lc = kld_host_k(e);
         if (lc != cached_leaf)
         {
           cached_leaf = lc;
@@ -1169,9 +1291,11 @@ int resample_systematic(bpf_engine* e, double w_diff)
       return BPF_OK;
   }
   // the kernel reads the targets straight from the pinned buffer (28 KB for 3.5 k samples) and, like the
-  // multinomial draw kernel, leaves the keys in pinned memory behind a generation word
+  // multinomial draw kernel, leaves the keys in pinned memory behind a generation word -- or, for a large set in BINS
+  // mode, in e->d_keys, where the device counts the new set's distinct keys (the key hash and one scan)
   A.targets = e->h_targets.p;
-  const bool zero_copy = e->zero_copy_keys && count <= (1 << 20);
+  const bool device_count = kld_bins(e) && count >= 8192;
+  const bool zero_copy = e->zero_copy_keys && count <= (1 << 20) && !device_count;
   if (zero_copy)
   {
     A.host_keys = e->h_keys.p;
@@ -1185,6 +1309,23 @@ int resample_systematic(bpf_engine* e, double w_diff)
     hipLaunchKernelGGL(k_systematic_select, dim3(blocks_for(count, 256)), dim3(256), 0, e->stream, A);
   }
   HIPCHK(e, hipGetLastError());
+  if (device_count)
+  {
+    bool handled = false;
+    int stop = -1, leaf = 0, bins = 0;
+    int rc = kld_tree_on_device(e, count, &handled, &stop, &leaf, &bins, true);
+    if (rc != BPF_OK)
+      return rc;
+    if (handled)
+    {
+      e->kld_device_used = true;
+      e->kld_leaf = e->kld_bins = bins;
+      e->rng = lcg_skip_host(e->rng, random_consumed, e->jump);
+      e->resample_windows = 1;
+      e->sample_count = count;
+      return BPF_OK;
+    }
+  }
   int k_stride = count;
   if (!(zero_copy && wait_generation(e, A.generation)))
   {
@@ -1198,15 +1339,13 @@ int resample_systematic(bpf_engine* e, double w_diff)
       k_stride = 0;
     }
   }
-  e->hist.clear();
-  e->seen.reset((size_t)std::min(count, 1 << 20));
+  kld_host_reset(e, std::min(count, 1 << 20));
   const int* keys = e->h_keys.p;
   for (int m = 0; m < count; ++m)
   {
     const int k0 = k_stride ? keys[m] : keys[3 * m], k1 = k_stride ? keys[k_stride + m] : keys[3 * m + 1],
               k2 = k_stride ? keys[2 * k_stride + m] : keys[3 * m + 2];
-    if (e->seen.first_time(k0, k1, k2))
-      e->hist.insert(k0, k1, k2);
+    kld_host_insert(e, k0, k1, k2);
   }
   // :316-324: the random pose calls took 2 (retries + 1) uniforms each, right after the systematic start
   e->rng = lcg_skip_host(e->rng, random_consumed, e->jump);

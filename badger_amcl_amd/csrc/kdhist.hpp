@@ -11,6 +11,8 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <set>
+#include <tuple>
 #include <vector>
 
 namespace bpf
@@ -162,6 +164,7 @@ public:
       cur_ = 1;
     }
     used_ = 0;
+    overflow_.clear();
   }
 
   // true when the key was not in the set (and is now); keys outside +-2^20 bins are never cached
@@ -188,11 +191,39 @@ public:
     }
   }
 
+  // first_time for every key, exactly (what a distinct-key count needs): keys the table does not take -- outside
+  // +-2^20 bins, or once it is half full -- are looked up in the table and then kept in an ordered overflow set
+  bool first_time_exact(int x, int y, int t)
+  {
+    const int lim = 1 << 20;
+    const bool in_range = !(x < -lim || x >= lim || y < -lim || y >= lim || t < -lim || t >= lim);
+    if (in_range && used_ * 2 <= keys_.size())
+      return first_time(x, y, t);
+    if (in_range && contains(x, y, t))
+      return false;
+    return overflow_.insert(std::make_tuple(x, y, t)).second;
+  }
+
 private:
+  bool contains(int x, int y, int t) const
+  {
+    const int lim = 1 << 20;
+    const uint64_t k = ((uint64_t)(x + lim) << 42) | ((uint64_t)(y + lim) << 21) | (uint64_t)(t + lim);
+    const uint64_t h = k * 0x9E3779B97F4A7C15ull;
+    for (size_t i = (size_t)(h >> 20) & (keys_.size() - 1);; i = (i + 1) & (keys_.size() - 1))
+    {
+      if (gen_[i] != cur_)
+        return false;
+      if (keys_[i] == k)
+        return true;
+    }
+  }
+
   std::vector<uint64_t> keys_;
   std::vector<uint32_t> gen_;
   uint32_t cur_ = 0;
   size_t used_ = 0;
+  std::set<std::tuple<int, int, int>> overflow_;
 };
 
 // ParticleFilter::resampleLimit (particle_filter.cpp:475-502)

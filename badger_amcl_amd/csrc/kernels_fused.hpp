@@ -577,14 +577,73 @@ __device__ __forceinline__ void fused_publish(volatile int* result_host, int gen
                      __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// The BINS form of the stop rule below, behind the same folding of repeated keys (is_first): bins after every draw by
+// a prefix count of the first occurrences, and the first draw with m + 1 > resampleLimit(bins so far).  No tree, so
+// no bin-count or depth limit.  A window may hold up to kFusedWindow bins, beyond the 1 025 limits the LDS table
+// S.limit holds: they come from the global table (16 KB, cached; every thread reads the entries of its own four
+// counts), so this form takes no LDS beyond the LEAVES form's.  Leaves S.leaf = S.bins, S.levels = 0.
+__device__ __forceinline__ void fused_stop_bins(FusedStatics& S, int window, int systematic, int max_samples,
+                                                const int* __restrict__ limit, const bool (&act)[kFusedPerThread],
+                                                const bool (&is_first)[kFusedPerThread], int* M_out, int* status_out)
+{
+  constexpr int Q = kFusedPerThread;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m_base = tid * Q;
+  int p[Q];
+  int sum = 0;
+#pragma unroll
+  for (int q = 0; q < Q; ++q)
+  {
+    sum += is_first[q] ? 1 : 0;
+    p[q] = sum;
+  }
+  const int incl = wave_incl_scan_int(sum);
+  if (lane == 63)
+    S.wx[wave] = incl;
+  __syncthreads();
+  int before = incl - sum;
+#pragma unroll
+  for (int k = 0; k < 16; ++k)
+    before += (k < wave) ? S.wx[k] : 0;
+  if (!systematic && S.bad == 0)
+  {
+    int stop = INT_MAX;
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+      if (act[q] && stop == INT_MAX && m_base + q + 1 > limit[before + p[q]])  // particle_filter.cpp:416
+        stop = m_base + q + 1;
+    if (stop != INT_MAX)
+      atomicMin(&S.stop, stop);
+  }
+  __syncthreads();
+  int M = S.stop;
+  int status = S.bad;
+  if (M == INT_MAX)
+  {
+    M = window;
+    if (!systematic && window < max_samples && status == 0)
+      status = BPF_FUSED_NO_STOP;
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q)
+    if (m_base + q == M - 1)
+      S.leaf = S.bins = before + p[q];
+  __syncthreads();
+  BPF_FUSED_STAMP(6);
+  *M_out = M;
+  *status_out = status;
+}
+
 // The stop rule over the window's draws, for the block that holds all of them (keys in L.key, thread t owns draws
 // 4t .. 4t + 3: act / pk): repeated keys fold onto their first draw, the histogram tree grows over the distinct ones,
 // and the first draw m with m + 1 > resampleLimit(leaves so far) ends the set (particle_filter.cpp:411-417).  Leaves
 // S.leaf / S.bins / S.levels behind; *M_out = samples of the new set, *status_out = BPF_FUSED_*.
+// BINS (BPF_KLD_COUNT_BINS): k = distinct keys so far, no tree (fused_stop_bins); `limit` is the global table it reads.
+template <bool BINS>
 __device__ __forceinline__ void fused_stop_rule(FusedStatics& S, const FusedLdsMap& L, int window, int systematic,
                                                 int max_samples, bool lds_tree, const bool (&act)[kFusedPerThread],
                                                 const unsigned long long (&pk)[kFusedPerThread], int* M_out,
-                                                int* status_out)
+                                                int* status_out, const int* __restrict__ limit)
 {
   constexpr int W = kFusedWindow;
   constexpr int Q = kFusedPerThread;
@@ -640,7 +699,7 @@ __device__ __forceinline__ void fused_stop_rule(FusedStatics& S, const FusedLdsM
       }
     }
     __syncthreads();
-    if (S.count > 64 || lds_tree)  // (the LDS trees' children live in the table; the register tree needs no LDS)
+    if (!BINS && (S.count > 64 || lds_tree))  // (the LDS trees' children live in the table; the register tree needs no LDS)
     {
       for (int s = tid; s < 2 * W; s += 1024)
         L.hash[s] = INT_MAX;
@@ -649,6 +708,11 @@ __device__ __forceinline__ void fused_stop_rule(FusedStatics& S, const FusedLdsM
   }
   const int n_bins = S.count;
   BPF_FUSED_STAMP(4);
+  if constexpr (BINS)
+  {
+    fused_stop_bins(S, window, systematic, max_samples, limit, act, is_first, M_out, status_out);
+    return;
+  }
 
   // ---- the tree
   if (usable && n_bins <= kFusedMaxBins)
@@ -816,7 +880,8 @@ __device__ __forceinline__ void fused_stop_rule(FusedStatics& S, const FusedLdsM
 // grid = ceil(window / 128) blocks of 1024 threads.  Draw phase: block b takes draws 128 b .. 128 b + 127 (its first two
 // waves, one draw per lane; a CU's texture path takes about one cache line per clock, so 4096 random gathers want to be
 // spread over many CUs).  The block that finishes last then holds every key and runs the rest alone.
-__global__ __launch_bounds__(1024) void k_resample_block(const ResampleBlockArgs A)
+template <bool BINS>
+__device__ __forceinline__ void resample_block_body(const ResampleBlockArgs& A)
 {
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ FusedStatics S;
@@ -1015,7 +1080,7 @@ __global__ __launch_bounds__(1024) void k_resample_block(const ResampleBlockArgs
   BPF_FUSED_STAMP(3);
 
   int M, status;
-  fused_stop_rule(S, L, A.window, A.systematic, A.max_samples, A.lds_tree != 0, act, pk, &M, &status);
+  fused_stop_rule<BINS>(S, L, A.window, A.systematic, A.max_samples, A.lds_tree != 0, act, pk, &M, &status, A.limit);
   // The host needs (M, leaf count, bin count, status) and nothing of what follows: it gets them now and spends its
   // turn-around (its bookkeeping, the next launches, which the stream orders behind this one) while the block writes
   // the weights and counts the converged samples.
@@ -1088,6 +1153,17 @@ __global__ __launch_bounds__(1024) void k_resample_block(const ResampleBlockArgs
   }
 }
 
+__global__ __launch_bounds__(1024) void k_resample_block(const ResampleBlockArgs A)
+{
+  resample_block_body<false>(A);
+}
+
+// BPF_KLD_COUNT_BINS: the stop rule on the distinct-key count (fused_stop_bins)
+__global__ __launch_bounds__(1024) void k_resample_block_bins(const ResampleBlockArgs A)
+{
+  resample_block_body<true>(A);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Sharded filter: the same stop rule for a draw window that every shard holds after the exchange (rows x, y, theta as
 // double bits and three int64 key rows; k_draw_window stored this shard's columns into all peers, or an integer
@@ -1119,7 +1195,8 @@ struct ShardStopArgs
 
 constexpr int BPF_FUSED_EXCHANGE = 5;  // the window did not arrive (mailbox time-out): nothing was written
 
-// the body of k_shard_stop_block (every thread of the 1 024-thread block calls it)
+// the body of k_shard_stop_block (every thread of the 1 024-thread block calls it); BINS: fused_stop_bins
+template <bool BINS>
 __device__ __forceinline__ void shard_stop_body(const ShardStopArgs& A, FusedStatics& S, const FusedLdsMap& L)
 {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1189,7 +1266,7 @@ __device__ __forceinline__ void shard_stop_body(const ShardStopArgs& A, FusedSta
   BPF_FUSED_STAMP(3);
 
   int M, status;
-  fused_stop_rule(S, L, A.count, A.systematic, A.max_samples, A.lds_tree != 0, act, pk, &M, &status);
+  fused_stop_rule<BINS>(S, L, A.count, A.systematic, A.max_samples, A.lds_tree != 0, act, pk, &M, &status, A.limit);
   if (tid == 0 && !A.debug)
     fused_publish(out, A.generation, M, S.leaf, S.bins, status, S.levels);  // (the host's turn-around runs beside the tail)
 
@@ -1269,7 +1346,15 @@ __global__ __launch_bounds__(1024) void k_shard_stop_block(const ShardStopArgs A
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ FusedStatics S;
   const FusedLdsMap L = fused_lds_map(smem);
-  shard_stop_body(A, S, L);
+  shard_stop_body<false>(A, S, L);
+}
+
+__global__ __launch_bounds__(1024) void k_shard_stop_block_bins(const ShardStopArgs A)
+{
+  extern __shared__ __align__(16) unsigned char smem[];
+  __shared__ FusedStatics S;
+  const FusedLdsMap L = fused_lds_map(smem);
+  shard_stop_body<true>(A, S, L);
 }
 
 // Mailbox mode, tracking regime: the draw window AND its consumer in one launch.  grid = ceil(draws / 128) blocks; every
@@ -1283,7 +1368,8 @@ struct ShardResampleArgs
   ShardStopArgs S;
 };
 
-__global__ __launch_bounds__(1024) void k_shard_resample_block(const ShardResampleArgs A)
+template <bool BINS>
+__device__ __forceinline__ void shard_resample_body(const ShardResampleArgs& A)
 {
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ FusedStatics S;
@@ -1343,7 +1429,17 @@ __global__ __launch_bounds__(1024) void k_shard_resample_block(const ShardResamp
   __syncthreads();
   if (!S.last)
     return;
-  shard_stop_body(A.S, S, L);
+  shard_stop_body<BINS>(A.S, S, L);
+}
+
+__global__ __launch_bounds__(1024) void k_shard_resample_block(const ShardResampleArgs A)
+{
+  shard_resample_body<false>(A);
+}
+
+__global__ __launch_bounds__(1024) void k_shard_resample_block_bins(const ShardResampleArgs A)
+{
+  shard_resample_body<true>(A);
 }
 
 }  // namespace bpf

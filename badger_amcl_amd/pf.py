@@ -23,6 +23,9 @@ MODEL_BEAM, MODEL_LIKELIHOOD_FIELD, MODEL_LIKELIHOOD_FIELD_PROB, MODEL_LIKELIHOO
 PF_RESAMPLE_MULTINOMIAL, PF_RESAMPLE_SYSTEMATIC = 0, 1
 RANDOM_POSE_NONE, RANDOM_POSE_FREE_SPACE_2D, RANDOM_POSE_FREE_SPACE_3D = 0, 1, 2
 POSE_CHECK_AS_REFERENCE, POSE_CHECK_SENSOR_MODEL = 0, 1
+# what the KLD stop rule counts (bpf_pf_set_kld_count): the reference's tree leaves (default), or the distinct
+# histogram bins of KLD-sampling and upstream AMCL (opt-in, parity unpinned by construction)
+KLD_COUNT_LEAVES, KLD_COUNT_BINS = 0, 1
 OPT_CDF_SERIAL, OPT_COUNT_CELLS, OPT_WINDOW_PATH, OPT_KLD_DEVICE_MIN, OPT_GRADED_SHARES = 0, 1, 2, 3, 4
 OPT_FUSED_RESAMPLE = 5
 OPT_CLOUD_DENSE = 6
@@ -295,6 +298,17 @@ class ParticleFilter:
         uniform_pose_deweight_multiplier); see bpf_pf_set_uniform_pose_check in include/badger_pf.h."""
         self.e.check(self.e.lib.bpf_pf_set_uniform_pose_check(self.e.h, float(threshold), float(multiplier),
                                                               int(scoring)))
+
+    def setKldCount(self, mode):
+        """KLD_COUNT_LEAVES (default, the reference's PFKDTree::getLeafCount) or KLD_COUNT_BINS (distinct histogram
+        bins, as in KLD-sampling; parity unpinned by construction).  Takes effect at the next resample; in BINS mode
+        every leaf count the filter reports or takes is a bin count.  See bpf_pf_set_kld_count."""
+        self.e.check(self.e.lib.bpf_pf_set_kld_count(self.e.h, int(mode)))
+
+    def getKldCount(self):
+        m = C.c_int(0)
+        self.e.check(self.e.lib.bpf_pf_get_kld_count(self.e.h, C.byref(m)))
+        return m.value
 
     def setPopulationSizeParameters(self, pop_err, pop_z):
         self.e.check(self.e.lib.bpf_pf_set_population_size_parameters(self.e.h, pop_err, pop_z))

@@ -280,6 +280,12 @@ class HipShardBackend:
     def set_uniform_pose_check(self, threshold, multiplier, scoring):
         self.pf.setUniformPoseCheck(threshold, multiplier, scoring)
 
+    def set_kld_count(self, mode):
+        self.pf.setKldCount(mode)
+
+    def kld_count(self):
+        return self.pf.getKldCount()
+
     def state(self):
         return self.pf.getState()
 
@@ -293,7 +299,9 @@ class ShardedFilter:
     """ParticleFilter::updateSensor / updateResample over W shards (see module docstring)."""
 
     def __init__(self, backend, dist, rank=None, world=None, first_window=4096, exchange="auto",
-                 mailbox_timeout_ms=None):
+                 mailbox_timeout_ms=None, kld_count=None):
+        """kld_count: what the KLD stop rule counts, pf.KLD_COUNT_LEAVES or pf.KLD_COUNT_BINS (None: the backend's
+        current mode).  Every rank must use the same mode; the constructor checks it over the process group."""
         self.b = backend
         self.mailbox_timeout_ms = mailbox_timeout_ms
         self.recoveries = 0  # exchanges that ran out of time and were finished over the collectives
@@ -309,6 +317,13 @@ class ShardedFilter:
         self.max_global = backend.max_samples()  # engines are created with the GLOBAL min / max sample counts
         n = torch.tensor([backend.n_local()], dtype=torch.int64, device=self.device)
         self.counts = [int(v) for v in self._all_gather(n).cpu().tolist()]
+        # every rank computes the same stop rule from the same window, so every rank must count the same way
+        if kld_count is not None:
+            backend.set_kld_count(int(kld_count))
+        self.kld_count = int(backend.kld_count()) if hasattr(backend, "kld_count") else 0
+        modes = self._all_gather(torch.tensor([self.kld_count], dtype=torch.int64, device=self.device)).cpu().tolist()
+        if len(set(int(m) for m in modes)) != 1:
+            raise ValueError("ShardedFilter: the ranks use different KLD count modes %s" % modes)
         self.window_hint = first_window
         self.out = torch.zeros((3, self.max_global), dtype=torch.float64, device=self.device)
         self.flags = torch.zeros(4, dtype=torch.int32, device=self.device)

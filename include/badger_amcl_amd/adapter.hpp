@@ -199,6 +199,15 @@ public:
   {
     e_->check(bpf_pf_set_uniform_pose_check(e_->get(), starting_weight_threshold, deweight_multiplier, scoring));
   }
+  // what the KLD stop rule counts: BPF_KLD_COUNT_LEAVES (default, the reference's) or BPF_KLD_COUNT_BINS (distinct
+  // histogram bins, parity unpinned by construction); see bpf_pf_set_kld_count
+  void setKldCount(int mode) { e_->check(bpf_pf_set_kld_count(e_->get(), mode)); }
+  int getKldCount() const
+  {
+    int mode = BPF_KLD_COUNT_LEAVES;
+    e_->check(bpf_pf_get_kld_count(e_->get(), &mode));
+    return mode;
+  }
   void setPopulationSizeParameters(double pop_err, double pop_z)
   {
     e_->check(bpf_pf_set_population_size_parameters(e_->get(), pop_err, pop_z));

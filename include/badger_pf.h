@@ -121,7 +121,8 @@ int bpf_host_buffer_is_registered(bpf_engine* e, const void* ptr, size_t bytes);
  * (BPF_OPT_TILE_SORT), 0 otherwise */
 int bpf_score_last_form(bpf_engine* e, int* form_out);
 /* which form the last device-side histogram tree took: 2 = grown in LDS-sized pieces (kernels_kld2.hpp), 1 = one launch
- * pair per level (also after the pieces declined a stream), 3 = the persistent launch, 0 = none yet */
+ * pair per level (also after the pieces declined a stream), 3 = the persistent launch, 4 = no tree: the distinct-key
+ * count of BPF_KLD_COUNT_BINS (bpf_pf_set_kld_count), 0 = none yet */
 int bpf_kld_last_form(bpf_engine* e, int* form_out);
 /* what the last bpf_planar_apply_model_to_sample_set did: chunks of the pipelined form (0 = the plain upload / score /
  * download sequence, -1 = one scoring launch that read and wrote the registered records in place); pinned = the buffer
@@ -255,6 +256,27 @@ int bpf_pf_set_uniform_pose_check(bpf_engine* e, double starting_weight_threshol
                                   int scoring);
 /* K of the AS_REFERENCE check above for (g0, m); -1 when it would pass 2^30.  Needs no engine. */
 int bpf_uniform_pose_retries(double starting_weight_threshold, double deweight_multiplier);
+/* What the KLD stop rule counts as k (particle_filter.cpp:411-417 and :276 call resampleLimit(k)).
+ *   BPF_KLD_COUNT_LEAVES (0, default): the reference's k, PFKDTree::getLeafCount -- the childless nodes of the
+ *     insertion-ordered histogram tree.  Bit-exact with the reference.
+ *   BPF_KLD_COUNT_BINS (1, opt-in): k = the number of distinct histogram keys, key = floor(pose / {0.5 m, 0.5 m,
+ *     10 deg}) with theta not normalised, as in Fox's KLD-sampling and upstream AMCL.  Parity unpinned by
+ *     construction: no reference run computes it.  Multinomial: after draw m (0-based) the set stops when
+ *     m + 1 > resampleLimit(distinct keys among draws 0 .. m).  Systematic: the set size is resampleLimit(distinct
+ *     keys of the current set), grown by (1 + w_diff) as before.  The drand48 stream, the draws, the recovery
+ *     branch and the uniform pose check are unchanged.  Every leaf count the engine reports or accepts is then a
+ *     bin count: bpf_pf_state.leaf_count == bin_count, the leaf_count argument of bpf_pf_set_samples (-1 still
+ *     computes it), leaf_count_io of the bpf_shard_* resample calls and the bpf_kld_* stage calls.
+ * The mode belongs to the engine, not to a filter: bpf_pf_create does not reset it, so a filter created on an engine
+ * switched to BINS counts bins.  A change of mode takes effect at the next resample and marks the current set's count
+ * stale, as bpf_pf_set_samples(..., -1) does.  Other values return BPF_ERR_INVALID_ARGUMENT and leave the mode. */
+enum
+{
+  BPF_KLD_COUNT_LEAVES = 0,
+  BPF_KLD_COUNT_BINS = 1
+};
+int bpf_pf_set_kld_count(bpf_engine* e, int mode);
+int bpf_pf_get_kld_count(const bpf_engine* e, int* mode_out);
 /* Seam B: ParticleFilter::updateResample (particle_filter.cpp:423-471). */
 int bpf_pf_update_resample(bpf_engine* e);
 
