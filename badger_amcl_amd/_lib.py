@@ -120,6 +120,13 @@ SIGNATURES = {
     "bpf_shard_tail_small_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bpf_shard_adopt_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bpf_shard_converged_dev": (C.c_int, [_vp, _vp, _vp, C.c_int]),
+    "bpf_shard_samples_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _ip]),
+    "bpf_shard_stats_gathered_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _ip]),
+    "bpf_shard_stats_local_bins_dev": (C.c_int, [_vp, C.c_longlong, C.POINTER(_vp), _ip, _ip]),
+    "bpf_shard_stats_label_dev": (C.c_int, [_vp, _vp, _ip, C.c_int, C.c_int, _ip]),
+    "bpf_shard_stats_local_sums_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    "bpf_shard_stats_finish_dev": (C.c_int, [_vp, _vp]),
+    "bpf_shard_stats_host": (C.c_int, [_vp, _dp, C.c_int]),
     "bpf_shard_mailbox_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_longlong, _vp]),
     "bpf_shard_mailbox_connect": (C.c_int, [_vp, _vp]),
     "bpf_shard_mailbox_selftest": (C.c_int, [_vp, C.c_int]),

@@ -60,6 +60,7 @@ int bpf_shard_score_planar(bpf_engine* e, const double* ranges, const double* an
                         &forced_zero, true, true);
   if (rc != BPF_OK)
     return rc;
+  e->set_epoch++;  // the weights change (or are about to): cached statistics no longer describe the slice
   if (e->skip_pending)
     return BPF_SHARD_NEED_BEAM_COUNTS;  // sum bpf_shard_beam_counts_dev over the shards, then ..._finish
   return shard_local_total(e);
@@ -90,6 +91,7 @@ int bpf_shard_score_planar_finish(bpf_engine* e, const double* ranges, const dou
                                         range_max, &forced_zero, true);
   if (rc != BPF_OK)
     return rc;
+  e->set_epoch++;
   return shard_local_total(e);
 }
 
@@ -107,6 +109,7 @@ int bpf_shard_score_cloud(bpf_engine* e, const float* points_xyz, int n_points)
   int rc = score_cloud(e, s.dev(), e->sample_count, points_xyz, n_points);
   if (rc != BPF_OK)
     return rc;
+  e->set_epoch++;
   return shard_sum_and_post(e, s.w.p, e->sample_count);
 }
 
@@ -131,6 +134,7 @@ int bpf_shard_normalize_dev(bpf_engine* e, const void* totals_dev, int world, in
   const int n = e->sample_count;
   const int nb = std::max(1, blocks_for(n, BPF_RED_TILE));
   HIPCHK(e, e->d_tile_sums.reserve((size_t)nb));
+  e->set_epoch++;  // the weights are rescaled
   // totals that are this engine's mailbox slots: the kernel itself waits for the peers' posts of this update
   MailboxDev wait{};
   const double* fold = nullptr;
@@ -387,6 +391,8 @@ int bpf_shard_adopt_dev(bpf_engine* e, const void* x_dev, const void* y_dev, con
   e->leaf_count = leaf_count;
   e->bin_count = bin_count;
   e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
+  e->set_epoch++;
+  e->hist_matches_set = false;
   return BPF_OK;
 }
 
@@ -413,6 +419,8 @@ int bpf_shard_tail_small_dev(bpf_engine* e, const void* x_all_dev, const void* y
   e->leaf_count = leaf_count;
   e->bin_count = bin_count;
   e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
+  e->set_epoch++;
+  e->hist_matches_set = false;
   e->converged_pending = true;
   e->conv_n = global_count;
   return BPF_OK;
@@ -524,6 +532,7 @@ int shard_stop_block(bpf_engine* e, const long long* window, int stride, int cou
   e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
   e->converged_pending = true;
   e->conv_n = M;
+  e->set_epoch++;
   e->hist_matches_set = false;  // no host histogram of this set
   return BPF_OK;
 }

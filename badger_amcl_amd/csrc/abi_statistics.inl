@@ -2,6 +2,63 @@
 // ---------------------------------------------------------------------- cluster statistics
 namespace
 {
+// The tracking regime: everything in one single-block launch (k_stats_block) over n <= kStatBlockMax samples at `p`
+// (the engine's own set, or a gathered copy of a sharded one), the result in pinned memory.  *status = 0: installed as
+// the engine's statistics; 1 / 2: more than 1024 bins / 64 clusters; >= 10: key range / non-finite term.
+int stats_block_evaluate(bpf_engine* e, ParticlesDev p, int n, int* status)
+{
+  HIPCHK(e, e->d_stats_clusters.reserve((size_t)std::max(n, kStatBlockClusters)));
+  HIPCHK(e, e->h_stats_block.reserve(64));
+  if (!e->stats_lds_attr_set)
+  {
+    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(k_stats_block),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStatBlockLds));
+    e->stats_lds_attr_set = true;
+  }
+  StatsBlockArgs B{};
+  B.p = p;
+  B.n = n;
+  B.clusters = reinterpret_cast<ClusterDev*>(e->d_stats_clusters.p);
+  B.result_host = e->h_stats_block.p;
+  e->stats_generation = (e->stats_generation % 0x3fffffff) + 1;
+  B.generation = e->stats_generation;
+  hipLaunchKernelGGL(k_stats_block, dim3(1), dim3(1024), kStatBlockLds, e->stream, B);
+  HIPCHK(e, hipGetLastError());
+  const auto t0 = std::chrono::steady_clock::now();
+  bool seen = false;
+  for (unsigned spins = 0; !seen; ++spins)
+  {
+    seen = __atomic_load_n(e->h_stats_block.p, __ATOMIC_ACQUIRE) == B.generation;
+    if (!seen && (spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50))
+      break;
+    if (!seen)
+      __builtin_ia32_pause();
+  }
+  if (!seen)
+  {
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (__atomic_load_n(e->h_stats_block.p, __ATOMIC_ACQUIRE) != B.generation)
+      return e->fail(BPF_ERR_HIP, "k_stats_block did not publish its result");
+  }
+  if (e->h_stats_block.p[1] == 0)
+  {
+    StatsResult r;
+    std::memcpy(&r, e->h_stats_block.p + 4, sizeof(r));
+    e->stats_cluster_count = r.cluster_count;
+    e->stats_best = r.best;
+    e->stats_best_weight = r.best_weight;
+    std::memcpy(e->stats_best_pose, r.best_pose, sizeof(r.best_pose));
+    std::memcpy(e->set_mean, r.set_mean, sizeof(r.set_mean));
+    std::memcpy(e->set_cov, r.set_cov, sizeof(r.set_cov));
+    e->clusters.clear();
+    e->stats_clusters_fetched = false;
+    e->stats_on_device = true;
+    e->stats_epoch = e->set_epoch;
+  }
+  *status = e->h_stats_block.p[1];
+  return BPF_OK;
+}
+
 // particle_filter.cpp:505-636 on the device (kernels_stats.hpp): bins, 26-connected components, fixed-point sums,
 // moments, heaviest cluster; the host reads back one small result block (and the cluster array only if asked for one).
 // *handled = false: a key outside the packing range or a non-finite term -- the caller evaluates on the host.
@@ -15,58 +72,16 @@ int compute_cluster_stats_device(bpf_engine* e, bool* handled)
   SampleSet& s = e->sets[e->cur];
   if (n <= kStatBlockMax)
   {
-    // the tracking regime: everything in one single-block launch (k_stats_block), the result in pinned memory
-    HIPCHK(e, e->d_stats_clusters.reserve((size_t)std::max(n, kStatBlockClusters)));
-    HIPCHK(e, e->h_stats_block.reserve(64));
-    if (!e->stats_lds_attr_set)
+    int status = 0;
+    int rcb = stats_block_evaluate(e, s.dev(), n, &status);
+    if (rcb != BPF_OK)
+      return rcb;
+    if (status == 0)
     {
-      HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(k_stats_block),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStatBlockLds));
-      e->stats_lds_attr_set = true;
-    }
-    StatsBlockArgs B{};
-    B.p = s.dev();
-    B.n = n;
-    B.clusters = reinterpret_cast<ClusterDev*>(e->d_stats_clusters.p);
-    B.result_host = e->h_stats_block.p;
-    e->stats_generation = (e->stats_generation % 0x3fffffff) + 1;
-    B.generation = e->stats_generation;
-    hipLaunchKernelGGL(k_stats_block, dim3(1), dim3(1024), kStatBlockLds, e->stream, B);
-    HIPCHK(e, hipGetLastError());
-    const auto t0 = std::chrono::steady_clock::now();
-    bool seen = false;
-    for (unsigned spins = 0; !seen; ++spins)
-    {
-      seen = __atomic_load_n(e->h_stats_block.p, __ATOMIC_ACQUIRE) == B.generation;
-      if (!seen && (spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50))
-        break;
-      if (!seen)
-        __builtin_ia32_pause();
-    }
-    if (!seen)
-    {
-      HIPCHK(e, hipStreamSynchronize(e->stream));
-      if (__atomic_load_n(e->h_stats_block.p, __ATOMIC_ACQUIRE) != B.generation)
-        return e->fail(BPF_ERR_HIP, "k_stats_block did not publish its result");
-    }
-    if (e->h_stats_block.p[1] == 0)
-    {
-      StatsResult r;
-      std::memcpy(&r, e->h_stats_block.p + 4, sizeof(r));
-      e->stats_cluster_count = r.cluster_count;
-      e->stats_best = r.best;
-      e->stats_best_weight = r.best_weight;
-      std::memcpy(e->stats_best_pose, r.best_pose, sizeof(r.best_pose));
-      std::memcpy(e->set_mean, r.set_mean, sizeof(r.set_mean));
-      std::memcpy(e->set_cov, r.set_cov, sizeof(r.set_cov));
-      e->clusters.clear();
-      e->stats_clusters_fetched = false;
-      e->stats_on_device = true;
-      e->stats_epoch = e->set_epoch;
       *handled = true;
       return BPF_OK;
     }
-    if (e->h_stats_block.p[1] >= 10)
+    if (status >= 10)
       return BPF_OK;  // key range / non-finite term: the host evaluation
     // more than 1024 bins or 64 clusters in a small set: the general device path below
   }
@@ -170,43 +185,11 @@ int fetch_device_clusters(bpf_engine* e)
   return BPF_OK;
 }
 
-// particle_filter.cpp:505-636 on a host copy of the current set, in index order (BPF_OPT_STATS_HOST, and the fallback
-// of the device evaluation)
-int compute_cluster_stats(bpf_engine* e)
+// particle_filter.cpp:505-636 over n samples (x, y, theta, w) in index order, `hist` holding their bins in creation
+// order: the clusters, the set's mean / cov.  The caller marks the result current.
+int host_cluster_stats(bpf_engine* e, const double* s, int n, KdHistogram& hist, int max_clusters)
 {
-  if (e->stats_epoch == e->set_epoch)
-    return BPF_OK;
-  if (!e->stats_host)
-  {
-    bool handled = false;
-    int rcd = compute_cluster_stats_device(e, &handled);
-    if (rcd != BPF_OK)
-      return rcd;
-    if (handled)
-      return BPF_OK;
-  }
-  e->stats_on_device = false;
-  const int n = e->sample_count;
-  std::vector<double> s((size_t)n * 4);
-  int got = 0;
-  int rc = bpf_pf_get_samples(e, s.data(), n, &got);
-  if (rc != BPF_OK)
-    return rc;
-  if (!e->hist_matches_set)
-  {
-    // the histogram tree of this set is not at hand (set loaded with an explicit leaf count, or
-    // restored): rebuild it the way initWith* / the resamplers do, by inserting every pose in order
-    e->hist.clear();
-    for (int i = 0; i < n; ++i)
-    {
-      int key[3];
-      host_pose_key(s[4 * i], s[4 * i + 1], s[4 * i + 2], key);
-      e->hist.insert(key[0], key[1], key[2]);
-    }
-    e->hist_matches_set = true;
-  }
-  e->hist.label_components();
-  const int max_clusters = e->max_samples;  // cluster_max_count (particle_filter.cpp:84)
+  hist.label_components();
   struct Acc
   {
     int count = 0;
@@ -217,12 +200,12 @@ int compute_cluster_stats(bpf_engine* e)
   double weight = 0.0, m[4] = { 0, 0, 0, 0 }, c[4] = { 0, 0, 0, 0 };
   for (int i = 0; i < n; ++i)
   {
-    const double* p = &s[4 * i];
+    const double* p = &s[4 * (size_t)i];
     const double w = p[3];
     int key[3];
     host_pose_key(p[0], p[1], p[2], key);
-    const int node = e->hist.find(key[0], key[1], key[2]);
-    const int cidx = node < 0 ? -1 : e->hist.label_of(node);
+    const int node = hist.find(key[0], key[1], key[2]);
+    const int cidx = node < 0 ? -1 : hist.label_of(node);
     if (cidx < 0 || cidx >= max_clusters)
       continue;  // :574-576
     if (cidx + 1 > cluster_count)
@@ -270,8 +253,48 @@ int compute_cluster_stats(bpf_engine* e)
     for (int q = 0; q < 2; ++q)
       e->set_cov[2 * j + q] = c[2 * j + q] / weight - e->set_mean[j] * e->set_mean[q];
   e->set_cov[4] = -2 * std::log(std::sqrt(m[2] * m[2] + m[3] * m[3]));
-  e->stats_epoch = e->set_epoch;
   return BPF_OK;
+}
+
+// particle_filter.cpp:505-636 on a host copy of the current set, in index order (BPF_OPT_STATS_HOST, and the fallback
+// of the device evaluation)
+int compute_cluster_stats(bpf_engine* e)
+{
+  if (e->stats_epoch == e->set_epoch)
+    return BPF_OK;
+  if (!e->stats_host)
+  {
+    bool handled = false;
+    int rcd = compute_cluster_stats_device(e, &handled);
+    if (rcd != BPF_OK)
+      return rcd;
+    if (handled)
+      return BPF_OK;
+  }
+  e->stats_on_device = false;
+  const int n = e->sample_count;
+  std::vector<double> s((size_t)n * 4);
+  int got = 0;
+  int rc = bpf_pf_get_samples(e, s.data(), n, &got);
+  if (rc != BPF_OK)
+    return rc;
+  if (!e->hist_matches_set)
+  {
+    // the histogram tree of this set is not at hand (set loaded with an explicit leaf count, or
+    // restored): rebuild it the way initWith* / the resamplers do, by inserting every pose in order
+    e->hist.clear();
+    for (int i = 0; i < n; ++i)
+    {
+      int key[3];
+      host_pose_key(s[4 * i], s[4 * i + 1], s[4 * i + 2], key);
+      e->hist.insert(key[0], key[1], key[2]);
+    }
+    e->hist_matches_set = true;
+  }
+  rc = host_cluster_stats(e, s.data(), n, e->hist, e->max_samples);  // cluster_max_count (particle_filter.cpp:84)
+  if (rc == BPF_OK)
+    e->stats_epoch = e->set_epoch;
+  return rc;
 }
 }  // namespace
 

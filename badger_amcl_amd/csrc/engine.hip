@@ -28,6 +28,7 @@
 #include "kernels_pf.hpp"
 #include "kernels_fused.hpp"
 #include "kernels_stats.hpp"
+#include "kernels_shard_stats.hpp"
 #include "kernels_score.hpp"
 #include "kernels_window.hpp"
 
@@ -62,6 +63,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_cloud3d.inl"
 #include "abi_mailbox.inl"
 #include "abi_sharded.inl"
+#include "abi_shard_stats.inl"
 #include "abi_mailbox_step.inl"
 #include "abi_bootstrap.inl"
 #include "abi_measure.inl"

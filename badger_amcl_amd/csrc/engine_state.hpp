@@ -414,6 +414,16 @@ struct bpf_engine
   int stats_generation = 0;
   bool stats_lds_attr_set = false;
 
+  // ---- cluster statistics of a sharded set (kernels_shard_stats.hpp, abi_shard_stats.inl)
+  int ss_stage = 0;                 // 0 none, 1 local bins listed, 2 bins merged and labelled, 3 local sums exported
+  long long ss_epoch = -1;          // set_epoch the stages in progress belong to
+  int ss_clusters = 0;              // global cluster count (stage 2)
+  unsigned ss_gmask = 0;            // global bin table size - 1 (stage 2)
+  DevBuf<long long> d_ss_bins, d_ss_limbs;
+  DevBuf<unsigned long long> d_ss_gkey, d_ss_parent;
+  DevBuf<int> d_ss_gtmin, d_ss_eslot, d_ss_eroot, d_ss_label, d_ss_binlabel;
+  DevBuf<double> d_ss_w;
+
   // ---- cluster statistics (host, lazy)
   std::vector<bpf_cluster> clusters;
   double set_mean[3] = { 0, 0, 0 }, set_cov[5] = { 0, 0, 0, 0, 0 };

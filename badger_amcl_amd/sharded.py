@@ -14,6 +14,16 @@ xGMI) carries the three small exchanges the path really has:
                    Recovery draws (w_diff > 0): every rank resolves the same draw chain and shard 0 writes
                    the random free-space poses -- no further exchange.
 
+  statistics       (compute_cluster_stats / get_cluster / get_max_weight_pose: the clusters of the GLOBAL set and
+                   the pose of the heaviest one, the same bits on every rank as one engine holding the whole set)
+                   up to 4096 particles: one all-gather of the slices' x / y / theta / weight (<= 128 KB), every rank
+                   evaluates the whole set in one single-block launch.  Larger sets stay where they are: all-gather
+                   of the per-rank bin lists (packed key + global index of the key's first sample, 16 B per occupied
+                   bin), bins merged and labelled redundantly on every rank, then one integer all-reduce(sum) of the
+                   per-cluster fixed-point sums (ten 128-bit sums per cluster as four 32-bit limbs in int64 words, so
+                   the lane-wise sum is exact).  A key outside the packing range or a non-finite term on any rank
+                   sends every rank to the host evaluation of the gathered set (32 B per particle).
+
 Scoring itself shards with no communication.  The KLD stop rule (an ordered kd-tree replay) runs
 redundantly on every rank from the assembled key window, so all ranks agree on the sample count
 without another exchange; the resampled set is re-split evenly in index order.
@@ -259,6 +269,69 @@ class HipShardBackend:
     def skip(self, state, n):
         return int(self.e.lib.bpf_drand48_skip(C.c_uint64(state), C.c_uint64(n)))
 
+    # ---- cluster statistics of the global set (include/badger_pf.h, bpf_shard_stats_*)
+    def stats_local_soa(self):
+        """float64 [4, n_local] device tensor: x, y, theta, weight of the slice (a copy; the gather pads it)."""
+        p = [C.c_void_p() for _ in range(4)]
+        n = C.c_int()
+        self.e.check(self.e.lib.bpf_shard_samples_dev(self.e.h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2]),
+                                                      C.byref(p[3]), C.byref(n)))
+        if n.value == 0:
+            return torch.empty((4, 0), dtype=torch.float64, device=self.device)
+        return torch.stack([torch.as_tensor(_DevArray(q.value, (n.value,), "<f8"), device=self.device) for q in p])
+
+    def stats_gathered(self, soa, global_n):
+        """Gathered form on the whole set [4, global_n]: 1 installed, 0 declined (too many bins / clusters),
+        -1 host route."""
+        h = C.c_int()
+        self.e.check(self.e.lib.bpf_shard_stats_gathered_dev(
+            self.e.h, C.c_void_p(soa[0].data_ptr()), C.c_void_p(soa[1].data_ptr()), C.c_void_p(soa[2].data_ptr()),
+            C.c_void_p(soa[3].data_ptr()), int(global_n), C.byref(h)))
+        return h.value
+
+    def stats_local_bins(self, global_first):
+        """(int64 [2, n_bins] device tensor: packed keys, global first indices; host-route flag)."""
+        p, n, hr = C.c_void_p(), C.c_int(), C.c_int()
+        self.e.check(self.e.lib.bpf_shard_stats_local_bins_dev(self.e.h, int(global_first), C.byref(p), C.byref(n),
+                                                               C.byref(hr)))
+        if n.value == 0:
+            return torch.empty((2, 0), dtype=torch.int64, device=self.device), bool(hr.value)
+        return torch.as_tensor(_DevArray(p.value, (2, n.value), "<i8"), device=self.device), bool(hr.value)
+
+    def stats_label(self, all_bins, counts, pad):
+        """all_bins: int64 [world, 2, pad] gathered lists; returns the global cluster count."""
+        c = (C.c_int * len(counts))(*[int(v) for v in counts])
+        out = C.c_int()
+        self.e.check(self.e.lib.bpf_shard_stats_label_dev(self.e.h, C.c_void_p(all_bins.data_ptr()), c, len(counts),
+                                                          int(pad), C.byref(out)))
+        return out.value
+
+    def stats_local_sums(self):
+        """int64 limb words of the slice's per-cluster sums (engine memory; reduced in place by the caller)."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self.e.check(self.e.lib.bpf_shard_stats_local_sums_dev(self.e.h, C.byref(p), C.byref(n)))
+        return torch.as_tensor(_DevArray(p.value, (n.value,), "<i8"), device=self.device)
+
+    def stats_finish(self, reduced):
+        self.e.check(self.e.lib.bpf_shard_stats_finish_dev(self.e.h, C.c_void_p(reduced.data_ptr())))
+
+    def stats_local_samples_host(self):
+        """numpy [n_local, 4] copy of the slice (the host route only)."""
+        return self.pf.getCurrentSet().samples
+
+    def stats_host(self, all_samples):
+        a = np.ascontiguousarray(all_samples, dtype=np.float64)
+        self.e.check(self.e.lib.bpf_shard_stats_host(self.e.h, a.ctypes.data_as(C.POINTER(C.c_double)), a.shape[0]))
+
+    def stats_result(self):
+        return self.pf.computeClusterStats()
+
+    def stats_cluster(self, k):
+        return self.pf.getClusterStats(k)
+
+    def stats_max_weight_pose(self):
+        return self.pf.getMaxWeightPose()
+
     def rng_state(self):
         return self.pf.getRngState()
 
@@ -332,6 +405,8 @@ class ShardedFilter:
         self.leaf_count = self.bin_count = 0
         self.windows_used = 0
         self.totals = None  # per-shard weight totals of the last update_sensor (None: weights changed since)
+        self._stats_valid = False  # the backend holds the statistics of the current GLOBAL set
+        self.stats_route = None    # how the last statistics were evaluated: "gathered", "distributed" or "host"
         self._fused_totals = False  # the last update_sensor went through the engine's one-call mailbox form
         # exchange: "mailbox" = peer stores through IPC-mapped device memory (all ranks on one node), "collective" =
         # torch.distributed all-gather / all-reduce, "auto" = mailbox when every rank could set it up
@@ -483,11 +558,13 @@ class ShardedFilter:
 
     # ---- motion update (Odom::updateAction): no exchange
     def update_action(self, odom, data):
+        self._stats_valid = False
         first = sum(self.counts[:self.rank])
         self.b.update_action(odom, data, first, self.sample_count)
 
     # ---- Seam A
     def update_sensor(self, data):
+        self._stats_valid = False
         if self.mailbox and not hasattr(data, "points_") and hasattr(self.b, "mailbox_update_sensor"):
             # mailbox: the exchange is inside the kernels, so the whole update is one call into the engine
             if self.b.mailbox_update_sensor(data, self.sample_count):
@@ -568,6 +645,7 @@ class ShardedFilter:
 
     # ---- Seam B (multinomial, w_diff == 0)
     def update_resample(self):
+        self._stats_valid = False
         self._update_resample()
         self._step += 1
 
@@ -679,7 +757,71 @@ class ShardedFilter:
         self.sample_count = sum(counts)
         self.totals = None
         self._fused_totals = False
+        self._stats_valid = False
         self.leaf_count = leaf_count
+
+    # ---- cluster statistics of the GLOBAL set (particle_filter.cpp:505-636, node_2d.cpp:588-617)
+    STATS_GATHER_MAX = 4096  # kStatBlockMax: up to here every rank evaluates the gathered set in one launch
+
+    def _gather_ragged(self, mine, counts):
+        """All-gather of [rows, counts[rank]] tensors of different widths: padded to the widest, [world, rows, pad]."""
+        pad = max(max(counts), 1)
+        buf = torch.zeros((mine.shape[0], pad), dtype=mine.dtype, device=mine.device)
+        buf[:, :mine.shape[1]] = mine
+        return self._all_gather(buf.reshape(-1)).reshape(self.world, mine.shape[0], pad), pad
+
+    def _ensure_stats(self):
+        """Lazy, like the single engine: evaluated at the first query after the set changed.  Every rank has to
+        make the query (the exchanges are collective)."""
+        if self._stats_valid:
+            return
+        b, W, n = self.b, self.world, self.sample_count
+        route = None
+        if n <= self.STATS_GATHER_MAX:
+            # the tracking regime: the whole set on every rank, evaluated redundantly
+            allv, _ = self._gather_ragged(b.stats_local_soa(), self.counts)
+            soa = torch.cat([allv[r, :, :self.counts[r]] for r in range(W)], dim=1).contiguous()
+            handled = b.stats_gathered(soa, n)
+            if handled > 0:
+                route = "gathered"
+            elif handled < 0:
+                route = "host"
+        if route is None:
+            bins, host_route = b.stats_local_bins(sum(self.counts[:self.rank]))
+            meta = torch.tensor([bins.shape[1], 1 if host_route else 0], dtype=torch.int64, device=self.device)
+            meta = self._all_gather(meta).reshape(W, 2).cpu().tolist()
+            bin_counts = [int(m[0]) for m in meta]
+            if any(int(m[1]) for m in meta):
+                route = "host"  # the flag travelled with the first exchange: every rank turns off here together
+            else:
+                all_bins, pad = self._gather_ragged(bins, bin_counts)
+                b.stats_label(all_bins, bin_counts, pad)
+                sums = b.stats_local_sums()
+                self._all_reduce_sum(sums)  # limb form: the lane-wise int64 sum is exact
+                b.stats_finish(sums)
+                route = "distributed"
+        if route == "host":
+            local = torch.from_numpy(np.ascontiguousarray(b.stats_local_samples_host()[:, :4].T))
+            allv, _ = self._gather_ragged(local.to(self.device), self.counts)
+            allv = allv.cpu()
+            b.stats_host(torch.cat([allv[r, :, :self.counts[r]] for r in range(W)], dim=1).T.contiguous().numpy())
+        self.stats_route = route
+        self._stats_valid = True
+
+    def compute_cluster_stats(self):
+        """(cluster_count, set_mean[3], set_cov[5]) of the global set; cov entries (0,0) (0,1) (1,0) (1,1) (2,2)."""
+        self._ensure_stats()
+        return self.b.stats_result()
+
+    def get_cluster(self, k):
+        """(weight, mean[3], count, cov[5]) of cluster k of the global set, None past the last cluster."""
+        self._ensure_stats()
+        return self.b.stats_cluster(k)
+
+    def get_max_weight_pose(self):
+        """Node2D::getMaxWeightPose over the global set: (weight, pose) of the heaviest cluster."""
+        self._ensure_stats()
+        return self.b.stats_max_weight_pose()
 
     def set_random_pose_generator(self, mode):
         """random_pose_fn of this rank's engine (pf.RANDOM_POSE_*); every rank sets the same mode.  Every rank

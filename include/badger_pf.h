@@ -519,6 +519,64 @@ int bpf_shard_adopt_dev(bpf_engine* e, const void* x_dev, const void* y_dev, con
 /* updateConverged (particle_filter.cpp:170-220) over the WHOLE resampled set (every rank holds it
  * after the window exchange); fetched lazily by bpf_pf_get_state. */
 int bpf_shard_converged_dev(bpf_engine* e, const void* x_all_dev, const void* y_all_dev, int global_count);
+
+/* ------------------------------------------------------------------ cluster statistics of a sharded set
+ * computeClusterStatsForSet (particle_filter.cpp:505-636), PFKDTree::cluster (pf_kdtree.cpp:58-90,169-194) and
+ * Node2D::getMaxWeightPose (node_2d.cpp:588-617) for the GLOBAL set S = the ranks' slices in rank order, without
+ * moving the particles.  After the last stage bpf_pf_compute_cluster_stats, bpf_pf_get_cluster and
+ * bpf_pf_get_max_weight_pose of this engine return, bit for bit, what ONE engine holding S returns -- same bins, same
+ * components, same labels (a component's label is the rank of its earliest bin by GLOBAL sample index), the same ten
+ * 32.96 fixed-point sums per cluster as exact integers, the same finishing arithmetic -- until this engine's slice
+ * next changes.  Every stage that changes the slice's poses or weights (bpf_shard_update_action, the scoring stages,
+ * bpf_shard_normalize_dev, bpf_shard_adopt_dev, bpf_shard_tail_small_dev, the one-call mailbox forms) drops the
+ * installed result; the plain getters then evaluate THIS ENGINE'S SLICE ONLY (clusters cut at the shard boundary,
+ * local labels, weights that sum to about 1 / world): that is not the global figure, run the stages again for it.
+ * The stage functions are asynchronous on the engine's stream except where they return a count; no kernel waits for
+ * another rank, the exchanges are the caller's, between the calls.  Calls out of order, or after the slice changed,
+ * return BPF_ERR_NOT_CONFIGURED.  Two forms, chosen by the GLOBAL count so that every rank chooses alike:
+ *
+ * Gathered form (global_count <= 4096, the tracking regime).  Crosses between ranks: one all-gather of the slices'
+ * x / y / theta / weight (<= 128 KB), the caller's.  Redundant: every rank runs the single-block evaluation
+ * (k_stats_block) on the whole set.  w_all NULL = every weight 1 / global_count (the set straight after a resample).
+ * *handled_out: BPF_SHARD_STATS_INSTALLED; BPF_SHARD_STATS_DECLINED when the set holds more than 1024 bins or 64
+ * clusters (use the distributed form); BPF_SHARD_STATS_HOST_ROUTE for a key outside the packing range, a non-finite
+ * term, or BPF_OPT_STATS_HOST = 1 (use bpf_shard_stats_host).  All ranks see the same set, so they decide alike. */
+/* the slice itself for that all-gather: device addresses of the current set's x / y / theta / weight arrays
+ * (*count_out doubles each), valid until the next call that changes the set; work queued on the engine's stream has
+ * to be ordered before a reader on another stream */
+int bpf_shard_samples_dev(bpf_engine* e, void** x_dev, void** y_dev, void** theta_dev, void** w_dev, int* count_out);
+#define BPF_SHARD_STATS_INSTALLED 1
+#define BPF_SHARD_STATS_DECLINED 0
+#define BPF_SHARD_STATS_HOST_ROUTE (-1)
+int bpf_shard_stats_gathered_dev(bpf_engine* e, const void* x_all, const void* y_all, const void* theta_all,
+                                 const void* w_all, int global_count, int* handled_out);
+/* Distributed form, stage 1 (pf_kdtree.cpp:49-56, the bins of the slice): *bins_dev = int64[2][*n_bins_out] in engine
+ * memory, row 0 the distinct packed bin keys of the slice, row 1 the GLOBAL index (global_first + local index) of each
+ * key's first sample, in increasing first-index order.  *host_route_out = 1: a key outside the packing range, a
+ * non-finite term, or BPF_OPT_STATS_HOST = 1 on this rank.  Crosses between ranks afterwards (exchange 1): the
+ * counts with the host-route flags, then the lists padded to the largest count; if ANY rank raised the flag every
+ * rank takes bpf_shard_stats_host instead.  Waits for the stream (the count comes back). */
+int bpf_shard_stats_local_bins_dev(bpf_engine* e, long long global_first, void** bins_dev, int* n_bins_out,
+                                   int* host_route_out);
+/* Stage 2 (pf_kdtree.cpp:58-90,169-194), redundant on every rank: all_bins_dev = int64[world][2][pad], rank r's list
+ * in its first counts[r] columns (world <= 16, counts in host memory).  One global bin table (a key held by several
+ * ranks keeps its smallest first index), union-find over the 26 neighbours of each bin, labels by an exclusive scan
+ * of "this bin is a root" over the bins in first-index order.  Waits for the stream. */
+int bpf_shard_stats_label_dev(bpf_engine* e, const void* all_bins_dev, const int* counts, int world, int pad,
+                              int* cluster_count_out);
+/* Stage 3 (particle_filter.cpp:569-605 over the slice): every sample adds its ten terms to the accumulators of its
+ * bin's cluster.  *sums_dev = int64[10 * cluster_count][4] in engine memory: each 128-bit sum as four 32-bit limbs,
+ * least significant first, the top one signed, so that a lane-wise int64 sum over <= 16 ranks is exact.  Crosses
+ * between ranks afterwards (exchange 2): an integer all-reduce(sum) of these *n_words_out words. */
+int bpf_shard_stats_local_sums_dev(bpf_engine* e, void** sums_dev, size_t* n_words_out);
+/* Stage 4 (particle_filter.cpp:541-567,607-635, node_2d.cpp:608-612), redundant on every rank: carries propagated,
+ * the single engine's finishing kernels on the reduced sums, the result installed as this engine's statistics.
+ * reduced_sums_dev may be the buffer stage 3 returned, reduced in place.  Waits for the stream. */
+int bpf_shard_stats_finish_dev(bpf_engine* e, const void* reduced_sums_dev);
+/* The host route, redundant on every rank: particle_filter.cpp:505-636 in index order over the gathered set,
+ * all_samples = global_count x (x, y, theta, w) in host memory; bit for bit the BPF_OPT_STATS_HOST = 1 evaluation of
+ * one engine holding the set.  Crosses between ranks: the all-gather of the slices (32 B per particle), the caller's. */
+int bpf_shard_stats_host(bpf_engine* e, const double* all_samples, int global_count);
 /* Advance a drand48 state by n draws (host arithmetic; the LCG jump the kernels use). */
 uint64_t bpf_drand48_skip(uint64_t state48, uint64_t n);
 /* Host-side exact KLD stop rule: replay ordered histogram keys through the fork's kd-tree
