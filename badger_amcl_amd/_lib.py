@@ -137,6 +137,10 @@ SIGNATURES = {
     "bpf_shard_shutdown": (C.c_int, [_vp]),
     "bpf_shard_update_sensor_planar": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, C.c_longlong]),
     "bpf_shard_update_resample": (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "bpf_shard_update_sensor_cloud": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, C.c_longlong]),
+    "bpf_shard_compute_cluster_stats": (C.c_int, [_vp, _ip, _dp, _dp, _ip]),
+    "bpf_shard_get_max_weight_pose": (C.c_int, [_vp, _dp, _dp]),
+    "bpf_shard_exchange_count": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
     "bpf_shard_mailbox_update_sensor_planar": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, C.c_longlong]),
     "bpf_shard_mailbox_update_resample": (C.c_int, [_vp, _vp, _ip, _ip, _ip, _ip, _ip]),
     "bpf_shard_mailbox_destroy": (C.c_int, [_vp]),

@@ -13,7 +13,8 @@
 //
 //   bpf_shard_update_sensor_planar / bpf_shard_update_resample
 //
-// the sharded sensor update and resample as one call each, whichever exchange the bootstrap chose.
+// the sharded sensor update and resample as one call each, whichever exchange the bootstrap chose (the 3-D update and
+// the global statistics: abi_shard_node.inl).
 #include <arpa/inet.h>
 #include <dlfcn.h>
 #include <netdb.h>
@@ -242,8 +243,10 @@ int collective_load(bpf_engine* e)
   c.fn.allgather_f64 = reinterpret_cast<int (*)(void*, const double*, double*, size_t, void*)>(sym("bpfc_allgather_f64"));
   c.fn.allreduce_sum_i64 = reinterpret_cast<int (*)(void*, long long*, size_t, void*)>(sym("bpfc_allreduce_sum_i64"));
   c.fn.allreduce_sum_i32 = reinterpret_cast<int (*)(void*, int*, size_t, void*)>(sym("bpfc_allreduce_sum_i32"));
+  c.fn.allgather_i64 =
+      reinterpret_cast<int (*)(void*, const long long*, long long*, size_t, void*)>(sym("bpfc_allgather_i64"));
   if (!c.fn.last_error || !c.fn.unique_id_bytes || !c.fn.unique_id || !c.fn.init || !c.fn.destroy ||
-      !c.fn.allgather_f64 || !c.fn.allreduce_sum_i64 || !c.fn.allreduce_sum_i32)
+      !c.fn.allgather_f64 || !c.fn.allreduce_sum_i64 || !c.fn.allreduce_sum_i32 || !c.fn.allgather_i64)
     return e->fail(BPF_ERR_NOT_CONFIGURED, path + " does not export the collective entry points");
   return BPF_OK;
 }
@@ -302,6 +305,7 @@ int bpf_shard_bootstrap(bpf_engine* e, int rank, int world, const char* host_por
   }
   if (agreed)
   {
+    e->mb.gen_base = e->mb.tot_gen + e->mb.win_gen;  // the self-test's windows are not exchanges of the filter
     if (mode_out)
       *mode_out = BPF_SHARD_EXCHANGE_MAILBOX;
     return BPF_OK;
@@ -330,6 +334,7 @@ int bpf_shard_bootstrap(bpf_engine* e, int rank, int world, const char* host_por
     return e->fail(BPF_ERR_EXCHANGE, "bootstrap: RCCL communicator: " + (ok ? std::string("a peer failed") : init_error));
   }
   e->coll.active = true;
+  e->coll.exchanges = 0;
   if (mode_out)
     *mode_out = BPF_SHARD_EXCHANGE_RCCL;
   return BPF_OK;
@@ -347,7 +352,8 @@ int bpf_shard_shutdown(bpf_engine* e)
 int bpf_shard_update_sensor_planar(bpf_engine* e, const double* ranges, const double* angles, int range_count,
                                    double range_max, long long global_count)
 {
-  return bpf_shard_mailbox_update_sensor_planar(e, ranges, angles, range_count, range_max, global_count);
+  // unlike the mailbox form this one completes the prob model's beam skipping over the mailbox too
+  return shard_update_sensor_planar(e, ranges, angles, range_count, range_max, global_count, true);
 }
 
 int bpf_shard_update_resample(bpf_engine* e, int* global_count_io, int* leaf_count_io, int* bin_count_out,

@@ -6,6 +6,10 @@
 // The same sequence also runs with RCCL collectives between the stages (bpf_shard_bootstrap falls back to that when the
 // mailbox cannot be set up): the totals go through ncclAllGather after the scoring stage and every draw window through
 // an integer ncclAllReduce(sum) before its first consumer -- ShardExchange hides which of the two it is.
+//
+// ShardExchange also carries the two general small exchanges of the one-call forms (abi_shard_node.inl, the beam-skip
+// counts below): a ragged all-gather and an integer all-reduce(sum), over the mailbox's window region
+// (k_mailbox_post_words / k_mailbox_take_ragged / k_mailbox_take_sum) or over RCCL.
 namespace
 {
 struct ShardExchange
@@ -40,9 +44,138 @@ struct ShardExchange
   {
     if (!collective())
       return BPF_OK;  // the draw kernel stored them into all peers; the window's first consumer waits for them
+    ++e->coll.exchanges;
     if (e->coll.fn.allreduce_sum_i64(e->coll.comm, window, (size_t)6 * stride, e->stream) != 0)
       return e->fail(BPF_ERR_EXCHANGE, std::string("RCCL window all-reduce: ") + e->coll.fn.last_error());
     return BPF_OK;
+  }
+
+  // the next generation of the window region for an exchange addressed by word offset
+  int next_words(unsigned long long* gen)
+  {
+    if (e->mb.win_wait)
+      return e->fail(BPF_ERR_NOT_CONFIGURED, "mailbox: the previous window was never consumed");
+    *gen = ++e->mb.win_gen;
+    return BPF_OK;
+  }
+  // blocks of 256 for `words` words, never more than a grid may wait with
+  static int small_grid(long long words)
+  {
+    return (int)std::max<long long>(1, std::min<long long>((words + 255) / 256, kMailboxFusedWaitBlocks));
+  }
+
+  // Ragged all-gather of int64 words: this rank contributes `rows` rows of counts[rank] words (row k at src[k]), every
+  // rank ends with rank r's row k at dst[dst_off[r] + k * dst_stride ...].  counts: host, the same on every rank.
+  // Asynchronous on the engine's stream; after a mailbox wait that ran out dst is left alone (finish() tells).
+  int gather(const long long* const* src, int rows, const long long* counts, long long* dst, const long long* dst_off,
+             long long dst_stride)
+  {
+    const int W = e->shard_world, rank = e->shard_rank;
+    if (rows < 1 || rows > 4 || W < 1 || W > kMailboxMaxWorld)
+      return e->fail(BPF_ERR_INVALID_ARGUMENT, "shard gather: 1 .. 4 rows, at most 16 ranks");
+    MbRagged L{};
+    L.world = W;
+    L.rows = rows;
+    L.dst_stride = dst_stride;
+    long long total = 0, widest = 1;
+    for (int r = 0; r < W; ++r)
+    {
+      L.count[r] = counts[r];
+      L.dst_off[r] = dst_off[r];
+      L.src_off[r] = total;
+      L.src_stride[r] = counts[r];
+      total += (long long)rows * counts[r];
+      widest = std::max(widest, counts[r]);
+    }
+    if (!collective())
+    {
+      if (total > 6 * e->mb.max_window)
+        return e->fail(BPF_ERR_CAPACITY, "mailbox windows are smaller than the gathered payload");
+      unsigned long long g = 0;
+      int rc = next_words(&g);
+      if (rc != BPF_OK)
+        return rc;
+      MbPostArgs A{};
+      for (int k = 0; k < rows; ++k)
+        A.src[k] = src[k];
+      A.rows = rows;
+      A.count = counts[rank];
+      A.word_off = L.src_off[rank];
+      hipLaunchKernelGGL(k_mailbox_post_words, dim3(small_grid(rows * counts[rank])), dim3(256), 0, e->stream,
+                         mailbox_dev(e), A, (int)(g & 1), g, e->d_mb_counter.p);
+      hipLaunchKernelGGL(k_mailbox_take_ragged, dim3(small_grid(rows * widest)), dim3(256), 0, e->stream, mailbox_dev(e),
+                         (const long long*)nullptr, dst, L, (int)(g & 1), g);
+      HIPCHK(e, hipGetLastError());
+      return BPF_OK;
+    }
+    // RCCL: every contribution padded to the widest one, then the same re-layout out of the receive buffer
+    ++e->coll.exchanges;
+    const size_t per = (size_t)rows * (size_t)widest;
+    HIPCHK(e, e->coll.send.reserve(per));
+    HIPCHK(e, e->coll.recv.reserve(per * (size_t)W));
+    HIPCHK(e, hipMemsetAsync(e->coll.send.p, 0, per * sizeof(long long), e->stream));
+    for (int k = 0; k < rows && counts[rank] > 0; ++k)
+      HIPCHK(e, hipMemcpyAsync(e->coll.send.p + (size_t)k * widest, src[k], (size_t)counts[rank] * sizeof(long long),
+                               hipMemcpyDeviceToDevice, e->stream));
+    if (e->coll.fn.allgather_i64(e->coll.comm, e->coll.send.p, e->coll.recv.p, per, e->stream) != 0)
+      return e->fail(BPF_ERR_EXCHANGE, std::string("RCCL all-gather: ") + e->coll.fn.last_error());
+    for (int r = 0; r < W; ++r)
+    {
+      L.src_off[r] = (long long)r * (long long)per;
+      L.src_stride[r] = widest;
+    }
+    hipLaunchKernelGGL(k_mailbox_take_ragged, dim3(small_grid(rows * widest)), dim3(256), 0, e->stream, MailboxDev{},
+                       (const long long*)e->coll.recv.p, dst, L, 0, 0ull);
+    HIPCHK(e, hipGetLastError());
+    return BPF_OK;
+  }
+
+  // All-reduce(sum) in place of n integer words (int32 when i32, else int64).  Mailbox: gather-then-sum in rank order, in
+  // as many rounds as the window region takes (W spans per round).
+  int reduce_sum(void* buf, size_t n, bool i32)
+  {
+    if (collective())
+    {
+      ++e->coll.exchanges;
+      const int bad = i32 ? e->coll.fn.allreduce_sum_i32(e->coll.comm, static_cast<int*>(buf), n, e->stream)
+                          : e->coll.fn.allreduce_sum_i64(e->coll.comm, static_cast<long long*>(buf), n, e->stream);
+      if (bad)
+        return e->fail(BPF_ERR_EXCHANGE, std::string("RCCL all-reduce: ") + e->coll.fn.last_error());
+      return BPF_OK;
+    }
+    const int W = e->shard_world, rank = e->shard_rank;
+    const size_t per = (size_t)(6 * e->mb.max_window) / (size_t)W;
+    if (per == 0)
+      return e->fail(BPF_ERR_CAPACITY, "mailbox windows are smaller than one word per rank");
+    for (size_t done = 0; done < n; done += per)
+    {
+      const size_t chunk = std::min(per, n - done);
+      unsigned long long g = 0;
+      int rc = next_words(&g);
+      if (rc != BPF_OK)
+        return rc;
+      void* at = i32 ? static_cast<void*>(static_cast<int*>(buf) + done)
+                     : static_cast<void*>(static_cast<long long*>(buf) + done);
+      MbPostArgs A{};
+      A.src[0] = static_cast<const long long*>(at);
+      A.rows = 1;
+      A.widen32 = i32 ? 1 : 0;
+      A.count = (long long)chunk;
+      A.word_off = (long long)rank * (long long)chunk;
+      hipLaunchKernelGGL(k_mailbox_post_words, dim3(small_grid((long long)chunk)), dim3(256), 0, e->stream,
+                         mailbox_dev(e), A, (int)(g & 1), g, e->d_mb_counter.p);
+      hipLaunchKernelGGL(k_mailbox_take_sum, dim3(small_grid((long long)chunk)), dim3(256), 0, e->stream, mailbox_dev(e),
+                         at, (long long)chunk, i32 ? 1 : 0, (int)(g & 1), g);
+      HIPCHK(e, hipGetLastError());
+    }
+    return BPF_OK;
+  }
+
+  // the host's check behind exchanges whose result it (or a stage that must not run on half of it) depends on
+  int finish()
+  {
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return collective() ? BPF_OK : mailbox_check(e);
   }
 
   // the W weight totals of the scoring stage just issued
@@ -50,6 +183,7 @@ struct ShardExchange
   {
     if (!collective())
       return bpf_shard_mailbox_totals(e, out);
+    ++e->coll.exchanges;
     HIPCHK(e, e->coll.totals.reserve((size_t)e->shard_world));
     if (e->coll.fn.allgather_f64(e->coll.comm, &e->d_scalars.p->v[0], e->coll.totals.p, 1, e->stream) != 0)
       return e->fail(BPF_ERR_EXCHANGE, std::string("RCCL totals all-gather: ") + e->coll.fn.last_error());
@@ -66,8 +200,28 @@ int shard_step_ready(bpf_engine* e)
 }
 }  // namespace
 
-int bpf_shard_mailbox_update_sensor_planar(bpf_engine* e, const double* ranges, const double* angles, int range_count,
-                                           double range_max, long long global_count)
+namespace
+{
+// totals of the scoring stage just issued, normalisation, and what bpf_shard_mailbox_update_resample requires of
+// "the totals of this update"
+int shard_totals_and_normalize(bpf_engine* e, ShardExchange& X, long long global_count)
+{
+  void* totals = nullptr;
+  int rc = X.totals(&totals);
+  if (rc != BPF_OK)
+    return rc;
+  rc = bpf_shard_normalize_dev(e, totals, e->shard_world, (int)global_count);
+  if (rc != BPF_OK)
+    return rc;
+  e->mb_totals = totals;
+  e->mb_totals_valid = true;
+  return BPF_OK;
+}
+
+// counts_over_mailbox: sum the beam-skip counts over the mailbox too (bpf_shard_update_sensor_planar); false hands
+// BPF_SHARD_NEED_BEAM_COUNTS back in mailbox mode (bpf_shard_mailbox_update_sensor_planar, whose caller sums them)
+int shard_update_sensor_planar(bpf_engine* e, const double* ranges, const double* angles, int range_count,
+                               double range_max, long long global_count, bool counts_over_mailbox)
 {
   if (!e || global_count <= 0)
     return BPF_ERR_INVALID_ARGUMENT;
@@ -77,7 +231,7 @@ int bpf_shard_mailbox_update_sensor_planar(bpf_engine* e, const double* ranges, 
   ShardExchange X{ e };
   e->mb_totals_valid = false;
   rc = bpf_shard_score_planar(e, ranges, angles, range_count, range_max);
-  if (rc == BPF_SHARD_NEED_BEAM_COUNTS && X.collective())
+  if (rc == BPF_SHARD_NEED_BEAM_COUNTS && (X.collective() || counts_over_mailbox))
   {
     // beam skipping: the per-beam agreement counts are summed over the shards between the two passes
     void* counts = nullptr;
@@ -85,24 +239,25 @@ int bpf_shard_mailbox_update_sensor_planar(bpf_engine* e, const double* ranges, 
     rc = bpf_shard_beam_counts_dev(e, &counts, &n_counts);
     if (rc != BPF_OK)
       return rc;
-    if (e->coll.fn.allreduce_sum_i32(e->coll.comm, static_cast<int*>(counts), (size_t)n_counts, e->stream) != 0)
-      return e->fail(BPF_ERR_EXCHANGE, std::string("RCCL beam-count all-reduce: ") + e->coll.fn.last_error());
+    rc = X.reduce_sum(counts, (size_t)n_counts, true);
+    if (rc == BPF_OK && !X.collective())
+      rc = X.finish();  // the second pass must not score against one shard's counts
+    if (rc != BPF_OK)
+      return rc;
     rc = bpf_shard_score_planar_finish(e, ranges, angles, range_count, range_max, global_count);
   }
   if (rc != BPF_OK)
-    return rc;  // includes BPF_SHARD_NEED_BEAM_COUNTS (mailbox mode): the caller sums the counts in between
+    return rc;  // includes BPF_SHARD_NEED_BEAM_COUNTS (mailbox form): the caller sums the counts in between
   if (e->pm.max_beams < 2)
     return BPF_OK;
-  void* totals = nullptr;
-  rc = X.totals(&totals);
-  if (rc != BPF_OK)
-    return rc;
-  rc = bpf_shard_normalize_dev(e, totals, e->shard_world, (int)global_count);
-  if (rc != BPF_OK)
-    return rc;
-  e->mb_totals = totals;
-  e->mb_totals_valid = true;
-  return BPF_OK;
+  return shard_totals_and_normalize(e, X, global_count);
+}
+}  // namespace
+
+int bpf_shard_mailbox_update_sensor_planar(bpf_engine* e, const double* ranges, const double* angles, int range_count,
+                                           double range_max, long long global_count)
+{
+  return shard_update_sensor_planar(e, ranges, angles, range_count, range_max, global_count, false);
 }
 
 int bpf_shard_mailbox_update_resample(bpf_engine* e, void* flags_dev, int* global_count_io, int* leaf_count_io,

@@ -1,0 +1,239 @@
+// C-ABI: what a C / C++ host of a sharded filter still needed a transport of its own for -- the 3-D sensor update and
+// the statistics of the GLOBAL set -- as one collective call each.  Every exchange goes through ShardExchange
+// (abi_mailbox_step.inl): the mailbox's peer stores, or RCCL after the bootstrap's fallback.  The stage functions run
+// in the order badger_amcl_amd/sharded.py runs them (update_sensor, _ensure_stats); there is no arithmetic here.
+namespace
+{
+// a few int64 words of every rank into host memory: all[r * n_each + k], in rank order (waits for the stream)
+int shard_gather_host_words(bpf_engine* e, ShardExchange& X, const long long* mine, int n_each, long long* all)
+{
+  const int W = e->shard_world;
+  const size_t n_all = (size_t)W * (size_t)n_each;
+  HIPCHK(e, e->d_x_words.reserve((size_t)(kMailboxMaxWorld + 1) * 4));
+  HIPCHK(e, e->h_x_words.reserve((size_t)(kMailboxMaxWorld + 1) * 4));
+  if (n_each < 1 || n_each > 4)
+    return e->fail(BPF_ERR_INVALID_ARGUMENT, "shard gather: 1 .. 4 words per rank");
+  long long counts[kMailboxMaxWorld], offs[kMailboxMaxWorld];
+  for (int r = 0; r < W; ++r)
+  {
+    counts[r] = n_each;
+    offs[r] = (long long)r * n_each;
+  }
+  for (int k = 0; k < n_each; ++k)
+    e->h_x_words.p[k] = mine[k];
+  HIPCHK(e, hipMemcpyAsync(e->d_x_words.p, e->h_x_words.p, (size_t)n_each * sizeof(long long), hipMemcpyHostToDevice,
+                           e->stream));
+  const long long* src[1] = { e->d_x_words.p };
+  int rc = X.gather(src, 1, counts, e->d_x_words.p + 4, offs, 0);
+  if (rc != BPF_OK)
+    return rc;
+  HIPCHK(e, hipMemcpyAsync(e->h_x_words.p + 4, e->d_x_words.p + 4, n_all * sizeof(long long), hipMemcpyDeviceToHost,
+                           e->stream));
+  rc = X.finish();
+  if (rc != BPF_OK)
+    return rc;
+  for (size_t i = 0; i < n_all; ++i)
+    all[i] = e->h_x_words.p[4 + i];
+  return BPF_OK;
+}
+
+// x / y / theta / weight of every slice, concatenated in rank order: d_x_gather = double[4][n]
+int shard_gather_slices(bpf_engine* e, ShardExchange& X, const long long* counts, int n)
+{
+  const int W = e->shard_world;
+  HIPCHK(e, e->d_x_gather.reserve((size_t)4 * (size_t)n));
+  SampleSet& s = e->sets[e->cur];
+  const long long* src[4] = { reinterpret_cast<const long long*>(s.x.p), reinterpret_cast<const long long*>(s.y.p),
+                              reinterpret_cast<const long long*>(s.th.p), reinterpret_cast<const long long*>(s.w.p) };
+  long long offs[kMailboxMaxWorld], at = 0;
+  for (int r = 0; r < W; ++r)
+  {
+    offs[r] = at;
+    at += counts[r];
+  }
+  return X.gather(src, 4, counts, e->d_x_gather.p, offs, n);
+}
+
+// ShardedFilter._ensure_stats
+int shard_ensure_stats(bpf_engine* e)
+{
+  if (!e->have_pf)
+    return e->fail(BPF_ERR_NOT_CONFIGURED, "bpf_pf_create first");
+  int rc = shard_step_ready(e);
+  if (rc != BPF_OK)
+    return rc;
+  if (e->ss_global_epoch == e->set_epoch && e->stats_epoch == e->set_epoch)
+    return BPF_OK;  // no slice has changed since the global figures were installed: no exchange
+  HIPCHK(e, hipSetDevice(e->device));
+  ShardExchange X{ e };
+  const int W = e->shard_world, rank = e->shard_rank;
+  long long counts[kMailboxMaxWorld] = { 0 };
+  const long long mine = e->sample_count;
+  rc = shard_gather_host_words(e, X, &mine, 1, counts);
+  if (rc != BPF_OK)
+    return rc;
+  long long total = 0, first = 0;
+  for (int r = 0; r < W; ++r)
+  {
+    if (counts[r] < 0)
+      return e->fail(BPF_ERR_EXCHANGE, "sharded statistics: a negative sample count arrived");
+    if (r < rank)
+      first += counts[r];
+    total += counts[r];
+  }
+  if (total <= 0 || total >= (1ll << 30))
+    return e->fail(BPF_ERR_INVALID_ARGUMENT, "sharded statistics: the global set is empty, or beyond 2^30 samples");
+  const int n = (int)total;
+  int route = 0;
+  if (n <= kStatBlockMax)
+  {
+    // the tracking regime: the whole set on every rank, evaluated redundantly
+    rc = shard_gather_slices(e, X, counts, n);
+    if (rc == BPF_OK)
+      rc = X.finish();
+    if (rc != BPF_OK)
+      return rc;
+    const double* d = reinterpret_cast<const double*>(e->d_x_gather.p);
+    int handled = BPF_SHARD_STATS_DECLINED;
+    rc = bpf_shard_stats_gathered_dev(e, d, d + n, d + 2 * (size_t)n, d + 3 * (size_t)n, n, &handled);
+    if (rc != BPF_OK)
+      return rc;
+    if (handled == BPF_SHARD_STATS_INSTALLED)
+      route = BPF_SHARD_STATS_ROUTE_GATHERED;
+    else if (handled == BPF_SHARD_STATS_HOST_ROUTE)
+      route = BPF_SHARD_STATS_ROUTE_HOST;
+  }
+  if (route == 0)
+  {
+    void* bins = nullptr;
+    int n_bins = 0, host_route = 0;
+    rc = bpf_shard_stats_local_bins_dev(e, first, &bins, &n_bins, &host_route);
+    if (rc != BPF_OK)
+      return rc;
+    const long long meta[2] = { n_bins, host_route };
+    long long metas[2 * kMailboxMaxWorld] = { 0 };
+    rc = shard_gather_host_words(e, X, meta, 2, metas);
+    if (rc != BPF_OK)
+      return rc;
+    long long bin_counts[kMailboxMaxWorld], pad = 1;
+    int bin_counts_i[kMailboxMaxWorld];
+    bool any_host = false;
+    for (int r = 0; r < W; ++r)
+    {
+      bin_counts[r] = metas[2 * r];
+      if (bin_counts[r] < 0 || bin_counts[r] > counts[r])
+        return e->fail(BPF_ERR_EXCHANGE, "sharded statistics: a bin count outside its slice arrived");
+      bin_counts_i[r] = (int)bin_counts[r];
+      pad = std::max(pad, bin_counts[r]);
+      any_host = any_host || metas[2 * r + 1] != 0;
+    }
+    if (any_host)
+      route = BPF_SHARD_STATS_ROUTE_HOST;  // the flag travelled with the counts: every rank turns off here together
+    else
+    {
+      // the lists as bpf_shard_stats_label_dev reads them: int64[world][2][pad]
+      const size_t flat = (size_t)W * 2 * (size_t)pad;
+      HIPCHK(e, e->d_x_gather.reserve(flat));
+      HIPCHK(e, hipMemsetAsync(e->d_x_gather.p, 0, flat * sizeof(long long), e->stream));
+      const long long* src[2] = { static_cast<const long long*>(bins), static_cast<const long long*>(bins) + n_bins };
+      long long offs[kMailboxMaxWorld];
+      for (int r = 0; r < W; ++r)
+        offs[r] = (long long)r * 2 * pad;
+      rc = X.gather(src, 2, bin_counts, e->d_x_gather.p, offs, pad);
+      if (rc == BPF_OK)
+        rc = X.finish();
+      if (rc != BPF_OK)
+        return rc;
+      int clusters = 0;
+      rc = bpf_shard_stats_label_dev(e, e->d_x_gather.p, bin_counts_i, W, (int)pad, &clusters);
+      if (rc != BPF_OK)
+        return rc;
+      void* sums = nullptr;
+      size_t n_words = 0;
+      rc = bpf_shard_stats_local_sums_dev(e, &sums, &n_words);
+      if (rc != BPF_OK)
+        return rc;
+      rc = X.reduce_sum(sums, n_words, false);  // limb form: the lane-wise int64 sum is exact
+      if (rc == BPF_OK)
+        rc = X.finish();
+      if (rc != BPF_OK)
+        return rc;
+      rc = bpf_shard_stats_finish_dev(e, sums);
+      if (rc != BPF_OK)
+        return rc;
+      route = BPF_SHARD_STATS_ROUTE_DISTRIBUTED;
+    }
+  }
+  if (route == BPF_SHARD_STATS_ROUTE_HOST)
+  {
+    rc = shard_gather_slices(e, X, counts, n);
+    if (rc != BPF_OK)
+      return rc;
+    std::vector<double> soa((size_t)4 * (size_t)n), all((size_t)4 * (size_t)n);
+    HIPCHK(e, hipMemcpyAsync(soa.data(), e->d_x_gather.p, soa.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    rc = X.finish();
+    if (rc != BPF_OK)
+      return rc;
+    for (int i = 0; i < n; ++i)
+      for (int k = 0; k < 4; ++k)
+        all[4 * (size_t)i + k] = soa[(size_t)k * (size_t)n + i];
+    rc = bpf_shard_stats_host(e, all.data(), n);
+    if (rc != BPF_OK)
+      return rc;
+  }
+  e->ss_global_epoch = e->set_epoch;
+  e->ss_route = route;
+  return BPF_OK;
+}
+}  // namespace
+
+int bpf_shard_update_sensor_cloud(bpf_engine* e, const float* points_xyz, int n_points, long long global_count)
+{
+  if (!e || global_count <= 0)
+    return BPF_ERR_INVALID_ARGUMENT;
+  int rc = shard_step_ready(e);
+  if (rc != BPF_OK)
+    return rc;
+  ShardExchange X{ e };
+  e->mb_totals_valid = false;
+  rc = bpf_shard_score_cloud(e, points_xyz, n_points);
+  if (rc != BPF_OK)
+    return rc;
+  if (e->cloud_max_beams < 2)
+    return BPF_OK;  // PointCloudScanner::updateSensor returns false (point_cloud_scanner.cpp:95-96): nothing was posted
+  return shard_totals_and_normalize(e, X, global_count);
+}
+
+int bpf_shard_compute_cluster_stats(bpf_engine* e, int* cluster_count_out, double set_mean[3], double set_cov[5],
+                                    int* route_out)
+{
+  if (!e)
+    return BPF_ERR_INVALID_ARGUMENT;
+  int rc = shard_ensure_stats(e);
+  if (rc != BPF_OK)
+    return rc;
+  if (route_out)
+    *route_out = e->ss_route;
+  return bpf_pf_compute_cluster_stats(e, cluster_count_out, set_mean, set_cov);
+}
+
+int bpf_shard_get_max_weight_pose(bpf_engine* e, double* max_weight, double pose[3])
+{
+  if (!e || !max_weight || !pose)
+    return BPF_ERR_INVALID_ARGUMENT;
+  int rc = shard_ensure_stats(e);
+  if (rc != BPF_OK)
+    return rc;
+  return bpf_pf_get_max_weight_pose(e, max_weight, pose);
+}
+
+int bpf_shard_exchange_count(bpf_engine* e, long long* out)
+{
+  if (!e || !out)
+    return BPF_ERR_INVALID_ARGUMENT;
+  int rc = shard_step_ready(e);
+  if (rc != BPF_OK)
+    return rc;
+  *out = e->mb.active ? (long long)(e->mb.tot_gen + e->mb.win_gen - e->mb.gen_base) : (long long)e->coll.exchanges;
+  return BPF_OK;
+}

@@ -7,6 +7,8 @@
 //   window   ncclAllReduce(sum, int64) of a [6][count] draw window in which every column has exactly one non-zero
 //            writer, so the integer sum is bit-exact
 //   counts   ncclAllReduce(sum, int32) of the beam-skip agreement counts
+//   lists    ncclAllGather(int64) of the statistics' ragged contributions (sample counts, slices, bin lists), each
+//            padded to the largest one; the limb words of the per-cluster sums go through the int64 all-reduce
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -64,6 +66,13 @@ int bpfc_allgather_f64(void* comm, const double* send, double* recv, size_t coun
   const ncclResult_t r = ncclAllGather(send, recv, count_per_rank, ncclDouble, static_cast<ncclComm_t>(comm),
                                        static_cast<hipStream_t>(stream));
   return r == ncclSuccess ? 0 : fail(r, "ncclAllGather");
+}
+
+int bpfc_allgather_i64(void* comm, const long long* send, long long* recv, size_t count_per_rank, void* stream)
+{
+  const ncclResult_t r = ncclAllGather(send, recv, count_per_rank, ncclInt64, static_cast<ncclComm_t>(comm),
+                                       static_cast<hipStream_t>(stream));
+  return r == ncclSuccess ? 0 : fail(r, "ncclAllGather(int64)");
 }
 
 int bpfc_allreduce_sum_i64(void* comm, long long* buf, size_t count, void* stream)

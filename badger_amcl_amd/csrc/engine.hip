@@ -65,6 +65,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_sharded.inl"
 #include "abi_shard_stats.inl"
 #include "abi_mailbox_step.inl"
+#include "abi_shard_node.inl"
 #include "abi_bootstrap.inl"
 #include "abi_measure.inl"
 }  // extern "C"

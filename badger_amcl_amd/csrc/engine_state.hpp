@@ -328,6 +328,7 @@ struct bpf_engine
     bool win_wait = false;          // that window's columns are in flight: its first consumer kernel has to wait
     unsigned long long hello = 0;
     int fold_deferred = 0;          // > 0: that many scoring partials wait to be folded and posted by the normalise launch
+    unsigned long long gen_base = 0; // tot_gen + win_gen when the set-up ended (bpf_shard_exchange_count starts there)
   } mb;
   int shard_rank = 0, shard_world = 1;  // of the shard exchange in use (mailbox or collective)
   // ---- RCCL collectives (libbadger_pf_rccl.so, loaded by bpf_shard_bootstrap when the mailbox cannot be used)
@@ -346,11 +347,19 @@ struct bpf_engine
       int (*allgather_f64)(void*, const double*, double*, size_t, void*) = nullptr;
       int (*allreduce_sum_i64)(void*, long long*, size_t, void*) = nullptr;
       int (*allreduce_sum_i32)(void*, int*, size_t, void*) = nullptr;
+      int (*allgather_i64)(void*, const long long*, long long*, size_t, void*) = nullptr;
     } fn;
     DevBuf<double> totals;
     DevBuf<long long> window[2];
     int window_turn = 0;
+    DevBuf<long long> send, recv;       // a ragged all-gather, padded to the largest contribution
+    unsigned long long exchanges = 0;   // collectives issued since the communicator was made
   } coll;
+  // ---- the one-call sharded forms that do their own exchanges (abi_shard_node.inl)
+  DevBuf<long long> d_x_words, d_x_gather;  // a few words (counts, flags) and their gathered form; gathered payloads
+  PinnedBuf<long long> h_x_words;
+  long long ss_global_epoch = -1;   // set_epoch for which bpf_shard_compute_cluster_stats installed the GLOBAL figures
+  int ss_route = 0;                 //   and the route it took (BPF_SHARD_STATS_ROUTE_*)
   DevBuf<int> d_shard_flags;        // the CDF-miss flag word of the one-call sharded updates
   void* mb_totals = nullptr;        // bpf_shard_mailbox_update_sensor_planar: this update's totals (mailbox slots)
   bool mb_totals_valid = false;

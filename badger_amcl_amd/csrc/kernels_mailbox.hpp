@@ -17,7 +17,8 @@
 //                                256  tot_val [2][16] f64     totals: values
 //                                512  win_done[2][16] u64     window: "rank r has written all its columns"
 //                                768  hello   [16]    u64     connect-time self-test
-//                               4096  win     [2][6][max_window] i64
+//                               4096  win     [2][6][max_window] i64   draw windows; also the spans of the general
+//                                                                      small exchanges, by word offset (see below)
 #pragma once
 #include "device_types.hpp"
 
@@ -171,6 +172,95 @@ __global__ void k_mailbox_wait(const MailboxDev M, int which, int parity, unsign
 {
   (void)mb_block_wait(M, which == 0 ? mb_tot_gen(M.peer[M.rank], parity, 0) : mb_win_done(M.peer[M.rank], parity, 0), gen,
                       which);
+}
+
+// ---- general small exchanges (the one-call statistics, the beam-skip counts): the window region as 6 * max_window
+// int64 words in which a rank's span is addressed by WORD OFFSET instead of by column c % world.  They share win_gen,
+// the "done" words and the two parities with the draw windows, so the ordering argument above carries over: a rank
+// posts exchange g + 1 only behind (in stream order) its consumer of g, which has seen every peer's word of g.
+//
+//   ragged all-gather   rank r stores rows x count[r] words at its offset (the prefix sum over the ranks before it) into
+//                       every peer; the consumer copies the spans out of its own mailbox into engine memory, in the
+//                       layout the next stage wants
+//   all-reduce(sum)     gather-then-sum: rank r stores its n words at r * n into every peer; the consumer adds the W
+//                       spans lane-wise IN RANK ORDER (integer sums: exact, and the same bits on every rank)
+struct MbPostArgs
+{
+  const long long* src[4];  // row k of this rank's contribution (int32 words when widen32)
+  int rows;
+  int widen32;              // the source rows are int32: sign-extended into the int64 words
+  long long count;          // words per row
+  long long word_off;       // of this rank's span in the window region
+};
+
+// where the spans of a ragged gather lie in the source (a mailbox window, or the padded receive buffer of a
+// collective all-gather) and where they go
+struct MbRagged
+{
+  int world, rows;
+  long long count[kMailboxMaxWorld];       // words per row of rank r
+  long long src_off[kMailboxMaxWorld];     // rank r's row k starts at src_off[r] + k * src_stride[r]
+  long long src_stride[kMailboxMaxWorld];
+  long long dst_off[kMailboxMaxWorld];     //   and goes to dst_off[r] + k * dst_stride
+  long long dst_stride;
+};
+
+// producer of both kinds: plain vector stores into every peer, then "done" by the last block (<= 64 blocks)
+__global__ void k_mailbox_post_words(const MailboxDev M, const MbPostArgs A, int parity, unsigned long long gen,
+                                     unsigned* counter)
+{
+  const long long n = (long long)A.rows * A.count;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+  {
+    const int row = (int)(i / A.count);
+    const long long j = i - (long long)row * A.count;
+    const long long v = A.widen32 ? (long long)reinterpret_cast<const int*>(A.src[row])[j] : A.src[row][j];
+    for (int r = 0; r < M.world; ++r)
+      mb_window(M.peer[r], parity, M.max_window)[A.word_off + i] = v;
+  }
+  mb_window_done_when_last(M, parity, gen, counter);
+}
+
+// consumer of a ragged all-gather (<= kMailboxFusedWaitBlocks blocks, every one waits).  M.world == 0: no mailbox, the
+// spans are already in `src` (the collective branch) and only the re-layout is done.
+__global__ void k_mailbox_take_ragged(const MailboxDev M, const long long* src, long long* dst, const MbRagged L,
+                                      int parity, unsigned long long gen)
+{
+  if (M.world > 0)
+  {
+    if (!mb_block_wait(M, mb_win_done(M.peer[M.rank], parity, 0), gen, 1))
+      return;  // the destination stays as it was
+    src = mb_window(M.peer[M.rank], parity, M.max_window);
+  }
+  for (int r = 0; r < L.world; ++r)
+  {
+    const long long c = L.count[r], n = (long long)L.rows * c;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    {
+      const int row = (int)(i / c);
+      const long long j = i - (long long)row * c;
+      dst[L.dst_off[r] + (long long)row * L.dst_stride + j] = src[L.src_off[r] + (long long)row * L.src_stride[r] + j];
+    }
+  }
+}
+
+// consumer of an all-reduce(sum): dst[i] = span_0[i] + span_1[i] + ... in rank order (int32 words when narrow32)
+__global__ void k_mailbox_take_sum(const MailboxDev M, void* dst, long long n, int narrow32, int parity,
+                                   unsigned long long gen)
+{
+  if (!mb_block_wait(M, mb_win_done(M.peer[M.rank], parity, 0), gen, 1))
+    return;
+  const long long* s = mb_window(M.peer[M.rank], parity, M.max_window);
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+  {
+    long long acc = 0;
+    for (int r = 0; r < M.world; ++r)
+      acc += s[(long long)r * n + i];
+    if (narrow32)
+      static_cast<int*>(dst)[i] = (int)acc;
+    else
+      static_cast<long long*>(dst)[i] = acc;
+  }
 }
 
 // Self-test of the window path with a payload that can be checked: rank r stores pattern(r, gen, column) into the

@@ -390,4 +390,78 @@ private:
   int max_beams_ = 0;
 };
 
+// One filter sharded over the GPUs of a node, this process being one rank of it (badger_pf.h, "sharded operation"):
+// the engine holds this rank's contiguous slice and the GLOBAL min / max sample counts; every member below except the
+// constructor is collective -- every rank calls it, in the same order.  The exchanges are the engine's own (mailbox
+// peer stores, RCCL after the bootstrap's fallback); the class owns the figures the C calls pass back and forth.
+class ShardedParticleFilter
+{
+public:
+  // pf: this rank's filter, its slice loaded; global_count: samples of the whole set; leaf_count: of the whole set's
+  // histogram tree (only the systematic resampler reads it before the first resample)
+  ShardedParticleFilter(std::shared_ptr<ParticleFilter> pf, int global_count, int leaf_count = 1, int first_window = 4096)
+      : pf_(std::move(pf)), global_count_(global_count), leaf_count_(leaf_count), window_hint_(first_window)
+  {
+  }
+  // host_port: "host:port" rank 0 listens on; max_window >= the filter's max_samples; flags: BPF_BOOTSTRAP_*;
+  // returns BPF_SHARD_EXCHANGE_MAILBOX or BPF_SHARD_EXCHANGE_RCCL
+  int bootstrap(int rank, int world, const std::string& host_port, long long max_window, int flags = 0)
+  {
+    int mode = 0;
+    e().check(bpf_shard_bootstrap(e().get(), rank, world, host_port.c_str(), max_window, flags, &mode));
+    rank_ = rank;
+    world_ = world;
+    return mode;
+  }
+  // PlanarScanner::updateSensor over the shards (beam skipping of the prob model included)
+  bool updateSensor(std::shared_ptr<PlanarData> data)
+  {
+    e().check(bpf_shard_update_sensor_planar(e().get(), data->ranges_.data(), data->angles_.data(), data->range_count_,
+                                             data->range_max_, global_count_));
+    return true;
+  }
+  // PointCloudScanner::updateSensor over the shards; xyz: n packed float triples in the scanner frame
+  bool updateSensorCloud(const float* xyz, int n)
+  {
+    e().check(bpf_shard_update_sensor_cloud(e().get(), xyz, n, global_count_));
+    return true;
+  }
+  // ParticleFilter::updateResample over the shards; this rank adopts its even share of the new set
+  void updateResample()
+  {
+    e().check(bpf_shard_update_resample(e().get(), &global_count_, &leaf_count_, &bin_count_, &windows_, &window_hint_,
+                                        &cdf_miss_));
+  }
+  // Node2D::getMaxWeightPose over the GLOBAL set, the same bits on every rank
+  void getMaxWeightPose(double* max_weight_out, std::array<double, 3>* max_pose)
+  {
+    double pose[3] = { 0, 0, 0 };
+    e().check(bpf_shard_get_max_weight_pose(e().get(), max_weight_out, pose));
+    *max_pose = { pose[0], pose[1], pose[2] };
+  }
+  // ParticleFilter::getClusterStats over the GLOBAL set
+  bool getClusterStats(int cidx, double* weight, std::array<double, 3>* mean)
+  {
+    int count = 0;
+    e().check(bpf_shard_compute_cluster_stats(e().get(), &count, nullptr, nullptr, &route_));
+    return pf_->getClusterStats(cidx, weight, mean);
+  }
+  void shutdown() { e().check(bpf_shard_shutdown(e().get())); }
+  int globalSampleCount() const { return global_count_; }
+  int leafCount() const { return leaf_count_; }
+  int binCount() const { return bin_count_; }
+  int windowsUsed() const { return windows_; }
+  bool cdfMiss() const { return cdf_miss_ != 0; }
+  int statsRoute() const { return route_; }  // BPF_SHARD_STATS_ROUTE_* of the last getClusterStats
+  int rank() const { return rank_; }
+  int world() const { return world_; }
+
+private:
+  Engine& e() { return pf_->engine(); }
+  std::shared_ptr<ParticleFilter> pf_;
+  int global_count_, leaf_count_, window_hint_;
+  int bin_count_ = 0, windows_ = 0, cdf_miss_ = 0, route_ = 0;
+  int rank_ = 0, world_ = 1;
+};
+
 }  // namespace badger_amcl_amd

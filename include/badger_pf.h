@@ -532,7 +532,8 @@ int bpf_shard_converged_dev(bpf_engine* e, const void* x_all_dev, const void* y_
  * installed result; the plain getters then evaluate THIS ENGINE'S SLICE ONLY (clusters cut at the shard boundary,
  * local labels, weights that sum to about 1 / world): that is not the global figure, run the stages again for it.
  * The stage functions are asynchronous on the engine's stream except where they return a count; no kernel waits for
- * another rank, the exchanges are the caller's, between the calls.  Calls out of order, or after the slice changed,
+ * another rank, the exchanges are the caller's, between the calls (a host without a transport of its own calls
+ * bpf_shard_compute_cluster_stats / bpf_shard_get_max_weight_pose instead: the same stages over the engine's exchange).  Calls out of order, or after the slice changed,
  * return BPF_ERR_NOT_CONFIGURED.  Two forms, chosen by the GLOBAL count so that every rank chooses alike:
  *
  * Gathered form (global_count <= 4096, the tracking regime).  Crosses between ranks: one all-gather of the slices'
@@ -632,7 +633,12 @@ int bpf_shard_systematic_window_dev(bpf_engine* e, uint64_t rng_state48, int cou
  *   window   a fresh [6][stride] int64 window for the next exchange: bpf_shard_draw_window_dev /
  *            bpf_shard_systematic_window_dev given this pointer store every owned column into all peers' copies, and
  *            the first consumer (bpf_kld_feed_dev / bpf_kld_insert_dev / bpf_kld_stop_dev) waits for all shards.
- *            The window stays valid until the next-but-one call; copy out what has to live longer. */
+ *            The window stays valid until the next-but-one call; copy out what has to live longer.
+ * The one-call forms further down (bpf_shard_update_sensor_planar with beam skipping, bpf_shard_compute_cluster_stats,
+ * bpf_shard_get_max_weight_pose) send their small payloads through the same window region, addressed by word offset:
+ * ragged all-gathers (every rank's span in rank order) and an integer all-reduce as gather-then-sum in rank order.
+ * They take window generations of their own, so a window handed out by bpf_shard_mailbox_window must have been
+ * consumed before one of them is called. */
 /* A wait is bounded (default 5 s; set before create / connect).  When a bound runs out the consumer kernel leaves its
  * data alone -- after a failed wait for the totals the weights stay scored but NOT normalised, the local total in
  * bpf_shard_scalars_dev [0]; a failed window wait touches nothing of the current set -- and the next host check returns
@@ -687,11 +693,45 @@ int bpf_shard_bootstrap(bpf_engine* e, int rank, int world, const char* host_por
 int bpf_shard_shutdown(bpf_engine* e);
 /* The sharded sensor update and resample as one call each, over whichever exchange bpf_shard_bootstrap (or
  * bpf_shard_mailbox_connect) set up; arguments as bpf_shard_mailbox_update_sensor_planar / _update_resample, with the
- * CDF-miss flag word owned by the engine (*cdf_miss_out, nullable, reads it back). */
+ * CDF-miss flag word owned by the engine (*cdf_miss_out, nullable, reads it back).
+ * bpf_shard_update_sensor_planar is NOT an alias of the mailbox form: with the prob model's beam skipping active it
+ * sums the per-beam counts over the engine's own exchange between the two passes (mailbox: gather-then-sum of
+ * max_beams words through the window region; RCCL: an int32 all-reduce) and finishes the update, where
+ * bpf_shard_mailbox_update_sensor_planar hands BPF_SHARD_NEED_BEAM_COUNTS back to a caller with a transport of its
+ * own.  It never returns BPF_SHARD_NEED_BEAM_COUNTS. */
 int bpf_shard_update_sensor_planar(bpf_engine* e, const double* ranges, const double* angles, int range_count,
                                    double range_max, long long global_count);
 int bpf_shard_update_resample(bpf_engine* e, int* global_count_io, int* leaf_count_io, int* bin_count_out,
                               int* windows_out, int* window_hint_io, int* cdf_miss_out);
+/* PointCloudScanner::updateSensor (point_cloud_scanner.cpp:92-102) over the shards, as bpf_pf_update_sensor_cloud has
+ * it for one engine: bpf_shard_score_cloud, the exchange of the W totals, bpf_shard_normalize_dev.  Leaves what
+ * bpf_shard_update_resample requires of "the totals of this update". */
+int bpf_shard_update_sensor_cloud(bpf_engine* e, const float* points_xyz, int n_points, long long global_count);
+/* The statistics of the GLOBAL set in one collective call (every rank, in the same order): the stage functions of
+ * "cluster statistics of a sharded set" above, in the order badger_amcl_amd/sharded.py runs them, with the engine's
+ * own exchanges between them -- the local sample counts, then by the GLOBAL count the gathered form (<= 4096: the
+ * slices' x / y / theta / weight) or the distributed form (the bin counts with the host-route flags, the bin lists, the
+ * limb words of the per-cluster sums as an exact integer all-reduce, in rounds when they exceed the window region);
+ * the host route (the slices, 32 B per particle) when any rank raises the flag or the gathered form asks for it.
+ * Afterwards bpf_pf_get_cluster and the plain getters of THIS engine return the global figures, the same bits on
+ * every rank, until the slice next changes.  Lazy: a second query while no slice has changed makes no exchange
+ * (bpf_shard_exchange_count stays).  *route_out (nullable): which form evaluated the figures in force.
+ * BPF_ERR_NOT_CONFIGURED without an exchange; BPF_ERR_EXCHANGE after a mailbox wait that ran out -- the set and any
+ * statistics installed before are untouched, and bpf_shard_mailbox_error_stage reports these waits as the window
+ * kind. */
+enum
+{
+  BPF_SHARD_STATS_ROUTE_GATHERED = 1,
+  BPF_SHARD_STATS_ROUTE_DISTRIBUTED = 2,
+  BPF_SHARD_STATS_ROUTE_HOST = 3
+};
+int bpf_shard_compute_cluster_stats(bpf_engine* e, int* cluster_count_out, double set_mean[3], double set_cov[5],
+                                    int* route_out);
+/* Node2D::getMaxWeightPose over the global set (the same evaluation, the same laziness) */
+int bpf_shard_get_max_weight_pose(bpf_engine* e, double* max_weight, double pose[3]);
+/* Diagnostic: exchanges this engine has issued since bpf_shard_bootstrap (or bpf_shard_mailbox_connect) set the
+ * exchange up -- totals, draw windows, gathers and reduce rounds together. */
+int bpf_shard_exchange_count(bpf_engine* e, long long* out);
 /* insert every key of the window into the engine's histogram tree (no stop rule): the tree of a systematic
  * resample, or of an initial set (keys as bpf_kld_feed / bpf_kld_feed_dev take them) */
 int bpf_kld_insert(bpf_engine* e, const void* keys, int keys_are_int64, int stride, int n_keys);
