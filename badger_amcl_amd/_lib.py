@@ -127,6 +127,16 @@ SIGNATURES = {
     "bpf_shard_stats_local_sums_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "bpf_shard_stats_finish_dev": (C.c_int, [_vp, _vp]),
     "bpf_shard_stats_host": (C.c_int, [_vp, _dp, C.c_int]),
+    "bpf_shard_init_with_gaussian": (C.c_int, [_vp, _dp, _dp, _dp, C.c_longlong, C.c_int, C.c_longlong]),
+    "bpf_shard_init_with_random_poses": (C.c_int, [_vp, C.c_longlong, C.c_int, C.c_longlong]),
+    "bpf_shard_tree_local_bins_dev": (C.c_int, [_vp, C.c_longlong, C.POINTER(_vp), _ip, _ip]),
+    "bpf_shard_tree_merge_dev": (C.c_int, [_vp, _vp, _ip, C.c_int, C.c_int, _ip, _ip]),
+    "bpf_shard_tree_local_keys_dev": (C.c_int, [_vp, C.POINTER(_vp), _ip]),
+    "bpf_shard_tree_from_keys": (C.c_int, [_vp, _ip, C.c_int, _ip, _ip]),
+    "bpf_shard_tree_last_route": (C.c_int, [_vp, _ip]),
+    "bpf_shard_init_with_gaussian_all": (C.c_int, [_vp, _dp, _dp, _dp]),
+    "bpf_shard_init_with_random_poses_all": (C.c_int, [_vp]),
+    "bpf_shard_global_leaf_count": (C.c_int, [_vp, _ip, _ip]),
     "bpf_shard_mailbox_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_longlong, _vp]),
     "bpf_shard_mailbox_connect": (C.c_int, [_vp, _vp]),
     "bpf_shard_mailbox_selftest": (C.c_int, [_vp, C.c_int]),

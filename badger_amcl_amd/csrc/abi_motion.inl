@@ -142,8 +142,9 @@ int update_action(bpf_engine* e, const double pose[3], const double delta[3], co
   long long consumed = 0;
   // optimistic: poses go to the other set, which becomes current only once the pass is known good
   int rc = generate_gaussians(e, 3 * global_count, 3 * global_first, 3ll * n, M.sd, &consumed, [&]() {
-    hipLaunchKernelGGL(k_motion_apply, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, src.dev(), dst.dev(), n, M,
-                       (const double*)e->d_gauss.p);
+    if (n > 0)  // (an empty shard still walks the stream)
+      hipLaunchKernelGGL(k_motion_apply, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, src.dev(), dst.dev(), n, M,
+                         (const double*)e->d_gauss.p);
   });
   if (rc != BPF_OK)
     return rc;

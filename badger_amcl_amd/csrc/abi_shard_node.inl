@@ -38,11 +38,11 @@ int shard_gather_host_words(bpf_engine* e, ShardExchange& X, const long long* mi
 }
 
 // x / y / theta / weight of every slice, concatenated in rank order: d_x_gather = double[4][n]
-int shard_gather_slices(bpf_engine* e, ShardExchange& X, const long long* counts, int n)
+int shard_gather_slices(bpf_engine* e, ShardExchange& X, const long long* counts, int n, SampleSet* set = nullptr)
 {
   const int W = e->shard_world;
   HIPCHK(e, e->d_x_gather.reserve((size_t)4 * (size_t)n));
-  SampleSet& s = e->sets[e->cur];
+  SampleSet& s = set ? *set : e->sets[e->cur];
   const long long* src[4] = { reinterpret_cast<const long long*>(s.x.p), reinterpret_cast<const long long*>(s.y.p),
                               reinterpret_cast<const long long*>(s.th.p), reinterpret_cast<const long long*>(s.w.p) };
   long long offs[kMailboxMaxWorld], at = 0;
@@ -225,6 +225,166 @@ int bpf_shard_get_max_weight_pose(bpf_engine* e, double* max_weight, double pose
   if (rc != BPF_OK)
     return rc;
   return bpf_pf_get_max_weight_pose(e, max_weight, pose);
+}
+
+namespace
+{
+// The tree of the GLOBAL set (abi_shard_init.inl) over the engine's exchange: `s` holds this rank's n samples from
+// global index `first`, counts[] every rank's sample count.  Installs the counts; a failed exchange installs nothing.
+int shard_global_tree(bpf_engine* e, ShardExchange& X, SampleSet& s, int n, long long first, const long long* counts,
+                      int* leaf_out, int* bins_out)
+{
+  const int W = e->shard_world;
+  int n_bins = 0, out_of_range = 0;
+  int rc = tree_local_bins(e, s, n, first, &n_bins, &out_of_range);
+  if (rc != BPF_OK)
+    return rc;
+  const long long meta[2] = { n_bins, out_of_range };
+  long long metas[2 * kMailboxMaxWorld] = { 0 };
+  rc = shard_gather_host_words(e, X, meta, 2, metas);
+  if (rc != BPF_OK)
+    return rc;
+  long long bin_counts[kMailboxMaxWorld], pad = 1, total = 0;
+  int bin_counts_i[kMailboxMaxWorld];
+  bool any_out = false;
+  for (int r = 0; r < W; ++r)
+  {
+    bin_counts[r] = metas[2 * r];
+    if (bin_counts[r] < 0 || bin_counts[r] > counts[r])
+      return e->fail(BPF_ERR_EXCHANGE, "global tree: a bin count outside its slice arrived");
+    bin_counts_i[r] = (int)bin_counts[r];
+    pad = std::max(pad, bin_counts[r]);
+    any_out = any_out || metas[2 * r + 1] != 0;
+    total += counts[r];
+  }
+  if (any_out)
+  {
+    // the keys route (the flag travelled with the counts: every rank turns off here together): the slices cross,
+    // every pose's key goes through the host tree in index order
+    const int N = (int)total;
+    rc = shard_gather_slices(e, X, counts, N, &s);
+    if (rc != BPF_OK)
+      return rc;
+    std::vector<double> soa((size_t)3 * (size_t)N);
+    HIPCHK(e, hipMemcpyAsync(soa.data(), e->d_x_gather.p, soa.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    rc = X.finish();
+    if (rc != BPF_OK)
+      return rc;
+    std::vector<int> keys((size_t)3 * (size_t)N);
+    for (int i = 0; i < N; ++i)
+      host_pose_key(soa[i], soa[(size_t)N + i], soa[2 * (size_t)N + i], &keys[3 * (size_t)i]);
+    return tree_from_keys(e, keys.data(), N, leaf_out, bins_out);
+  }
+  const size_t flat = (size_t)W * 2 * (size_t)pad;
+  HIPCHK(e, e->d_x_gather.reserve(flat));
+  HIPCHK(e, hipMemsetAsync(e->d_x_gather.p, 0, flat * sizeof(long long), e->stream));
+  const long long* src[2] = { e->d_gt_bins.p, e->d_gt_bins.p + n_bins };
+  long long offs[kMailboxMaxWorld];
+  for (int r = 0; r < W; ++r)
+    offs[r] = (long long)r * 2 * pad;
+  rc = X.gather(src, 2, bin_counts, e->d_x_gather.p, offs, pad);
+  if (rc == BPF_OK)
+    rc = X.finish();
+  if (rc != BPF_OK)
+    return rc;
+  return tree_merge(e, e->d_x_gather.p, bin_counts_i, W, (int)pad, leaf_out, bins_out);
+}
+
+// write this rank's even share into the spare set, find the global tree, and only then make the set current
+int shard_init_all(bpf_engine* e, bool spread, const std::function<int(long long, int, long long, uint64_t*)>& write)
+{
+  if (!e->have_pf)
+    return e->fail(BPF_ERR_NOT_CONFIGURED, "bpf_pf_create first");
+  int rc = shard_step_ready(e);
+  if (rc != BPF_OK)
+    return rc;
+  HIPCHK(e, hipSetDevice(e->device));
+  ShardExchange X{ e };
+  const int W = e->shard_world, rank = e->shard_rank;
+  const long long G = e->max_samples;
+  long long counts[kMailboxMaxWorld] = { 0 };
+  for (int r = 0; r < W; ++r)
+    counts[r] = (G * (r + 1)) / W - (G * r) / W;
+  const long long first = (G * rank) / W;
+  const int n = (int)counts[rank];
+  uint64_t rng_after = 0;
+  rc = write(first, n, G, &rng_after);
+  if (rc != BPF_OK)
+    return rc;
+  const int leaf_before = e->leaf_count, bins_before = e->bin_count, route_before = e->gt_route;
+  const bool pending_before = e->tree_pending;
+  int leaf = 0, bins = 0;
+  rc = shard_global_tree(e, X, e->sets[e->cur ^ 1], n, first, counts, &leaf, &bins);
+  const int route = e->gt_route;
+  // (the counts describe the set that is not current yet)
+  e->leaf_count = leaf_before;
+  e->bin_count = bins_before;
+  e->gt_route = route_before;
+  e->tree_pending = pending_before;
+  if (rc != BPF_OK)
+    return rc;
+  rc = shard_init_commit(e, n, rng_after, spread);
+  if (rc != BPF_OK)
+    return rc;
+  tree_install(e, leaf, bins, route);
+  return BPF_OK;
+}
+}  // namespace
+
+int bpf_shard_init_with_gaussian_all(bpf_engine* e, const double mean[3], const double rotation[9],
+                                     const double sigma[3])
+{
+  if (!e || !mean || !rotation || !sigma)
+    return BPF_ERR_INVALID_ARGUMENT;
+  return shard_init_all(e, false, [&](long long first, int n, long long G, uint64_t* rng_after) {
+    return shard_init_gaussian_write(e, mean, rotation, sigma, first, n, G, rng_after);
+  });
+}
+
+int bpf_shard_init_with_random_poses_all(bpf_engine* e)
+{
+  if (!e)
+    return BPF_ERR_INVALID_ARGUMENT;
+  return shard_init_all(e, true, [&](long long first, int n, long long G, uint64_t* rng_after) {
+    return shard_init_random_write(e, first, n, G, rng_after);
+  });
+}
+
+int bpf_shard_global_leaf_count(bpf_engine* e, int* leaf_count_out, int* bin_count_out)
+{
+  if (!e || !leaf_count_out || !bin_count_out)
+    return BPF_ERR_INVALID_ARGUMENT;
+  if (!e->have_pf)
+    return e->fail(BPF_ERR_NOT_CONFIGURED, "bpf_pf_create first");
+  int rc = shard_step_ready(e);
+  if (rc != BPF_OK)
+    return rc;
+  if (!e->tree_pending && e->leaf_count > 0)
+  {
+    *leaf_count_out = e->leaf_count;  // of the global set (an init, this call or a resample installed it): no exchange
+    *bin_count_out = e->bin_count;
+    return BPF_OK;
+  }
+  HIPCHK(e, hipSetDevice(e->device));
+  ShardExchange X{ e };
+  const int W = e->shard_world, rank = e->shard_rank;
+  long long counts[kMailboxMaxWorld] = { 0 };
+  const long long mine = e->sample_count;
+  rc = shard_gather_host_words(e, X, &mine, 1, counts);
+  if (rc != BPF_OK)
+    return rc;
+  long long total = 0, first = 0;
+  for (int r = 0; r < W; ++r)
+  {
+    if (counts[r] < 0)
+      return e->fail(BPF_ERR_EXCHANGE, "global tree: a negative sample count arrived");
+    if (r < rank)
+      first += counts[r];
+    total += counts[r];
+  }
+  if (total <= 0 || total > (long long)e->max_samples)
+    return e->fail(BPF_ERR_INVALID_ARGUMENT, "global tree: the global set is empty, or beyond max_samples");
+  return shard_global_tree(e, X, e->sets[e->cur], e->sample_count, first, counts, leaf_count_out, bin_count_out);
 }
 
 int bpf_shard_exchange_count(bpf_engine* e, long long* out)

@@ -29,6 +29,7 @@
 #include "kernels_fused.hpp"
 #include "kernels_stats.hpp"
 #include "kernels_shard_stats.hpp"
+#include "kernels_shard_init.hpp"
 #include "kernels_score.hpp"
 #include "kernels_window.hpp"
 
@@ -64,6 +65,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_mailbox.inl"
 #include "abi_sharded.inl"
 #include "abi_shard_stats.inl"
+#include "abi_shard_init.inl"
 #include "abi_mailbox_step.inl"
 #include "abi_shard_node.inl"
 #include "abi_bootstrap.inl"

@@ -433,6 +433,13 @@ struct bpf_engine
   DevBuf<int> d_ss_gtmin, d_ss_eslot, d_ss_eroot, d_ss_label, d_ss_binlabel;
   DevBuf<double> d_ss_w;
 
+  // ---- the GLOBAL set's histogram tree from the ranks' bin lists (kernels_shard_init.hpp, abi_shard_init.inl)
+  DevBuf<long long> d_gt_bins;      // [2][bins] this slice's list: packed keys, global first indices
+  DevBuf<unsigned long long> d_gt_key;
+  DevBuf<int> d_gt_tmin, d_gt_eslot, d_gt_tiles, d_gt_flags;
+  PinnedBuf<int> h_gt_flags;
+  int gt_route = 0;                 // BPF_SHARD_TREE_ROUTE_* of the counts installed last (0: none since the last init)
+
   // ---- cluster statistics (host, lazy)
   std::vector<bpf_cluster> clusters;
   double set_mean[3] = { 0, 0, 0 }, set_cov[5] = { 0, 0, 0, 0, 0 };

@@ -14,6 +14,13 @@ xGMI) carries the three small exchanges the path really has:
                    Recovery draws (w_diff > 0): every rank resolves the same draw chain and shard 0 writes
                    the random free-space poses -- no further exchange.
 
+  init             (init_with_gaussian / init_with_random_poses: every rank writes its even share of the set ONE
+                   engine would produce and ends on the same drand48 state -- no exchange for the poses) then the
+                   histogram tree of the GLOBAL set, whose leaf count the systematic resampler reads first: all-gather
+                   of the per-rank bin lists (16 B per occupied bin), merged redundantly on every rank into the distinct
+                   keys in first-appearance order, and the tree of those.  A key outside the packing range on any
+                   rank sends every rank down the keys route (12 B per particle, host tree).
+
   statistics       (compute_cluster_stats / get_cluster / get_max_weight_pose: the clusters of the GLOBAL set and
                    the pose of the heaviest one, the same bits on every rank as one engine holding the whole set)
                    up to 4096 particles: one all-gather of the slices' x / y / theta / weight (<= 128 KB), every rank
@@ -332,6 +339,78 @@ class HipShardBackend:
     def stats_max_weight_pose(self):
         return self.pf.getMaxWeightPose()
 
+    # ---- a sharded set initialised on its ranks, and the global set's tree (include/badger_pf.h, bpf_shard_init_*,
+    # bpf_shard_tree_*)
+    @staticmethod
+    def _gauss_args(mean, rotation, sigma):
+        m, r, d = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (mean, rotation, sigma))
+        assert m.size == 3 and r.size == 9 and d.size == 3
+        dp = C.POINTER(C.c_double)
+        return (m, r, d), (m.ctypes.data_as(dp), r.ctypes.data_as(dp), d.ctypes.data_as(dp))
+
+    def init_gaussian(self, mean, rotation, sigma, global_first, local_count, global_count):
+        keep, ptr = self._gauss_args(mean, rotation, sigma)
+        self.e.check(self.e.lib.bpf_shard_init_with_gaussian(self.e.h, ptr[0], ptr[1], ptr[2], int(global_first),
+                                                             int(local_count), int(global_count)))
+
+    def init_random_poses(self, global_first, local_count, global_count):
+        self.e.check(self.e.lib.bpf_shard_init_with_random_poses(self.e.h, int(global_first), int(local_count),
+                                                                 int(global_count)))
+
+    def init_gaussian_all(self, mean, rotation, sigma):
+        """The init and the global tree over the engine's own exchange (mailbox): (leaf_count, bin_count)."""
+        keep, ptr = self._gauss_args(mean, rotation, sigma)
+        self.e.check(self.e.lib.bpf_shard_init_with_gaussian_all(self.e.h, ptr[0], ptr[1], ptr[2]))
+        return self.global_leaf_count()
+
+    def init_random_poses_all(self):
+        self.e.check(self.e.lib.bpf_shard_init_with_random_poses_all(self.e.h))
+        return self.global_leaf_count()
+
+    def global_leaf_count(self):
+        a, b = C.c_int(), C.c_int()
+        self.e.check(self.e.lib.bpf_shard_global_leaf_count(self.e.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def tree_local_bins(self, global_first):
+        """(int64 [2, n_bins] device tensor: packed keys, global first indices; key-out-of-range flag)."""
+        p, n, oor = C.c_void_p(), C.c_int(), C.c_int()
+        self.e.check(self.e.lib.bpf_shard_tree_local_bins_dev(self.e.h, int(global_first), C.byref(p), C.byref(n),
+                                                              C.byref(oor)))
+        if n.value == 0:
+            return torch.empty((2, 0), dtype=torch.int64, device=self.device), bool(oor.value)
+        return torch.as_tensor(_DevArray(p.value, (2, n.value), "<i8"), device=self.device), bool(oor.value)
+
+    def tree_merge(self, all_bins, counts, pad):
+        """all_bins: int64 [world, 2, pad] gathered lists; installs and returns (leaf_count, bin_count)."""
+        c = (C.c_int * len(counts))(*[int(v) for v in counts])
+        a, b = C.c_int(), C.c_int()
+        self.e.check(self.e.lib.bpf_shard_tree_merge_dev(self.e.h, C.c_void_p(all_bins.data_ptr()), c, len(counts),
+                                                         int(pad), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def tree_local_keys(self):
+        """int64 [3, n_local] device tensor: the raw histogram keys of the slice (the keys route only)."""
+        p, n = C.c_void_p(), C.c_int()
+        self.e.check(self.e.lib.bpf_shard_tree_local_keys_dev(self.e.h, C.byref(p), C.byref(n)))
+        if n.value == 0:
+            return torch.empty((3, 0), dtype=torch.int64, device=self.device)
+        k = torch.as_tensor(_DevArray(p.value, (n.value, 3), "<i4"), device=self.device)
+        return k.to(torch.int64).t().contiguous()
+
+    def tree_from_keys(self, all_keys):
+        """all_keys: int [global_n, 3] on the host, in index order; installs and returns (leaf_count, bin_count)."""
+        k = np.ascontiguousarray(all_keys, dtype=np.int32)
+        a, b = C.c_int(), C.c_int()
+        self.e.check(self.e.lib.bpf_shard_tree_from_keys(self.e.h, k.ctypes.data_as(C.POINTER(C.c_int)), k.shape[0],
+                                                         C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def tree_last_route(self):
+        r = C.c_int()
+        self.e.check(self.e.lib.bpf_shard_tree_last_route(self.e.h, C.byref(r)))
+        return r.value
+
     def rng_state(self):
         return self.pf.getRngState()
 
@@ -372,8 +451,10 @@ class ShardedFilter:
     """ParticleFilter::updateSensor / updateResample over W shards (see module docstring)."""
 
     def __init__(self, backend, dist, rank=None, world=None, first_window=4096, exchange="auto",
-                 mailbox_timeout_ms=None, kld_count=None):
-        """kld_count: what the KLD stop rule counts, pf.KLD_COUNT_LEAVES or pf.KLD_COUNT_BINS (None: the backend's
+                 mailbox_timeout_ms=None, kld_count=None, init_follows=False):
+        """init_follows: the caller starts the set with init_with_gaussian / init_with_random_poses next, so the tree
+        of whatever the engines hold now is not built (it matters to the systematic resampler only).
+        kld_count: what the KLD stop rule counts, pf.KLD_COUNT_LEAVES or pf.KLD_COUNT_BINS (None: the backend's
         current mode).  Every rank must use the same mode; the constructor checks it over the process group."""
         self.b = backend
         self.mailbox_timeout_ms = mailbox_timeout_ms
@@ -397,7 +478,8 @@ class ShardedFilter:
         modes = self._all_gather(torch.tensor([self.kld_count], dtype=torch.int64, device=self.device)).cpu().tolist()
         if len(set(int(m) for m in modes)) != 1:
             raise ValueError("ShardedFilter: the ranks use different KLD count modes %s" % modes)
-        self.window_hint = first_window
+        self.window_hint = self._first_window = first_window
+        self.tree_route = None  # how the last init found the global leaf count: "device", "host", "bins" or "keys"
         self.out = torch.zeros((3, self.max_global), dtype=torch.float64, device=self.device)
         self.flags = torch.zeros(4, dtype=torch.int32, device=self.device)
         self._windows = {}
@@ -421,7 +503,7 @@ class ShardedFilter:
             self.mailbox = self._setup_mailbox()
         if exchange == "mailbox" and not self.mailbox:
             raise RuntimeError("mailbox exchange requested but not every rank could set it up")
-        if backend.resample_model() == 1:
+        if backend.resample_model() == 1 and not init_follows:
             # the systematic resampler sizes the new set from the leaf count of the CURRENT set's tree, which the
             # reference builds when the set is created (not after motion updates): take it now
             self._global_leaf_count()
@@ -555,6 +637,61 @@ class ShardedFilter:
             p = window[0:3].view(torch.float64)
             v = self._pose_views[id(window)] = (p[0], p[1], p[2], window)  # keeps the buffer alive with its id
         return v
+
+    # ---- initWithGaussian / initWithPoseFn over the shards (particle_filter.cpp:105-163): no exchange for the poses
+    TREE_ROUTES = {1: "device", 2: "host", 3: "bins", 4: "keys"}
+
+    def init_with_gaussian(self, mean, rotation, sigma):
+        """ParticleFilter::initWithGaussian given PDFGaussian's decomposition (cr_ row-major 3x3, cd_): every rank
+        passes the same arguments and holds the same rng state; rank r ends with samples [G r / W, G (r + 1) / W) of
+        the max_samples = G samples one engine would hold."""
+        if self.mailbox and hasattr(self.b, "init_gaussian_all"):
+            return self._after_init(*self.b.init_gaussian_all(mean, rotation, sigma))
+        lo, n = self._even_share()
+        self.b.init_gaussian(mean, rotation, sigma, lo, n, self.max_global)
+        self._after_init(*self._global_tree())
+
+    def init_with_random_poses(self):
+        """ParticleFilter::initWithPoseFn with the generator of set_random_pose_generator (global localisation)."""
+        if self.mailbox and hasattr(self.b, "init_random_poses_all"):
+            return self._after_init(*self.b.init_random_poses_all())
+        lo, n = self._even_share()
+        self.b.init_random_poses(lo, n, self.max_global)
+        self._after_init(*self._global_tree())
+
+    def _even_share(self):
+        G, W, r = self.max_global, self.world, self.rank
+        self.counts = [(G * (q + 1)) // W - (G * q) // W for q in range(W)]
+        self.sample_count = G
+        return (G * r) // W, self.counts[r]
+
+    def _after_init(self, leaf, bins):
+        self._even_share()
+        self.leaf_count, self.bin_count = leaf, bins
+        self.totals = None
+        self._fused_totals = False
+        self._stats_valid = False
+        self.window_hint = self._first_window
+        self.windows_used = 0
+        if hasattr(self.b, "tree_last_route"):
+            self.tree_route = self.TREE_ROUTES.get(self.b.tree_last_route())
+
+    def _global_tree(self):
+        """Leaf and bin count of the tree of the whole set from the ranks' bin lists (self.counts describes the
+        slices); installed in the backend."""
+        b, W = self.b, self.world
+        bins, out_of_range = b.tree_local_bins(sum(self.counts[:self.rank]))
+        meta = torch.tensor([bins.shape[1], 1 if out_of_range else 0], dtype=torch.int64, device=self.device)
+        meta = self._all_gather(meta).reshape(W, 2).cpu().tolist()
+        bin_counts = [int(m[0]) for m in meta]
+        if any(int(m[1]) for m in meta):
+            # the keys route (the flag travelled with the counts: every rank turns off here together)
+            allk, _ = self._gather_ragged(b.tree_local_keys(), self.counts)
+            allk = allk.cpu()
+            keys = torch.cat([allk[r, :, :self.counts[r]] for r in range(W)], dim=1).t().contiguous().numpy()
+            return b.tree_from_keys(keys)
+        all_bins, pad = self._gather_ragged(bins, bin_counts)
+        return b.tree_merge(all_bins.contiguous(), bin_counts, pad)
 
     # ---- motion update (Odom::updateAction): no exchange
     def update_action(self, odom, data):

@@ -230,6 +230,15 @@ public:
   {
     e_->check(bpf_pf_set_samples(e_->get(), reinterpret_cast<const double*>(s.data()), (int)s.size(), leaf_count));
   }
+  // ParticleFilter::initWithGaussian given PDFGaussian's decomposition (cr_ row-major 3x3, cd_), and
+  // ParticleFilter::initWithPoseFn with the generator of setRandomFreeSpacePoseGenerator (global localisation)
+  void initWithGaussian(const std::array<double, 3>& mean, const std::array<double, 9>& rotation,
+                        const std::array<double, 3>& sigma)
+  {
+    e_->check(bpf_pf_init_with_gaussian(e_->get(), mean.data(), rotation.data(), sigma.data()));
+  }
+  void initWithRandomPoses() { e_->check(bpf_pf_init_with_random_poses(e_->get())); }
+  int maxSamples() const { return max_samples_; }
   void updateResample() { e_->check(bpf_pf_update_resample(e_->get())); }
   std::shared_ptr<PFSampleSet> getCurrentSet()
   {
@@ -397,10 +406,14 @@ private:
 class ShardedParticleFilter
 {
 public:
-  // pf: this rank's filter, its slice loaded; global_count: samples of the whole set; leaf_count: of the whole set's
-  // histogram tree (only the systematic resampler reads it before the first resample)
-  ShardedParticleFilter(std::shared_ptr<ParticleFilter> pf, int global_count, int leaf_count = 1, int first_window = 4096)
-      : pf_(std::move(pf)), global_count_(global_count), leaf_count_(leaf_count), window_hint_(first_window)
+  // pf: this rank's filter; a slice loaded by hand comes with global_count (samples of the whole set), leaf_count (of
+  // the whole set's histogram tree: only the systematic resampler reads it before the first resample) and global_first
+  // (the global index of the slice's first sample: the motion update needs it).  A set started with initWithGaussian /
+  // initWithRandomPoses needs none of the three.
+  ShardedParticleFilter(std::shared_ptr<ParticleFilter> pf, int global_count, int leaf_count = 1, int first_window = 4096,
+                        long long global_first = 0)
+      : pf_(std::move(pf)), global_count_(global_count), leaf_count_(leaf_count), window_hint_(first_window),
+        first_window_(first_window), global_first_(global_first)
   {
   }
   // host_port: "host:port" rank 0 listens on; max_window >= the filter's max_samples; flags: BPF_BOOTSTRAP_*;
@@ -412,6 +425,27 @@ public:
     rank_ = rank;
     world_ = world;
     return mode;
+  }
+  // ParticleFilter::initWithGaussian / initWithPoseFn over the shards (after bootstrap): this rank ends with its even
+  // share of the max_samples samples one engine would hold, every rank with the same rng state and with the leaf /
+  // bin counts of the whole set's histogram tree
+  void initWithGaussian(const std::array<double, 3>& mean, const std::array<double, 9>& rotation,
+                        const std::array<double, 3>& sigma)
+  {
+    e().check(bpf_shard_init_with_gaussian_all(e().get(), mean.data(), rotation.data(), sigma.data()));
+    afterInit();
+  }
+  void initWithRandomPoses()
+  {
+    e().check(bpf_shard_init_with_random_poses_all(e().get()));
+    afterInit();
+  }
+  // Odom::updateAction on this rank's slice: no exchange, every rank ends on the same rng state
+  bool updateAction(std::shared_ptr<OdomData> data)
+  {
+    e().check(bpf_shard_update_action(e().get(), data->pose.data(), data->delta.data(), data->absolute_motion.data(),
+                                      global_first_, global_count_));
+    return true;
   }
   // PlanarScanner::updateSensor over the shards (beam skipping of the prob model included)
   bool updateSensor(std::shared_ptr<PlanarData> data)
@@ -431,6 +465,7 @@ public:
   {
     e().check(bpf_shard_update_resample(e().get(), &global_count_, &leaf_count_, &bin_count_, &windows_, &window_hint_,
                                         &cdf_miss_));
+    global_first_ = evenFirst(global_count_);
   }
   // Node2D::getMaxWeightPose over the GLOBAL set, the same bits on every rank
   void getMaxWeightPose(double* max_weight_out, std::array<double, 3>* max_pose)
@@ -453,14 +488,28 @@ public:
   int windowsUsed() const { return windows_; }
   bool cdfMiss() const { return cdf_miss_ != 0; }
   int statsRoute() const { return route_; }  // BPF_SHARD_STATS_ROUTE_* of the last getClusterStats
+  int treeRoute() const { return tree_route_; }  // BPF_SHARD_TREE_ROUTE_* of the last init
+  long long globalFirst() const { return global_first_; }
   int rank() const { return rank_; }
   int world() const { return world_; }
 
 private:
   Engine& e() { return pf_->engine(); }
+  // first global index of this rank's even share of n samples: the split the resample leaves
+  long long evenFirst(long long n) const { return n * rank_ / world_; }
+  void afterInit()
+  {
+    global_count_ = pf_->maxSamples();
+    global_first_ = evenFirst(global_count_);
+    e().check(bpf_shard_global_leaf_count(e().get(), &leaf_count_, &bin_count_));  // in force: no exchange
+    e().check(bpf_shard_tree_last_route(e().get(), &tree_route_));
+    window_hint_ = first_window_;
+    windows_ = cdf_miss_ = 0;
+  }
   std::shared_ptr<ParticleFilter> pf_;
-  int global_count_, leaf_count_, window_hint_;
-  int bin_count_ = 0, windows_ = 0, cdf_miss_ = 0, route_ = 0;
+  int global_count_, leaf_count_, window_hint_, first_window_;
+  long long global_first_;
+  int bin_count_ = 0, windows_ = 0, cdf_miss_ = 0, route_ = 0, tree_route_ = 0;
   int rank_ = 0, world_ = 1;
 };
 

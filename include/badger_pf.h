@@ -578,6 +578,52 @@ int bpf_shard_stats_finish_dev(bpf_engine* e, const void* reduced_sums_dev);
  * all_samples = global_count x (x, y, theta, w) in host memory; bit for bit the BPF_OPT_STATS_HOST = 1 evaluation of
  * one engine holding the set.  Crosses between ranks: the all-gather of the slices (32 B per particle), the caller's. */
 int bpf_shard_stats_host(bpf_engine* e, const double* all_samples, int global_count);
+/* ------------------------------------------------------------------ a sharded set initialised on its ranks
+ * ParticleFilter::initWithGaussian (particle_filter.cpp:105-132) and ParticleFilter::initWithPoseFn (:135-163, the
+ * global_localization service, node.cpp:870-882) for one shard: this engine writes samples
+ * [global_first, global_first + local_count) of the set that ONE engine with max_samples = global_count and the same
+ * rng state produces with bpf_pf_init_with_gaussian / bpf_pf_init_with_random_poses -- the same bits, weight
+ * 1 / global_count -- and advances its rng by what the WHOLE set consumes, so every rank ends on the same state.
+ * w_slow / w_fast are zeroed, the converged flag cleared, the slice becomes the current set (local_count 0: an empty
+ * shard).  The set's histogram tree is NOT built: leaf_count / bin_count read -1 until bpf_shard_tree_merge_dev,
+ * bpf_shard_tree_from_keys or a resample installs those of the GLOBAL set.  global_count must be the engine's
+ * max_samples (BPF_ERR_INVALID_ARGUMENT).  The uniform pose check applies in its AS_REFERENCE form, with the capacity
+ * refusals of the single call on the GLOBAL stream use; with BPF_POSE_CHECK_SENSOR_MODEL the random-pose form returns
+ * BPF_ERR_UNSUPPORTED and touches nothing.  No exchange: every rank walks the same stream. */
+int bpf_shard_init_with_gaussian(bpf_engine* e, const double mean[3], const double rotation[9], const double sigma[3],
+                                 long long global_first, int local_count, long long global_count);
+int bpf_shard_init_with_random_poses(bpf_engine* e, long long global_first, int local_count, long long global_count);
+/* The histogram tree of the GLOBAL set (the PFKDTree initWith* builds, particle_filter.cpp:126-131,157-162, whose
+ * leaf count the systematic resampler reads first, :285) without moving a particle: the shape of the tree depends
+ * only on the order in which DISTINCT keys first appear (pf_kdtree.cpp:97-150), so the ranks exchange their bins.
+ * local_bins: *bins_dev = int64[2][*n_bins_out] in engine memory, as bpf_shard_stats_local_bins_dev lists them (packed
+ * keys, GLOBAL first indices, first-index order); *out_of_range_out = 1: a key of the slice does not fit the packing.
+ * The statistics stages are not involved.  Crosses between ranks afterwards: the counts with the flags, then the
+ * lists padded to the largest count (16 B per occupied bin).
+ * merge (redundant on every rank; the slices must be contiguous in rank order): all_bins_dev = int64[world][2][pad],
+ * rank r's list in its first counts[r] columns.  One table in which a key keeps its smallest first index, the
+ * entries that are their key's first occurrence compacted in rank-then-list order, then the tree of those keys: the
+ * device tree from 8 192 distinct keys on, the host tree below that or when the device tree declines; with
+ * BPF_KLD_COUNT_BINS no tree, the leaf count is the bin count.  Installs leaf_count / bin_count where
+ * bpf_shard_adopt_dev does.  Statistics stages in progress on this engine start over.  Waits for the stream.
+ * If ANY rank raised out_of_range every rank takes the keys route instead: local_keys (*keys_dev = int32[*n_keys_out][3]
+ * of the slice, in engine memory), an all-gather of those, and from_keys on the host copy of all of them in index
+ * order -- correct and slow.  last_route: how the counts in force were found (0: none since the last init). */
+enum
+{
+  BPF_SHARD_TREE_ROUTE_DEVICE = 1,    /* merged bins, device tree */
+  BPF_SHARD_TREE_ROUTE_HOST = 2,      /* merged bins, host tree of the distinct keys */
+  BPF_SHARD_TREE_ROUTE_BIN_COUNT = 3, /* merged bins, BPF_KLD_COUNT_BINS: no tree */
+  BPF_SHARD_TREE_ROUTE_KEYS = 4       /* every raw key through the host tree */
+};
+int bpf_shard_tree_local_bins_dev(bpf_engine* e, long long global_first, void** bins_dev, int* n_bins_out,
+                                  int* out_of_range_out);
+int bpf_shard_tree_merge_dev(bpf_engine* e, const void* all_bins_dev, const int* counts, int world, int pad,
+                             int* leaf_count_out, int* bin_count_out);
+int bpf_shard_tree_local_keys_dev(bpf_engine* e, void** keys_dev, int* n_keys_out);
+int bpf_shard_tree_from_keys(bpf_engine* e, const int* all_keys, int global_count, int* leaf_count_out,
+                             int* bin_count_out);
+int bpf_shard_tree_last_route(bpf_engine* e, int* route_out);
 /* Advance a drand48 state by n draws (host arithmetic; the LCG jump the kernels use). */
 uint64_t bpf_drand48_skip(uint64_t state48, uint64_t n);
 /* Host-side exact KLD stop rule: replay ordered histogram keys through the fork's kd-tree
@@ -729,6 +775,21 @@ int bpf_shard_compute_cluster_stats(bpf_engine* e, int* cluster_count_out, doubl
                                     int* route_out);
 /* Node2D::getMaxWeightPose over the global set (the same evaluation, the same laziness) */
 int bpf_shard_get_max_weight_pose(bpf_engine* e, double* max_weight, double pose[3]);
+/* The sharded inits as one collective call each (every rank, same arguments, same rng state): this rank takes its
+ * even share [G r / W, G (r + 1) / W) of G = max_samples (the split the resample re-split uses, rank / world of
+ * bpf_shard_bootstrap or bpf_shard_mailbox_connect), runs the stage form above and then the global tree over the
+ * engine's own exchange: one gather of the bin counts with the out-of-range flags, one of the ragged bin lists (2
+ * words per bin through the window region), the merge; or, when any rank raised the flag, the slices and the keys
+ * route.  Afterwards every rank holds its slice, the common rng state and the leaf / bin counts of the global set.
+ * BPF_ERR_EXCHANGE after a failed exchange: rng, set and counts are as before the call. */
+int bpf_shard_init_with_gaussian_all(bpf_engine* e, const double mean[3], const double rotation[9],
+                                     const double sigma[3]);
+int bpf_shard_init_with_random_poses_all(bpf_engine* e);
+/* Leaf and bin count of the GLOBAL set's tree for slices loaded by hand (bpf_pf_set_samples on every rank, call this
+ * before the first motion update): the local sample counts, then the exchanges above.  While counts of the global
+ * set are in force (after one of the inits above, this call or a sharded resample) it returns them without an
+ * exchange. */
+int bpf_shard_global_leaf_count(bpf_engine* e, int* leaf_count_out, int* bin_count_out);
 /* Diagnostic: exchanges this engine has issued since bpf_shard_bootstrap (or bpf_shard_mailbox_connect) set the
  * exchange up -- totals, draw windows, gathers and reduce rounds together. */
 int bpf_shard_exchange_count(bpf_engine* e, long long* out);
