@@ -31,10 +31,7 @@ int bpf_pf_create(bpf_engine* e, int min_samples, int max_samples, double alpha_
                      1.0 / max_samples, max_samples);
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipMemsetAsync(e->d_scalars.p, 0, sizeof(FilterScalars), e->stream));
-  e->leaf_count = 0;
-  e->bin_count = 0;
-  e->converged = 0;
-  e->converged_pending = false;
+  e->filter_created();
   e->window_hint = 4096;
   e->have_pf = true;
   return BPF_OK;
@@ -92,7 +89,7 @@ int bpf_pf_get_rng_state(const bpf_engine* e, uint64_t* state48)
 
 namespace
 {
-int finish_init(bpf_engine* e, int n);  // abi_motion.inl
+int finish_init(bpf_engine* e, int n, bool spread);  // abi_motion.inl
 int ensure_set_tree(bpf_engine* e);     // abi_motion.inl
 }
 
@@ -109,30 +106,12 @@ int bpf_pf_set_samples(bpf_engine* e, const double* samples, int sample_count, i
   int rc = upload_samples(e, samples, sample_count, e->sets[e->cur]);
   if (rc != BPF_OK)
     return rc;
-  e->sample_count = sample_count;
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
-  e->set_epoch++;
-  e->hist_matches_set = leaf_count < 0;
-  // initWith*: w_slow_ = w_fast_ = 0, converged = false (particle_filter.cpp:127,157,164-168)
-  HIPCHK(e, hipMemsetAsync(e->d_scalars.p, 0, sizeof(FilterScalars), e->stream));
-  e->converged = 0;
-  e->converged_pending = false;
-  e->fused_partials = 0;
-  e->tree_pending = false;
-  e->spread_init = false;
-  if (leaf_count >= 0)
-  {
-    e->leaf_count = leaf_count;
-    e->bin_count = -1;
-  }
-  else
-  {
-    // the set's histogram tree, as the reference builds it when a set is created (on the device for large sets, as
-    // after initWithGaussian / initWithPoseFn), is built when it is first needed: ensure_set_tree
-    e->hist_matches_set = false;
-    e->leaf_count = e->bin_count = -1;
-    e->tree_pending = true;
-  }
+  // without a leaf count the set's histogram tree, as the reference builds it when a set is created (on the device
+  // for large sets, as after initWithGaussian / initWithPoseFn), is built when it is first needed: ensure_set_tree
+  rc = e->fresh_filter(sample_count, false, leaf_count >= 0 ? e->tree.counted(leaf_count, -1) : e->tree.pending(),
+                       false);
+  if (rc != BPF_OK)
+    return rc;
   HIPCHK(e, hipStreamSynchronize(e->stream));  // the caller's buffer is only the call's
   return BPF_OK;
 }
@@ -187,8 +166,8 @@ int bpf_pf_snapshot(bpf_engine* e)
   HIPCHK(e, hipMemcpyAsync(e->snap.th.p, s.th.p, n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
   HIPCHK(e, hipMemcpyAsync(e->snap.w.p, s.w.p, n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
   e->snap_count = e->sample_count;
-  e->snap_leaf = e->leaf_count;
-  e->snap_bins = e->bin_count;
+  e->snap_leaf = e->tree.leaf_count;
+  e->snap_bins = e->tree.bin_count;
   return BPF_OK;
 }
 
@@ -201,13 +180,7 @@ int bpf_pf_restore(bpf_engine* e)
   hipLaunchKernelGGL(k_copy4, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, e->sets[e->cur].dev(),
                      e->snap.dev(), n);
   HIPCHK(e, hipGetLastError());
-  e->sample_count = e->snap_count;
-  e->tree_pending = false;
-  e->leaf_count = e->snap_leaf;
-  e->bin_count = e->snap_bins;
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
-  e->set_epoch++;
-  e->hist_matches_set = false;
+  e->new_set(n, false, e->tree.counted(e->snap_leaf, e->snap_bins));
   return BPF_OK;
 }
 
@@ -215,8 +188,8 @@ int bpf_pf_fill_weights(bpf_engine* e, double weight)
 {
   if (!e || !e->have_pf)
     return BPF_ERR_INVALID_ARGUMENT;
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
-  e->set_epoch++;
+  e->weights_overwritten();
+  e->weights_changed();
   HIPCHK(e, hipSetDevice(e->device));
   hipLaunchKernelGGL(k_fill, dim3(blocks_for(e->sample_count, 256)), dim3(256), 0, e->stream,
                      e->sets[e->cur].w.p, weight, e->sample_count);
@@ -254,7 +227,7 @@ int bpf_pf_update_sensor_planar(bpf_engine* e, const double* ranges, const doubl
   int rc = score_planar(e, s.dev(), n, e->converged, ranges, angles, range_count, range_max, &forced_zero, true);
   if (rc != BPF_OK)
     return rc;
-  if (e->fused_partials > 0)
+  if (e->wc.fused_partials > 0)
   {
     // the scoring kernel left per-block weight partials: one launch folds them, normalises, updates the
     // running averages and leaves the tile sums for the CDF
@@ -271,12 +244,12 @@ int bpf_pf_update_sensor_planar(bpf_engine* e, const double* ranges, const doubl
     {
       ProfScope ps(e, BPF_K_NORMALIZE);
       hipLaunchKernelGGL(k_normalize_fused, dim3(nb), dim3(BPF_RED_BLOCK), 0, e->stream, s.w.p, n,
-                         e->d_block_partials.p, e->fused_partials, e->d_scalars.p, e->alpha_slow, e->alpha_fast,
+                         e->d_block_partials.p, e->wc.fused_partials, e->d_scalars.p, e->alpha_slow, e->alpha_fast,
                          e->d_tile_sums.p);
       HIPCHK(e, hipGetLastError());
-      e->tile_sums_n = n;
+      e->wc.tile_sums_left(n);
     }
-    e->fused_partials = 0;
+    e->wc.fused_partials = 0;
   }
   else
   {
@@ -289,7 +262,7 @@ int bpf_pf_update_sensor_planar(bpf_engine* e, const double* ranges, const doubl
     HIPCHK(e, hipGetLastError());
   }
   e->last_status = BPF_OK;
-  e->set_epoch++;
+  e->weights_changed();
   return BPF_OK;
 }
 
@@ -345,11 +318,7 @@ int bpf_pf_set_kld_count(bpf_engine* e, int mode)
     return BPF_OK;
   e->kld_count_mode = mode;
   if (e->have_pf && e->sample_count > 0)
-  {
-    // the current set's count was taken in the other mode: computed again when it is needed (bpf_pf_set_samples, -1)
-    e->leaf_count = e->bin_count = -1;
-    e->tree_pending = true;
-  }
+    e->tree_invalidated();  // as after bpf_pf_set_samples with leaf_count -1
   return BPF_OK;
 }
 
@@ -391,8 +360,7 @@ int bpf_pf_update_resample(bpf_engine* e)
     if (rc != BPF_OK)
       return rc;
   }
-  e->tree_pending = false;  // the multinomial resampler builds the new set's tree from its draws
-  e->spread_init = false;   // from here on the resample's own outcome says whether the cloud is spread
+  e->resample_begins();
   rc = build_cdf(e, a.w.p, e->sample_count);
   if (rc != BPF_OK)
     return rc;
@@ -405,32 +373,23 @@ int bpf_pf_update_resample(bpf_engine* e)
     HIPCHK(e, hipMemsetAsync(&e->d_scalars.p->v[1], 0, 2 * sizeof(double), e->stream));
   const int M = e->sample_count;
   SampleSet& b = e->sets[e->cur ^ 1];
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
-  e->cur ^= 1;
-  if (kld_bins(e))
-    e->leaf_count = e->bin_count = e->kld_device_used ? e->kld_bins : e->kld_host_bins;
-  else
-  {
-    e->leaf_count = e->kld_device_used ? e->kld_leaf : e->hist.leaf_count();
-    e->bin_count = e->kld_device_used ? e->kld_bins : e->hist.bin_count();
-  }
-  if (e->fused_used)
-  {
-    // k_resample_block already wrote the weights and counted the converged particles
-    e->converged_pending = true;
-    e->conv_n = M;
-  }
-  else if (M <= 8192)
+  const int bins = e->kld_device_used ? e->kld_bins : (kld_bins(e) ? e->kld_host_bins : e->hist.bin_count());
+  const int leaf = kld_bins(e) ? bins : (e->kld_device_used ? e->kld_leaf : e->hist.leaf_count());
+  // k_resample_block already wrote the weights and counted the converged particles, the single-block tail below
+  // does; a larger set gets launch_converged
+  e->new_set(M, true, e->tree.counted(leaf, bins), (e->fused_used || M <= 8192) ? M : 0);
+  // the device tree leaves no host histogram behind, nor does the host replay in BINS mode
+  if (!e->kld_device_used && !kld_bins(e))
+    e->hist_built();
+  if (!e->fused_used && M <= 8192)
   {
     // small resampled set: weights 1/M and updateConverged in one single-block launch
     ProfScope ps(e, BPF_K_FINALIZE);
     hipLaunchKernelGGL(k_resample_tail_small, dim3(1), dim3(1024), 0, e->stream, b.x.p, b.y.p, b.w.p, M,
                        e->dist_threshold, e->d_scalars.p, e->d_flags.p + 1);
     HIPCHK(e, hipGetLastError());
-    e->converged_pending = true;
-    e->conv_n = M;
   }
-  else
+  else if (!e->fused_used)
   {
     {
       ProfScope ps(e, BPF_K_FINALIZE);
@@ -444,9 +403,6 @@ int bpf_pf_update_resample(bpf_engine* e)
   }
   // miss flag was copied? read it with the next fetch; report asynchronously via last_status
   e->last_status = BPF_OK;
-  e->set_epoch++;
-  // the device tree leaves no host histogram behind, nor does the host replay in BINS mode
-  e->hist_matches_set = !e->kld_device_used && !kld_bins(e);
   return BPF_OK;
 }
 
@@ -467,8 +423,8 @@ int bpf_pf_get_state(bpf_engine* e, bpf_pf_state* out)
     e->last_status = BPF_ERR_CDF_MISS;
   std::memset(out, 0, sizeof(*out));
   out->sample_count = e->sample_count;
-  out->leaf_count = e->leaf_count;
-  out->bin_count = e->bin_count;
+  out->leaf_count = e->tree.leaf_count;
+  out->bin_count = e->tree.bin_count;
   out->converged = e->converged;
   out->percent_converged = e->percent_converged;
   out->total = e->h_scalars.p->v[0];

@@ -455,7 +455,7 @@ int bpf_shard_mailbox_update_resample(bpf_engine* e, void* flags_dev, int* globa
         int lim = 0;
         bpf_pf_resample_limit(e, lc, &lim);
         need = lim - m0;
-        win = std::max(1024, (need + need / 4 + 1023) / 1024 * 1024);
+        win = resample_window_for(need);
       }
     }
     if (!adopted)
@@ -470,7 +470,7 @@ int bpf_shard_mailbox_update_resample(bpf_engine* e, void* flags_dev, int* globa
       if (rc != BPF_OK)
         return rc;
     }
-    *window_hint_io = std::max(1024, ((M + M / 4) + 1023) / 1024 * 1024);
+    *window_hint_io = resample_window_for(M);
   }
   uint64_t rng_after = 0;
   rc = bpf_shard_end_resample(e, M, &rng_after);

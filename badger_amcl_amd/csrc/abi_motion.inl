@@ -149,11 +149,7 @@ int update_action(bpf_engine* e, const double pose[3], const double delta[3], co
   if (rc != BPF_OK)
     return rc;
   e->rng = lcg_skip_host(e->rng, (uint64_t)consumed, e->jump);
-  e->cur ^= 1;
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
-  e->fused_partials = 0;
-  e->set_epoch++;
-  e->hist_matches_set = false;
+  e->new_set(n, true, e->tree);  // (the tree stays the one of the poses the set was created with)
   return BPF_OK;
 }
 
@@ -166,24 +162,18 @@ int build_set_tree(bpf_engine* e, int n);
 // set's tree from its draws.
 int ensure_set_tree(bpf_engine* e)
 {
-  if (!e->tree_pending)
+  if (!e->tree.tree_pending)
     return BPF_OK;
   return build_set_tree(e, e->sample_count);
 }
 
 // what initWithGaussian / initWithPoseFn leave besides the poses (particle_filter.cpp:126-131,157-162): the
 // histogram tree of the set (leaf / bin counts), w_slow = w_fast = 0, converged = false
-int finish_init(bpf_engine* e, int n)
+int finish_init(bpf_engine* e, int n, bool spread)
 {
-  SampleSet& s = e->sets[e->cur];
-  e->sample_count = n;
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
-  e->fused_partials = 0;
-  e->set_epoch++;
-  e->hist_matches_set = false;
-  HIPCHK(e, hipMemsetAsync(e->d_scalars.p, 0, sizeof(FilterScalars), e->stream));
-  e->converged = 0;
-  e->converged_pending = false;
+  const int rc = e->fresh_filter(n, false, e->tree, spread);  // (build_set_tree replaces the counts)
+  if (rc != BPF_OK)
+    return rc;
   return build_set_tree(e, n);
 }
 
@@ -191,7 +181,6 @@ int finish_init(bpf_engine* e, int n)
 int build_set_tree(bpf_engine* e, int n)
 {
   SampleSet& s = e->sets[e->cur];
-  e->tree_pending = false;
   HIPCHK(e, e->d_keys.reserve((size_t)n * 3));
   hipLaunchKernelGGL(k_set_keys, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, s.dev(), n, e->d_keys.p);
   HIPCHK(e, hipGetLastError());
@@ -212,12 +201,9 @@ int build_set_tree(bpf_engine* e, int n)
       e->hist.insert(keys[3 * (size_t)i], keys[3 * (size_t)i + 1], keys[3 * (size_t)i + 2]);
     leaf = e->hist.leaf_count();
     bins = e->hist.bin_count();
-    e->hist_matches_set = true;
+    e->hist_built();
   }
-  if (kld_bins(e))
-    leaf = bins;
-  e->leaf_count = leaf;
-  e->bin_count = bins;
+  e->tree_counted(kld_bins(e) ? bins : leaf, bins);
   return BPF_OK;
 }
 }  // namespace
@@ -260,8 +246,7 @@ int bpf_pf_init_with_gaussian(bpf_engine* e, const double mean[3], const double 
   if (rc != BPF_OK)
     return rc;
   e->rng = lcg_skip_host(e->rng, (uint64_t)consumed, e->jump);
-  e->spread_init = false;
-  return finish_init(e, n);
+  return finish_init(e, n, false);
 }
 
 int bpf_pf_init_with_random_poses(bpf_engine* e)
@@ -294,8 +279,7 @@ int bpf_pf_init_with_random_poses(bpf_engine* e)
                      e->rng, e->jump, fs, 1.0 / (double)n);
   HIPCHK(e, hipGetLastError());
   e->rng = lcg_skip_host(e->rng, consumed, e->jump);
-  e->spread_init = true;  // uniform over the free space: scored in tile order until a resample says otherwise
-  return finish_init(e, n);
+  return finish_init(e, n, true);  // uniform over the free space: scored in tile order until a resample says otherwise
 }
 
 int bpf_pf_update_action(bpf_engine* e, const double pose[3], const double delta[3], const double absolute_motion[3])

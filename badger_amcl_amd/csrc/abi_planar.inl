@@ -157,8 +157,7 @@ int apply_model_records(bpf_engine* e, double* samples, int n, int set_converged
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
   };
   const double t0 = dbg ? now() : 0.0;
-  e->fused_partials = 0;
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
+  e->weights_overwritten();
   ScanSlot* s = nullptr;
   FieldScan fs;
   rcode = stage_field_scan(e, ranges, angles, rc, range_max, &s, &fs);
@@ -226,8 +225,7 @@ int apply_model_pipelined(bpf_engine* e, double* samples, int n, int set_converg
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
   };
   const double t0 = dbg ? now() : 0.0;
-  e->fused_partials = 0;
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
+  e->weights_overwritten();
   HIPCHK(e, e->d_aos.reserve((size_t)n));
   HIPCHK(e, e->scratch.reserve((size_t)n));
   // the weights come back through a FINE-grained pinned array: the scoring launches' stores are written through, so

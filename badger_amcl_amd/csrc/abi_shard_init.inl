@@ -65,22 +65,9 @@ int shard_init_random_write(bpf_engine* e, long long first, int n, long long glo
 int shard_init_commit(bpf_engine* e, int n, uint64_t rng_after, bool spread)
 {
   e->rng = rng_after;
-  e->cur ^= 1;
-  e->sample_count = n;
-  e->spread_init = spread;
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
-  e->shard_cdf_valid = false;
+  e->wc.shard_cdf_dropped();
   e->mb_totals_valid = false;
-  e->fused_partials = 0;
-  e->set_epoch++;
-  e->hist_matches_set = false;
-  HIPCHK(e, hipMemsetAsync(e->d_scalars.p, 0, sizeof(FilterScalars), e->stream));
-  e->converged = 0;
-  e->converged_pending = false;
-  e->tree_pending = false;
-  e->leaf_count = e->bin_count = -1;
-  e->gt_route = 0;
-  return BPF_OK;
+  return e->fresh_filter(n, true, TreeCounts{ -1, -1, 0, false }, spread);
 }
 
 int gtree_flags(bpf_engine* e)
@@ -157,11 +144,7 @@ int tree_local_bins(bpf_engine* e, SampleSet& s, int n, long long global_first, 
 // leaf / bin counts of the global set where bpf_shard_adopt_dev installs them
 void tree_install(bpf_engine* e, int leaf, int bins, int route)
 {
-  e->tree_pending = false;
-  e->leaf_count = kld_bins(e) ? bins : leaf;
-  e->bin_count = bins;
-  e->hist_matches_set = false;  // e->hist, where it was used, holds every distinct key ONCE: not the set's histogram
-  e->gt_route = route;
+  e->tree_installed(kld_bins(e) ? bins : leaf, bins, route);
 }
 
 // the merge stage and the tree on the merged keys
@@ -248,8 +231,8 @@ int tree_merge(bpf_engine* e, const long long* all, const int* counts, int world
     }
   }
   tree_install(e, leaf, n_distinct, route);
-  *leaf_out = e->leaf_count;
-  *bins_out = e->bin_count;
+  *leaf_out = e->tree.leaf_count;
+  *bins_out = e->tree.bin_count;
   return BPF_OK;
 }
 
@@ -260,8 +243,8 @@ int tree_from_keys(bpf_engine* e, const int* keys, int n, int* leaf_out, int* bi
   for (int i = 0; i < n; ++i)
     kld_host_insert(e, keys[3 * (size_t)i], keys[3 * (size_t)i + 1], keys[3 * (size_t)i + 2]);
   tree_install(e, kld_host_k(e), kld_bins(e) ? e->kld_host_bins : e->hist.bin_count(), BPF_SHARD_TREE_ROUTE_KEYS);
-  *leaf_out = e->leaf_count;
-  *bins_out = e->bin_count;
+  *leaf_out = e->tree.leaf_count;
+  *bins_out = e->tree.bin_count;
   return BPF_OK;
 }
 }  // namespace
@@ -356,6 +339,6 @@ int bpf_shard_tree_last_route(bpf_engine* e, int* route_out)
 {
   if (!e || !route_out)
     return BPF_ERR_INVALID_ARGUMENT;
-  *route_out = e->gt_route;
+  *route_out = e->tree.gt_route;
   return BPF_OK;
 }

@@ -54,6 +54,45 @@ int shard_gather_slices(bpf_engine* e, ShardExchange& X, const long long* counts
   return X.gather(src, 4, counts, e->d_x_gather.p, offs, n);
 }
 
+// The ranks' bin lists of a merge stage (statistics labels, the global tree).  Every rank's (n_bins, flag) pair crosses
+// first and the counts are checked against the slices (counts[]); *any_flag: some rank raised its flag -- it
+// travelled with the counts, so every rank turns off to its caller's other route here together, and no list crosses.
+// Otherwise the lists (`bins`: this rank's int64[2][n_bins]) cross, as their readers take them:
+// d_x_gather = int64[world][2][*pad_out], zero-filled.
+int shard_exchange_bin_lists(bpf_engine* e, ShardExchange& X, const long long* bins, int n_bins, int flag,
+                             const long long* counts, const char* bad_count, int* bin_counts_i, int* pad_out,
+                             bool* any_flag)
+{
+  const int W = e->shard_world;
+  const long long meta[2] = { n_bins, flag };
+  long long metas[2 * kMailboxMaxWorld] = { 0 };
+  int rc = shard_gather_host_words(e, X, meta, 2, metas);
+  if (rc != BPF_OK)
+    return rc;
+  long long bin_counts[kMailboxMaxWorld], offs[kMailboxMaxWorld], pad = 1;
+  *any_flag = false;
+  for (int r = 0; r < W; ++r)
+  {
+    bin_counts[r] = metas[2 * r];
+    if (bin_counts[r] < 0 || bin_counts[r] > counts[r])
+      return e->fail(BPF_ERR_EXCHANGE, bad_count);
+    bin_counts_i[r] = (int)bin_counts[r];
+    pad = std::max(pad, bin_counts[r]);
+    *any_flag = *any_flag || metas[2 * r + 1] != 0;
+  }
+  *pad_out = (int)pad;
+  if (*any_flag)
+    return BPF_OK;
+  const size_t flat = (size_t)W * 2 * (size_t)pad;
+  HIPCHK(e, e->d_x_gather.reserve(flat));
+  HIPCHK(e, hipMemsetAsync(e->d_x_gather.p, 0, flat * sizeof(long long), e->stream));
+  const long long* src[2] = { bins, bins + n_bins };
+  for (int r = 0; r < W; ++r)
+    offs[r] = (long long)r * 2 * pad;
+  rc = X.gather(src, 2, bin_counts, e->d_x_gather.p, offs, pad);
+  return rc == BPF_OK ? X.finish() : rc;
+}
+
 // ShardedFilter._ensure_stats
 int shard_ensure_stats(bpf_engine* e)
 {
@@ -110,42 +149,19 @@ int shard_ensure_stats(bpf_engine* e)
     rc = bpf_shard_stats_local_bins_dev(e, first, &bins, &n_bins, &host_route);
     if (rc != BPF_OK)
       return rc;
-    const long long meta[2] = { n_bins, host_route };
-    long long metas[2 * kMailboxMaxWorld] = { 0 };
-    rc = shard_gather_host_words(e, X, meta, 2, metas);
+    int bin_counts_i[kMailboxMaxWorld], pad = 1;
+    bool any_host = false;
+    rc = shard_exchange_bin_lists(e, X, static_cast<const long long*>(bins), n_bins, host_route, counts,
+                                  "sharded statistics: a bin count outside its slice arrived", bin_counts_i, &pad,
+                                  &any_host);
     if (rc != BPF_OK)
       return rc;
-    long long bin_counts[kMailboxMaxWorld], pad = 1;
-    int bin_counts_i[kMailboxMaxWorld];
-    bool any_host = false;
-    for (int r = 0; r < W; ++r)
-    {
-      bin_counts[r] = metas[2 * r];
-      if (bin_counts[r] < 0 || bin_counts[r] > counts[r])
-        return e->fail(BPF_ERR_EXCHANGE, "sharded statistics: a bin count outside its slice arrived");
-      bin_counts_i[r] = (int)bin_counts[r];
-      pad = std::max(pad, bin_counts[r]);
-      any_host = any_host || metas[2 * r + 1] != 0;
-    }
     if (any_host)
-      route = BPF_SHARD_STATS_ROUTE_HOST;  // the flag travelled with the counts: every rank turns off here together
+      route = BPF_SHARD_STATS_ROUTE_HOST;
     else
     {
-      // the lists as bpf_shard_stats_label_dev reads them: int64[world][2][pad]
-      const size_t flat = (size_t)W * 2 * (size_t)pad;
-      HIPCHK(e, e->d_x_gather.reserve(flat));
-      HIPCHK(e, hipMemsetAsync(e->d_x_gather.p, 0, flat * sizeof(long long), e->stream));
-      const long long* src[2] = { static_cast<const long long*>(bins), static_cast<const long long*>(bins) + n_bins };
-      long long offs[kMailboxMaxWorld];
-      for (int r = 0; r < W; ++r)
-        offs[r] = (long long)r * 2 * pad;
-      rc = X.gather(src, 2, bin_counts, e->d_x_gather.p, offs, pad);
-      if (rc == BPF_OK)
-        rc = X.finish();
-      if (rc != BPF_OK)
-        return rc;
       int clusters = 0;
-      rc = bpf_shard_stats_label_dev(e, e->d_x_gather.p, bin_counts_i, W, (int)pad, &clusters);
+      rc = bpf_shard_stats_label_dev(e, e->d_x_gather.p, bin_counts_i, W, pad, &clusters);
       if (rc != BPF_OK)
         return rc;
       void* sums = nullptr;
@@ -239,28 +255,18 @@ int shard_global_tree(bpf_engine* e, ShardExchange& X, SampleSet& s, int n, long
   int rc = tree_local_bins(e, s, n, first, &n_bins, &out_of_range);
   if (rc != BPF_OK)
     return rc;
-  const long long meta[2] = { n_bins, out_of_range };
-  long long metas[2 * kMailboxMaxWorld] = { 0 };
-  rc = shard_gather_host_words(e, X, meta, 2, metas);
+  int bin_counts_i[kMailboxMaxWorld], pad = 1;
+  bool any_out = false;
+  rc = shard_exchange_bin_lists(e, X, e->d_gt_bins.p, n_bins, out_of_range, counts,
+                                "global tree: a bin count outside its slice arrived", bin_counts_i, &pad, &any_out);
   if (rc != BPF_OK)
     return rc;
-  long long bin_counts[kMailboxMaxWorld], pad = 1, total = 0;
-  int bin_counts_i[kMailboxMaxWorld];
-  bool any_out = false;
-  for (int r = 0; r < W; ++r)
-  {
-    bin_counts[r] = metas[2 * r];
-    if (bin_counts[r] < 0 || bin_counts[r] > counts[r])
-      return e->fail(BPF_ERR_EXCHANGE, "global tree: a bin count outside its slice arrived");
-    bin_counts_i[r] = (int)bin_counts[r];
-    pad = std::max(pad, bin_counts[r]);
-    any_out = any_out || metas[2 * r + 1] != 0;
-    total += counts[r];
-  }
   if (any_out)
   {
-    // the keys route (the flag travelled with the counts: every rank turns off here together): the slices cross,
-    // every pose's key goes through the host tree in index order
+    // the keys route: the slices cross, every pose's key goes through the host tree in index order
+    long long total = 0;
+    for (int r = 0; r < W; ++r)
+      total += counts[r];
     const int N = (int)total;
     rc = shard_gather_slices(e, X, counts, N, &s);
     if (rc != BPF_OK)
@@ -275,19 +281,7 @@ int shard_global_tree(bpf_engine* e, ShardExchange& X, SampleSet& s, int n, long
       host_pose_key(soa[i], soa[(size_t)N + i], soa[2 * (size_t)N + i], &keys[3 * (size_t)i]);
     return tree_from_keys(e, keys.data(), N, leaf_out, bins_out);
   }
-  const size_t flat = (size_t)W * 2 * (size_t)pad;
-  HIPCHK(e, e->d_x_gather.reserve(flat));
-  HIPCHK(e, hipMemsetAsync(e->d_x_gather.p, 0, flat * sizeof(long long), e->stream));
-  const long long* src[2] = { e->d_gt_bins.p, e->d_gt_bins.p + n_bins };
-  long long offs[kMailboxMaxWorld];
-  for (int r = 0; r < W; ++r)
-    offs[r] = (long long)r * 2 * pad;
-  rc = X.gather(src, 2, bin_counts, e->d_x_gather.p, offs, pad);
-  if (rc == BPF_OK)
-    rc = X.finish();
-  if (rc != BPF_OK)
-    return rc;
-  return tree_merge(e, e->d_x_gather.p, bin_counts_i, W, (int)pad, leaf_out, bins_out);
+  return tree_merge(e, e->d_x_gather.p, bin_counts_i, W, pad, leaf_out, bins_out);
 }
 
 // write this rank's even share into the spare set, find the global tree, and only then make the set current
@@ -311,16 +305,12 @@ int shard_init_all(bpf_engine* e, bool spread, const std::function<int(long long
   rc = write(first, n, G, &rng_after);
   if (rc != BPF_OK)
     return rc;
-  const int leaf_before = e->leaf_count, bins_before = e->bin_count, route_before = e->gt_route;
-  const bool pending_before = e->tree_pending;
+  const TreeCounts before = e->tree;
   int leaf = 0, bins = 0;
   rc = shard_global_tree(e, X, e->sets[e->cur ^ 1], n, first, counts, &leaf, &bins);
-  const int route = e->gt_route;
+  const int route = e->tree.gt_route;
   // (the counts describe the set that is not current yet)
-  e->leaf_count = leaf_before;
-  e->bin_count = bins_before;
-  e->gt_route = route_before;
-  e->tree_pending = pending_before;
+  e->tree = before;
   if (rc != BPF_OK)
     return rc;
   rc = shard_init_commit(e, n, rng_after, spread);
@@ -359,10 +349,11 @@ int bpf_shard_global_leaf_count(bpf_engine* e, int* leaf_count_out, int* bin_cou
   int rc = shard_step_ready(e);
   if (rc != BPF_OK)
     return rc;
-  if (!e->tree_pending && e->leaf_count > 0)
+  if (!e->tree.tree_pending && e->tree.leaf_count > 0)
   {
-    *leaf_count_out = e->leaf_count;  // of the global set (an init, this call or a resample installed it): no exchange
-    *bin_count_out = e->bin_count;
+    // of the global set (an init, this call or a resample installed it): no exchange
+    *leaf_count_out = e->tree.leaf_count;
+    *bin_count_out = e->tree.bin_count;
     return BPF_OK;
   }
   HIPCHK(e, hipSetDevice(e->device));

@@ -19,7 +19,7 @@ int shard_sum_and_post(bpf_engine* e, const double* w, int n)
 int shard_local_total(bpf_engine* e)
 {
   SampleSet& s = e->sets[e->cur];
-  if (e->fused_partials > 0)
+  if (e->wc.fused_partials > 0)
   {
     // the scoring kernel left per-block partials: one small launch folds them into the local total
     if (e->mb.active)
@@ -27,16 +27,16 @@ int shard_local_total(bpf_engine* e)
       // mailbox: the fold and the post to the peers ride on the normalise launch that has to follow anyway
       // (bpf_shard_normalize_dev with bpf_shard_mailbox_totals); one launch less on the critical path
       ++e->mb.tot_gen;
-      e->mb.fold_deferred = e->fused_partials;
-      e->fused_partials = 0;
+      e->mb.fold_deferred = e->wc.fused_partials;
+      e->wc.fused_partials = 0;
       return BPF_OK;
     }
     const unsigned long long gen = 0;
     ProfScope ps(e, BPF_K_REDUCE);
     hipLaunchKernelGGL(k_fold_partials, dim3(1), dim3(BPF_RED_BLOCK), 0, e->stream, e->d_block_partials.p,
-                       e->fused_partials, e->d_scalars.p, 0, mailbox_dev(e), (int)(gen & 1), gen);
+                       e->wc.fused_partials, e->d_scalars.p, 0, mailbox_dev(e), (int)(gen & 1), gen);
     HIPCHK(e, hipGetLastError());
-    e->fused_partials = 0;
+    e->wc.fused_partials = 0;
     return BPF_OK;
   }
   return shard_sum_and_post(e, s.w.p, e->sample_count);
@@ -60,7 +60,7 @@ int bpf_shard_score_planar(bpf_engine* e, const double* ranges, const double* an
                         &forced_zero, true, true);
   if (rc != BPF_OK)
     return rc;
-  e->set_epoch++;  // the weights change (or are about to): cached statistics no longer describe the slice
+  e->weights_changed();  // (or are about to, when the second pass of beam skipping is still to come)
   if (e->skip_pending)
     return BPF_SHARD_NEED_BEAM_COUNTS;  // sum bpf_shard_beam_counts_dev over the shards, then ..._finish
   return shard_local_total(e);
@@ -91,7 +91,7 @@ int bpf_shard_score_planar_finish(bpf_engine* e, const double* ranges, const dou
                                         range_max, &forced_zero, true);
   if (rc != BPF_OK)
     return rc;
-  e->set_epoch++;
+  e->weights_changed();
   return shard_local_total(e);
 }
 
@@ -105,11 +105,11 @@ int bpf_shard_score_cloud(bpf_engine* e, const float* points_xyz, int n_points)
     return BPF_OK;
   HIPCHK(e, hipSetDevice(e->device));
   SampleSet& s = e->sets[e->cur];
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
+  e->weights_overwritten();
   int rc = score_cloud(e, s.dev(), e->sample_count, points_xyz, n_points);
   if (rc != BPF_OK)
     return rc;
-  e->set_epoch++;
+  e->weights_changed();
   return shard_sum_and_post(e, s.w.p, e->sample_count);
 }
 
@@ -134,7 +134,7 @@ int bpf_shard_normalize_dev(bpf_engine* e, const void* totals_dev, int world, in
   const int n = e->sample_count;
   const int nb = std::max(1, blocks_for(n, BPF_RED_TILE));
   HIPCHK(e, e->d_tile_sums.reserve((size_t)nb));
-  e->set_epoch++;  // the weights are rescaled
+  e->weights_changed();  // rescaled
   // totals that are this engine's mailbox slots: the kernel itself waits for the peers' posts of this update
   MailboxDev wait{};
   const double* fold = nullptr;
@@ -214,22 +214,18 @@ int bpf_shard_normalize_dev(bpf_engine* e, const void* totals_dev, int world, in
     G.sum_out = &e->d_scalars.p->v[7];
     hipLaunchKernelGGL(k_normalize_gathered_cdf, dim3(nb), dim3(BPF_RED_BLOCK), 0, e->stream, G);
     HIPCHK(e, hipGetLastError());
-    e->tile_sums_n = -1;
-    e->cdf_ready_n = n;
-    e->cdf_coarse_n = n;
-    e->cdf_guide_valid = false;
+    e->wc.cdf_left(n, false, true);
     e->shard_cdf_flags = e->shard_flags_last;
-    e->shard_cdf_valid = true;
     return BPF_OK;
   }
-  e->shard_cdf_valid = false;
+  e->wc.shard_cdf_dropped();
   hipLaunchKernelGGL(k_normalize_gathered, dim3(nb), dim3(BPF_RED_BLOCK), 0, e->stream, s.w.p, n,
                      static_cast<const double*>(totals_dev), world, global_sample_count, e->d_scalars.p,
                      e->alpha_slow, e->alpha_fast, e->d_tile_sums.p, wait, (int)(e->mb.tot_gen & 1),
                      e->mb.tot_gen, fold, n_fold,
                      (mailbox_owns(e, totals_dev) && e->d_mb_error.p) ? (const unsigned*)e->d_mb_error.p : nullptr);
   HIPCHK(e, hipGetLastError());
-  e->tile_sums_n = n;
+  e->wc.tile_sums_left(n);
   return BPF_OK;
 }
 
@@ -238,11 +234,11 @@ int bpf_shard_build_cdf(bpf_engine* e, void* flags_dev)
   if (!e || !e->have_pf)
     return BPF_ERR_INVALID_ARGUMENT;
   HIPCHK(e, hipSetDevice(e->device));
-  if (e->shard_cdf_valid && e->cdf_ready_n == e->sample_count && !e->cdf_serial)
+  if (e->wc.shard_cdf_valid && e->wc.cdf_ready_n == e->sample_count && !e->cdf_serial)
   {
     // k_normalize_gathered_cdf of this update left the CDF and its sum behind; it cleared the caller's miss flag too
     // if this is the word the previous resample used
-    e->shard_cdf_valid = false;
+    e->wc.shard_cdf_dropped();
     if (e->shard_cdf_flags != flags_dev && flags_dev)
       HIPCHK(e, hipMemsetAsync(flags_dev, 0, sizeof(int), e->stream));
     e->shard_flags_last = flags_dev;
@@ -341,7 +337,7 @@ int draw_window_args(bpf_engine* e, uint64_t rng_state48, int m0, int m1, const 
     A.jump_table_n = kFusedWindow;
   }
   size_t lds = 0;
-  if (e->cdf_coarse_n == A.n_src && A.n_src > 0 && m1 - m0 <= 2 * kFusedWindow)
+  if (e->wc.cdf_coarse_n == A.n_src && A.n_src > 0 && m1 - m0 <= 2 * kFusedWindow)
   {
     // a short window after k_normalize_gathered_cdf: the draws bracket themselves in the CDF subsample first
     A.coarse = e->d_cdf_coarse.p;
@@ -385,14 +381,7 @@ int bpf_shard_adopt_dev(bpf_engine* e, const void* x_dev, const void* y_dev, con
                        static_cast<const double*>(theta_dev), b.dev(), count, 1.0 / (double)global_count);
     HIPCHK(e, hipGetLastError());
   }
-  e->cur ^= 1;
-  e->sample_count = count;
-  e->tree_pending = false;
-  e->leaf_count = leaf_count;
-  e->bin_count = bin_count;
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
-  e->set_epoch++;
-  e->hist_matches_set = false;
+  e->new_set(count, true, e->tree.counted(leaf_count, bin_count));
   return BPF_OK;
 }
 
@@ -413,16 +402,7 @@ int bpf_shard_tail_small_dev(bpf_engine* e, const void* x_all_dev, const void* y
                        lo, hi, b.dev(), e->dist_threshold, e->d_scalars.p, e->d_flags.p + 1);
   }
   HIPCHK(e, hipGetLastError());
-  e->cur ^= 1;
-  e->sample_count = hi - lo;
-  e->tree_pending = false;
-  e->leaf_count = leaf_count;
-  e->bin_count = bin_count;
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
-  e->set_epoch++;
-  e->hist_matches_set = false;
-  e->converged_pending = true;
-  e->conv_n = global_count;
+  e->new_set(hi - lo, true, e->tree.counted(leaf_count, bin_count), global_count);
   return BPF_OK;
 }
 
@@ -524,16 +504,7 @@ int shard_stop_block(bpf_engine* e, const long long* window, int stride, int cou
   *M_out = M;
   *leaf_out = r5[1];
   *bins_out = r5[2];
-  e->cur ^= 1;
-  e->sample_count = hi - lo;
-  e->tree_pending = false;
-  e->leaf_count = r5[1];
-  e->bin_count = r5[2];
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
-  e->converged_pending = true;
-  e->conv_n = M;
-  e->set_epoch++;
-  e->hist_matches_set = false;  // no host histogram of this set
+  e->new_set(hi - lo, true, e->tree.counted(r5[1], r5[2]), M);
   return BPF_OK;
 }
 }  // namespace
@@ -804,7 +775,7 @@ int systematic_window_args(bpf_engine* e, uint64_t rng_state48, int count, const
   if (rcm != BPF_OK)
     return rcm;
   size_t lds = 0;
-  if (e->cdf_coarse_n == A.n_src && A.n_src > 0 && count <= 2 * kFusedWindow)
+  if (e->wc.cdf_coarse_n == A.n_src && A.n_src > 0 && count <= 2 * kFusedWindow)
   {
     A.coarse = e->d_cdf_coarse.p;
     A.coarse_shift = fused_coarse_shift(A.n_src);

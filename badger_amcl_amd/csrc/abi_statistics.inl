@@ -289,7 +289,7 @@ int compute_cluster_stats(bpf_engine* e)
       host_pose_key(s[4 * i], s[4 * i + 1], s[4 * i + 2], key);
       e->hist.insert(key[0], key[1], key[2]);
     }
-    e->hist_matches_set = true;
+    e->hist_built();
   }
   rc = host_cluster_stats(e, s.data(), n, e->hist, e->max_samples);  // cluster_max_count (particle_filter.cpp:84)
   if (rc == BPF_OK)

@@ -136,7 +136,69 @@ struct FieldScan
   int table_len = 0;
 };
 
+// What the last weight pass left behind for the passes that follow it.  Invariant: a field that is set describes the
+// weights of the CURRENT set (sets[cur].w, sample_count of them) as they are now; whoever rewrites weights -- of any
+// set, the buffers are shared -- drops them first (bpf_engine::weights_overwritten and the transitions on top of it),
+// and only the launch that produced a buffer sets its field.  The two flags are not dropped: cdf_guide_valid is read
+// only behind a build_cdf that has either found cdf_ready_n set by the producer of both or rewritten it, and
+// shard_cdf_valid is honoured only together with cdf_ready_n == sample_count.
+struct WeightCaches
+{
+  int fused_partials = 0;        // > 0: the last scoring launch left that many per-block weight partials
+  int tile_sums_n = -1;          // >= 0: d_tile_sums holds the 2048-tile sums of the current weights for that n
+  int cdf_ready_n = -1;          // >= 0: d_cdf (and the guide) already hold the CDF of the current weights for that n
+  int cdf_coarse_n = -1;         // >= 0: d_cdf_coarse holds the subsample of the CDF in d_cdf for that n
+  bool cdf_guide_valid = false;  // d_cdf_guide holds head starts for the bisection of d_cdf
+  bool shard_cdf_valid = false;  // k_normalize_gathered_cdf left the local CDF of the current weights behind
+  void drop()
+  {
+    fused_partials = 0;
+    tile_sums_n = cdf_ready_n = cdf_coarse_n = -1;
+  }
+  // k_normalize_cdf / k_normalize_gathered_cdf: the normalised weights' CDF and its subsample (the tile sums went
+  // into them); `sharded`: it is the local CDF a bpf_shard_build_cdf may take
+  void cdf_left(int n, bool guide, bool sharded = false)
+  {
+    tile_sums_n = -1;
+    cdf_ready_n = cdf_coarse_n = n;
+    cdf_guide_valid = guide;
+    if (sharded)
+      shard_cdf_valid = true;
+  }
+  // k_normalize_fused / k_normalize_gathered: the tile sums of the normalised weights, for build_cdf to scan
+  void tile_sums_left(int n) { tile_sums_n = n; }
+  // build_cdf's scan kernels are about to write d_cdf: they leave no subsample, and the guide unless they run serially
+  void cdf_scan_begins(bool guide)
+  {
+    cdf_coarse_n = -1;
+    cdf_guide_valid = guide;
+  }
+  // the local CDF was taken by bpf_shard_build_cdf, or this normalisation / this init leaves none
+  void shard_cdf_dropped() { shard_cdf_valid = false; }
+};
+
+// Leaf and bin counts of the histogram tree of the current set (of the GLOBAL set on a sharded filter).  Invariant:
+// tree_pending means the counts are -1 and ensure_set_tree builds them before anybody reads them; -1 without
+// tree_pending means nobody has supplied them (a set adopted with a leaf count only, a sharded init before its
+// bpf_shard_tree_* stage).  Otherwise they are the counts of the set that is current NOW.
+struct TreeCounts
+{
+  int leaf_count = 0, bin_count = 0;
+  int gt_route = 0;           // BPF_SHARD_TREE_ROUTE_* of the counts installed last (0: none since the last init)
+  bool tree_pending = false;  // the current set's histogram tree (leaf / bin counts) has not been built yet
+  TreeCounts counted(int leaf, int bins) const { return TreeCounts{ leaf, bins, gt_route, false }; }
+  TreeCounts pending() const { return TreeCounts{ -1, -1, gt_route, true }; }
+};
+
 }  // namespace
+
+#define HIPCHK(e, call)                          \
+  do                                             \
+  {                                              \
+    hipError_t _r = (call);                      \
+    if (_r != hipSuccess)                        \
+      return (e)->fail_hip(_r, #call);           \
+  } while (0)
 
 struct bpf_engine
 {
@@ -223,7 +285,8 @@ struct bpf_engine
   SampleSet sets[2];
   int cur = 0;
   int sample_count = 0;
-  int leaf_count = 0, bin_count = 0;
+  WeightCaches wc;
+  TreeCounts tree;
   int converged = 0;
   float percent_converged = 0;
   bool converged_pending = false;
@@ -238,11 +301,7 @@ struct bpf_engine
   KdHistogram hist;
   SeenKeys seen;
   DevBuf<int> d_cdf_guide;     // head start for the CDF bisection (k_scan_final / cdf_find_guided)
-  bool cdf_guide_valid = false;
   DevBuf<double> d_cdf, d_partials, d_targets, d_block_partials, d_tile_sums;
-  int fused_partials = 0;     // > 0: the last scoring launch left that many per-block weight partials
-  int tile_sums_n = -1;       // >= 0: d_tile_sums holds the 2048-tile sums of the current weights for that n
-  int cdf_ready_n = -1;       // >= 0: d_cdf (and the guide) already hold the CDF of the current weights (k_normalize_cdf)
   DevBuf<unsigned long long> d_tile_slots;  // k_normalize_cdf's look-back slots, [2][256]
   unsigned tile_generation = 0;
   bool fused_resample = true; // BPF_OPT_FUSED_RESAMPLE
@@ -255,7 +314,6 @@ struct bpf_engine
   int kld_generation = 0;
   int kld_persist_blocks_per_cu = -1;  // occupancy of k_kld_tree_persistent (-1: not asked yet)
   DevBuf<unsigned> d_kld_bar;
-  bool shard_cdf_valid = false;        // k_normalize_gathered_cdf left the local CDF of the current weights behind
   void* shard_cdf_flags = nullptr;     // the caller's miss flag that launch cleared (null: none)
   void* shard_flags_last = nullptr;    // flags_dev of the last bpf_shard_build_cdf
   int fused_used = 0;         // the last resample ran as the one-block kernel
@@ -265,7 +323,6 @@ struct bpf_engine
   DevBuf<unsigned long long> d_fused_keys;
   DevBuf<unsigned> d_fused_counter;
   DevBuf<double> d_cdf_coarse;
-  int cdf_coarse_n = -1;      // d_cdf_coarse holds the subsample of the CDF in d_cdf for that n
   DevBuf<FilterScalars> d_scalars;
   DevBuf<int> d_keys, d_src_index, d_flags;  // d_flags[0] miss, [1] converged count
   DevBuf<double4> d_aos;
@@ -438,7 +495,6 @@ struct bpf_engine
   DevBuf<unsigned long long> d_gt_key;
   DevBuf<int> d_gt_tmin, d_gt_eslot, d_gt_tiles, d_gt_flags;
   PinnedBuf<int> h_gt_flags;
-  int gt_route = 0;                 // BPF_SHARD_TREE_ROUTE_* of the counts installed last (0: none since the last init)
 
   // ---- cluster statistics (host, lazy)
   std::vector<bpf_cluster> clusters;
@@ -468,7 +524,6 @@ struct bpf_engine
   PinnedBuf<double> h_seam_w;       // [n] the chunked form's weights on their way back: FINE-grained (see PinnedBuf)
   int last_seam_chunks = 0;         // chunks the last applyModelToSampleSet used (0: the plain sequence)
   bool last_seam_registered = false;
-  bool tree_pending = false;        // the current set's histogram tree (leaf / bin counts) has not been built yet
 
   std::vector<double> stage_bx, stage_by;  // stage_field_scan's scratch: beam end points of every decimated beam
 
@@ -507,12 +562,77 @@ struct bpf_engine
   {
     return fail(BPF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(r));
   }
+
+  // ---- transitions: every change of the particle set goes through one of these, and wc, tree, set_epoch and
+  // hist_matches_set are written here and in the two structs' own members, nowhere else.  Two
+  // exceptions: wc.fused_partials is set by the scoring launch and cleared by the launch that folds the partials, and
+  // TrialScores::score and shard_init_all put back a saved copy of wc / tree around work on a set that is not current
+
+  // A scoring pass is about to overwrite the weights of a set that may not be the engine's (the candidate poses of
+  // the uniform pose check, the host-buffer seam's scratch set: applyModelToSampleSet on a set of the caller's): the
+  // buffers behind wc are its to use.  No epoch bump: the current set keeps its statistics.
+  void weights_overwritten() { wc.drop(); }
+  // The CURRENT set's weights changed (updateSensor's scoring and normalisation, a sharded stage of them): cached
+  // statistics no longer describe it.  What the pass itself left in wc describes the new weights and stays; a site
+  // that leaves nothing calls weights_overwritten as well.
+  void weights_changed() { set_epoch++; }
+  // Another set is current (updateResample's and updateAction's swap of current_set_, a set loaded or restored in
+  // place): n samples, in the other buffer when `flip`; `t` are its tree counts (tree.counted / tree.pending /
+  // tree itself when the poses' tree is the one already described).  converged_of > 0: updateConverged's count over
+  // that many samples is on the device, for fetch_scalars to turn into `converged`.
+  void new_set(int n, bool flip, const TreeCounts& t, int converged_of = 0)
+  {
+    if (flip)
+      cur ^= 1;
+    sample_count = n;
+    wc.drop();
+    set_epoch++;
+    hist_matches_set = false;
+    tree = t;
+    if (converged_of > 0)
+    {
+      converged_pending = true;
+      conv_n = converged_of;
+    }
+  }
+  // initWithGaussian / initWithPoseFn / a set given by the caller (particle_filter.cpp:126-131,157-168): a new set,
+  // w_slow = w_fast = 0, converged = false; `spread`: the poses are uniform over the free space
+  int fresh_filter(int n, bool flip, const TreeCounts& t, bool spread)
+  {
+    new_set(n, flip, t);
+    spread_init = spread;
+    HIPCHK(this, hipMemsetAsync(d_scalars.p, 0, sizeof(FilterScalars), stream));
+    converged = 0;
+    converged_pending = false;
+    return BPF_OK;
+  }
+  // ParticleFilter's constructor (particle_filter.cpp:62-89).  Not a new_set: bpf_pf_create has never invalidated
+  // what an earlier filter on this engine left
+  void filter_created()
+  {
+    tree.leaf_count = tree.bin_count = 0;
+    converged = 0;
+    converged_pending = false;
+  }
+  // updateResample has taken what it needs from the current set's tree and is about to draw: the resampler builds
+  // the new set's tree from its draws, and its outcome says from here on whether the cloud is spread
+  void resample_begins()
+  {
+    tree.tree_pending = false;
+    spread_init = false;
+  }
+  // the current set's tree was built from its poses (PFKDTree of every sample, pf_kdtree.cpp:49-56) ...
+  void tree_counted(int leaf, int bins) { tree = tree.counted(leaf, bins); }
+  // ... or, for the global set of a sharded filter, from the ranks' bin lists or keys: e->hist, where that used it,
+  // holds every distinct key ONCE and is not the set's histogram
+  void tree_installed(int leaf, int bins, int route)
+  {
+    tree = TreeCounts{ leaf, bins, route, false };
+    hist_matches_set = false;
+  }
+  // the counts were taken in the other KLD count mode: computed again when they are needed
+  void tree_invalidated() { tree = tree.pending(); }
+  // e->hist now holds every pose of the current set, inserted in index order
+  void hist_built() { hist_matches_set = true; }
 };
 
-#define HIPCHK(e, call)                          \
-  do                                             \
-  {                                              \
-    hipError_t _r = (call);                      \
-    if (_r != hipSuccess)                        \
-      return (e)->fail_hip(_r, #call);           \
-  } while (0)

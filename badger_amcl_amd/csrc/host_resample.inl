@@ -76,7 +76,7 @@ int ensure_cdf_buffers(bpf_engine* e, int n)
 }
 
 // ParticleFilter::updateSensor's normalisation and the CDF of the normalised weights in one launch (k_normalize_cdf);
-// needs the scoring kernel's per-block partials (e->fused_partials) and at most 256 tiles
+// needs the scoring kernel's per-block partials (e->wc.fused_partials) and at most 256 tiles
 int launch_normalize_cdf(bpf_engine* e, double* w, int n)
 {
   const int nb = std::max(1, blocks_for(n, BPF_RED_TILE));
@@ -93,7 +93,7 @@ int launch_normalize_cdf(bpf_engine* e, double* w, int n)
   A.w = w;
   A.n = n;
   A.block_partials = e->d_block_partials.p;
-  A.n_partials = e->fused_partials;
+  A.n_partials = e->wc.fused_partials;
   A.sc = e->d_scalars.p;
   A.alpha_slow = e->alpha_slow;
   A.alpha_fast = e->alpha_fast;
@@ -113,22 +113,19 @@ int launch_normalize_cdf(bpf_engine* e, double* w, int n)
   ProfScope ps(e, BPF_K_NORMALIZE);
   hipLaunchKernelGGL(k_normalize_cdf, dim3(nb), dim3(BPF_RED_BLOCK), 0, e->stream, A);
   HIPCHK(e, hipGetLastError());
-  e->tile_sums_n = -1;
-  e->cdf_ready_n = n;
-  e->cdf_coarse_n = n;
-  e->cdf_guide_valid = want_guide;
+  e->wc.cdf_left(n, want_guide);
   return BPF_OK;
 }
 
 int build_cdf(bpf_engine* e, const double* w, int n, int* zero_word2 = nullptr, double* sum_out = nullptr)
 {
-  if (e->cdf_ready_n == n && w == e->sets[e->cur].w.p && !e->cdf_serial && zero_word2 == nullptr && sum_out == nullptr)
+  if (e->wc.cdf_ready_n == n && w == e->sets[e->cur].w.p && !e->cdf_serial && zero_word2 == nullptr &&
+      sum_out == nullptr)
     return BPF_OK;  // k_normalize_cdf left it behind
   int rcb = ensure_cdf_buffers(e, n);
   if (rcb != BPF_OK)
     return rcb;
-  e->cdf_coarse_n = -1;  // the scan kernels below leave no subsample
-  e->cdf_guide_valid = !e->cdf_serial;
+  e->wc.cdf_scan_begins(!e->cdf_serial);
   ProfScope ps(e, BPF_K_CDF);
   if (e->cdf_serial)
   {
@@ -143,10 +140,10 @@ int build_cdf(bpf_engine* e, const double* w, int n, int* zero_word2 = nullptr, 
   {
     const int nb = std::max(1, blocks_for(n, BPF_RED_TILE));
     double* tiles;
-    if (e->tile_sums_n == n && w == e->sets[e->cur].w.p)
+    if (e->wc.tile_sums_n == n && w == e->sets[e->cur].w.p)
     {
       tiles = e->d_tile_sums.p;  // left behind by k_normalize_fused; consumed (scanned in place) here
-      e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
+      e->wc.drop();
     }
     else
     {
@@ -298,15 +295,12 @@ struct TrialScores
       HIPCHK(e, hipGetLastError());
       // the scoring call resets the engine's per-set caches (partials, CDF hand-over); the candidate set is not the
       // engine's set, so they are put back
-      const int fp = e->fused_partials, ts = e->tile_sums_n, cr = e->cdf_ready_n, cc = e->cdf_coarse_n;
+      const WeightCaches caches = e->wc;
       const long long ev = e->evals_last;
       bool forced_zero = false;
       int rc = score_planar(e, e->cand.dev(), n, 0, e->scan_ranges.data(), e->scan_angles.data(),
                             (int)e->scan_ranges.size(), e->scan_range_max, &forced_zero);
-      e->fused_partials = fp;
-      e->tile_sums_n = ts;
-      e->cdf_ready_n = cr;
-      e->cdf_coarse_n = cc;
+      e->wc = caches;
       e->evals_last = ev;
       if (rc != BPF_OK)
         return rc;
@@ -579,7 +573,7 @@ int resample_block(bpf_engine* e, int window, bool systematic, const double* tar
   A.n_src = e->sample_count;
   A.cdf = e->d_cdf.p;
   A.coarse_shift = fused_coarse_shift(A.n_src);
-  A.coarse = (e->cdf_coarse_n == A.n_src) ? e->d_cdf_coarse.p : nullptr;
+  A.coarse = (e->wc.cdf_coarse_n == A.n_src) ? e->d_cdf_coarse.p : nullptr;
   A.dst = b.dev();
   A.window = window;
   A.max_samples = e->max_samples;
@@ -1076,7 +1070,7 @@ int resample_multinomial(bpf_engine* e, double w_diff)
       {
         const int M = e->sample_count;
         e->rng = lcg_skip_host(e->rng, 2ull * (uint64_t)M, e->jump);
-        e->window_hint = std::max(1024, ((M + M / 4) + 1023) / 1024 * 1024);
+        e->window_hint = resample_window_for(M);
         return BPF_OK;
       }
     }
@@ -1112,7 +1106,7 @@ int resample_multinomial(bpf_engine* e, double w_diff)
     A.sharded = 0;
     A.chain = chain;
     A.free_space = free_space;
-    A.guide = e->cdf_guide_valid ? e->d_cdf_guide.p : nullptr;
+    A.guide = e->wc.cdf_guide_valid ? e->d_cdf_guide.p : nullptr;
     // long stream ahead: the previous cycle ran to the end, or the windows so far found no stop and the bound for
     // the leaves seen so far (a lower estimate of where the stop will be) is still far away
     const bool long_stream = (m0 > 0 ? cached_limit - m0 >= e->kld_device_min : e->window_hint >= maxs) &&
@@ -1188,7 +1182,7 @@ int resample_multinomial(bpf_engine* e, double w_diff)
     m0 = m1;
     // next window: up to a quarter past the bound for the leaves seen so far
     const int need = cached_limit - m0;
-    window = std::max(1024, (need + need / 4 + 1023) / 1024 * 1024);
+    window = resample_window_for(need);
   }
   const int M = (stop > 0) ? stop : maxs;
   // the window that found the stop also inserted nothing past it: hist is exactly set b's tree
@@ -1201,7 +1195,7 @@ int resample_multinomial(bpf_engine* e, double w_diff)
   }
   else
     e->rng = lcg_skip_host(e->rng, 2ull * (uint64_t)M, e->jump);
-  e->window_hint = std::max(1024, ((M + M / 4) + 1023) / 1024 * 1024);
+  e->window_hint = resample_window_for(M);
   e->sample_count = M;
   return BPF_OK;
 }
@@ -1212,7 +1206,7 @@ int resample_systematic(bpf_engine* e, double w_diff)
   SampleSet& b = e->sets[e->cur ^ 1];
   const int n = e->sample_count;
   e->fused_used = 0;
-  int count = resample_limit(e->leaf_count, e->min_samples, e->max_samples, e->pop_err, e->pop_z);
+  int count = resample_limit(e->tree.leaf_count, e->min_samples, e->max_samples, e->pop_err, e->pop_z);
   FreeSpaceDev free_space{};
   int num_random = 0;
   uint64_t random_consumed = 0;  // stream elements of the random pose calls, after the systematic start

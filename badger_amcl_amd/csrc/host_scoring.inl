@@ -393,7 +393,7 @@ int launch_field(bpf_engine* e, ParticlesDev p, int n, ScanSlot* s, const FieldS
   {
     HIPCHK(e, e->d_block_partials.reserve((size_t)grid));
     A.block_partials = e->d_block_partials.p;
-    e->fused_partials = grid;
+    e->wc.fused_partials = grid;
     // LDS-window path for big updates: the device decides (from the cloud's spread) whether the
     // window kernels or k_score_field do the work; the other one returns immediately.
     const int n_chunks = (fs.n_staged + 63) / 64;
@@ -470,7 +470,7 @@ int launch_field(bpf_engine* e, ParticlesDev p, int n, ScanSlot* s, const FieldS
     HIPCHK(e, e->d_block_partials.reserve((size_t)nb));
     hipLaunchKernelGGL(k_sum_partials, dim3(nb), dim3(BPF_RED_BLOCK), 0, e->stream, (const double*)p.w, n,
                        e->d_block_partials.p);
-    e->fused_partials = nb;  // the normalise launch folds these instead of the scoring kernel's
+    e->wc.fused_partials = nb;  // the normalise launch folds these instead of the scoring kernel's
     e->last_score_form = 3;
   }
   else if (table_lds)
@@ -585,8 +585,7 @@ int score_planar(bpf_engine* e, ParticlesDev p, int n, int set_converged, const 
                  bool defer_beamskip_pass2 = false, const double4* aos = nullptr)
 {
   *forced_zero = false;
-  e->fused_partials = 0;
-  e->tile_sums_n = e->cdf_ready_n = e->cdf_coarse_n = -1;
+  e->weights_overwritten();
   if (!e->have_map)
     return e->fail(BPF_ERR_NOT_CONFIGURED, "no 2-D map set");
   if (!e->have_lut)
