@@ -151,6 +151,10 @@ SIGNATURES = {
     "bpf_shard_compute_cluster_stats": (C.c_int, [_vp, _ip, _dp, _dp, _ip]),
     "bpf_shard_get_max_weight_pose": (C.c_int, [_vp, _dp, _dp]),
     "bpf_shard_exchange_count": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
+    "bpf_pf_get_pose_array": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, _ip]),
+    "bpf_shard_pose_rows_dev": (C.c_int, [_vp, C.c_longlong, C.c_longlong, C.c_int, C.POINTER(_vp), _ip]),
+    "bpf_pose_array_from_rows_dev": (C.c_int, [_vp, _vp, C.c_longlong, C.c_int, _dp, C.c_int]),
+    "bpf_shard_get_pose_array": (C.c_int, [_vp, C.c_int, C.c_longlong, C.c_int, _dp, C.c_int, _ip]),
     "bpf_shard_mailbox_update_sensor_planar": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, C.c_longlong]),
     "bpf_shard_mailbox_update_resample": (C.c_int, [_vp, _vp, _ip, _ip, _ip, _ip, _ip]),
     "bpf_shard_mailbox_destroy": (C.c_int, [_vp]),

@@ -26,6 +26,7 @@
 #include "kernels_kld_bins.hpp"
 #include "kernels_recovery.hpp"
 #include "kernels_pf.hpp"
+#include "kernels_pose_array.hpp"
 #include "kernels_fused.hpp"
 #include "kernels_stats.hpp"
 #include "kernels_shard_stats.hpp"
@@ -68,6 +69,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_shard_init.inl"
 #include "abi_mailbox_step.inl"
 #include "abi_shard_node.inl"
+#include "abi_pose_array.inl"
 #include "abi_bootstrap.inl"
 #include "abi_measure.inl"
 }  // extern "C"

@@ -427,6 +427,12 @@ struct bpf_engine
   PinnedBuf<int> h_mb_result;
   DevBuf<unsigned> d_mb_counter;
 
+  // ---- the particle-cloud message formed on the device (kernels_pose_array.hpp, abi_pose_array.inl): buffers of
+  // their own, so that a query between two updates disturbs nothing another stage has left behind
+  DevBuf<long long> d_pa_rows;      // int64[3][n_sel]: this slice's selected x / y / theta bits
+  DevBuf<long long> d_pa_gather;    // int64[3][count]: every rank's rows in global order
+  DevBuf<double> d_pa_out;          // double[count][7]: the formed poses on their way to the host
+
   // ---- KLD stop rule on the device (long draw streams)
   int kld_device_min = 8192;  // draws left after the first window from which the device tree takes over
   bool kld_device_used = false;

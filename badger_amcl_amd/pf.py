@@ -379,6 +379,21 @@ class ParticleFilter:
         self.e.check(self.e.lib.bpf_pf_get_samples(self.e.h, _dp(out), out.shape[0], C.byref(n)))
         return PFSampleSet(out[:n.value].copy() if mine else out[:n.value], st)
 
+    def getPoseArray(self, first=0, stride=1, out=None):
+        """Node::publishParticleCloud's poses (node.cpp:335-357) formed on the device: [count, 7] float64 rows
+        {x, y, 0, qx, qy, qz, qw} of samples first, first + stride, ...  `out`: the caller's own [>= count, 7] buffer,
+        e.g. one registered with Engine.registerHostBuffer (the copy engine then writes it directly); the result is a
+        view of it."""
+        if out is None:
+            n = self.getState().sample_count
+            room = (n - first + stride - 1) // stride if stride >= 1 and 0 <= first < n else 0
+            out = np.empty((max(room, 1), 7), dtype=np.float64)
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.ndim == 2 and out.shape[1] == 7
+        n = C.c_int()
+        self.e.check(self.e.lib.bpf_pf_get_pose_array(self.e.h, int(first), int(stride), _dp(out), out.shape[0],
+                                                      C.byref(n)))
+        return out[:n.value]
+
     def isConverged(self):
         return bool(self.getState().converged)
 

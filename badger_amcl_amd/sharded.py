@@ -76,6 +76,7 @@ class HipShardBackend:
         buf = (C.c_ubyte * 64)()
         rc = self.e.lib.bpf_shard_mailbox_create(self.e.h, rank, world, int(max_window), buf)
         self._mb_world, self._mb_stride, self._mb_views = world, int(max_window), {}
+        self._mb_rank = rank
         return bytes(buf) if rc == 0 else None
 
     def mailbox_connect(self, handles):
@@ -339,6 +340,37 @@ class HipShardBackend:
     def stats_max_weight_pose(self):
         return self.pf.getMaxWeightPose()
 
+    # ---- the particle cloud of the global set (include/badger_pf.h, bpf_shard_pose_rows_dev and the calls around it)
+    def pose_rows(self, global_first, first, stride):
+        """int64 [3, n_sel] device view: x / y / theta bits of the slice's samples that the selection first,
+        first + stride, ... of the GLOBAL index space picks (engine memory, valid until the next pose-array call)."""
+        p, n = C.c_void_p(), C.c_int()
+        self.e.check(self.e.lib.bpf_shard_pose_rows_dev(self.e.h, int(global_first), int(first), int(stride),
+                                                        C.byref(p), C.byref(n)))
+        if n.value == 0:
+            return torch.empty((3, 0), dtype=torch.int64, device=self.device)
+        return torch.as_tensor(_DevArray(p.value, (3, n.value), "<i8"), device=self.device)
+
+    def pose_array_from_rows(self, rows, n):
+        """rows: int64 [3, >= n] device tensor of gathered rows in global order; the [n, 7] float64 pose array."""
+        out = np.empty((max(int(n), 1), 7), dtype=np.float64)
+        assert rows.dtype == torch.int64 and rows.shape[0] == 3 and rows.stride(1) == 1 and rows.shape[1] >= n
+        self.e.check(self.e.lib.bpf_pose_array_from_rows_dev(
+            self.e.h, C.c_void_p(rows.data_ptr()), int(rows.stride(0)) if n else 0, int(n),
+            out.ctypes.data_as(C.POINTER(C.c_double)), out.shape[0]))
+        return out[:int(n)]
+
+    def get_pose_array_all(self, root, first, stride, room):
+        """The whole query over the engine's own exchange (mailbox): the [count, 7] array where this rank receives,
+        else None."""
+        receives = root < 0 or root == self._mb_rank
+        out = np.empty((max(int(room), 1), 7), dtype=np.float64) if receives else None
+        n = C.c_int()
+        self.e.check(self.e.lib.bpf_shard_get_pose_array(
+            self.e.h, int(root), int(first), int(stride),
+            out.ctypes.data_as(C.POINTER(C.c_double)) if receives else None, int(room), C.byref(n)))
+        return out[:n.value] if receives else None
+
     # ---- a sharded set initialised on its ranks, and the global set's tree (include/badger_pf.h, bpf_shard_init_*,
     # bpf_shard_tree_*)
     @staticmethod
@@ -440,6 +472,19 @@ class HipShardBackend:
 
     def state(self):
         return self.pf.getState()
+
+
+def pose_selection(counts, first, stride):
+    """Which samples of every slice the selection first, first + stride, ... of the global index space picks: per rank
+    (local index of the first selected sample, number selected), from the ranks' sample counts alone."""
+    if stride < 1 or first < 0:
+        raise ValueError("pose_selection: first >= 0 and stride >= 1")
+    out, at = [], 0
+    for n in counts:
+        i0 = (stride - (at - first) % stride) % stride if at >= first else first - at
+        out.append((i0, (n - i0 + stride - 1) // stride if i0 < n else 0))
+        at += n
+    return out
 
 
 class ShardedState:
@@ -959,6 +1004,30 @@ class ShardedFilter:
         """Node2D::getMaxWeightPose over the global set: (weight, pose) of the heaviest cluster."""
         self._ensure_stats()
         return self.b.stats_max_weight_pose()
+
+    # ---- the particle cloud (Node::publishParticleCloud, node.cpp:335-357) of the GLOBAL set
+    def get_pose_array(self, root=0, first=0, stride=1):
+        """[count, 7] float64 rows {x, y, 0, qx, qy, qz, qw} of the global samples first, first + stride, ... in
+        global order, on rank `root` (root = -1: on every rank); None on the other ranks.  Collective: every rank
+        calls it with the same arguments.  One ragged all-gather of the selected x / y / theta bits; the statistics,
+        the totals and the set stay as they are."""
+        if not -1 <= root < self.world:
+            raise ValueError("get_pose_array: root in [-1, world)")
+        sel = pose_selection(self.counts, first, stride)
+        count = sum(n for _, n in sel)
+        if self.mailbox and hasattr(self.b, "get_pose_array_all"):
+            return self.b.get_pose_array_all(root, first, stride, count)
+        receives = root < 0 or root == self.rank
+        if count == 0:
+            return np.empty((0, 7), dtype=np.float64) if receives else None
+        mine = self.b.pose_rows(sum(self.counts[:self.rank]), first, stride)
+        sel_counts = [n for _, n in sel]
+        assert mine.shape[1] == sel_counts[self.rank]
+        allr, _ = self._gather_ragged(mine, sel_counts)
+        if not receives:
+            return None
+        rows = torch.cat([allr[r, :, :sel_counts[r]] for r in range(self.world)], dim=1).contiguous()
+        return self.b.pose_array_from_rows(rows, count)
 
     def set_random_pose_generator(self, mode):
         """random_pose_fn of this rank's engine (pf.RANDOM_POSE_*); every rank sets the same mode.  Every rank

@@ -285,6 +285,22 @@ public:
     e_->check(bpf_pf_get_max_weight_pose(e_->get(), max_weight_out, pose));
     *max_pose = { pose[0], pose[1], pose[2] };
   }
+  // Node::publishParticleCloud's poses (node.cpp:335-357) formed on the device: *poses7 ends as count x
+  // {x, y, 0, qx, qy, qz, qw} of samples first, first + stride, ...  A vector that keeps its storage between calls can
+  // be registered once (bpf_host_buffer_register on poses7->data(), again only when it grows): the copy engine then
+  // writes it directly.
+  void getPoseArray(std::vector<double>* poses7, int first = 0, int stride = 1)
+  {
+    bpf_pf_state st;
+    e_->check(bpf_pf_get_state(e_->get(), &st));
+    const long long n = st.sample_count;
+    const long long room = (stride >= 1 && first >= 0 && first < n) ? (n - first + stride - 1) / stride : 0;
+    if (poses7->size() < (size_t)(7 * room + 7))
+      poses7->resize((size_t)(7 * room + 7));  // (never an empty vector: data() must be an address)
+    int count = 0;
+    e_->check(bpf_pf_get_pose_array(e_->get(), first, stride, poses7->data(), (int)room, &count));
+    poses7->resize((size_t)7 * (size_t)count);
+  }
   Engine& engine() { return *e_; }
 
 private:
@@ -473,6 +489,23 @@ public:
     double pose[3] = { 0, 0, 0 };
     e().check(bpf_shard_get_max_weight_pose(e().get(), max_weight_out, pose));
     *max_pose = { pose[0], pose[1], pose[2] };
+  }
+  // Node::publishParticleCloud's poses of the GLOBAL set in global order (samples first, first + stride, ...), on rank
+  // `root` or, with root = -1, on every rank: *poses7 ends as count x 7 doubles there and empty elsewhere (where it may
+  // be null).  Returns whether this rank received the array.
+  bool getPoseArray(int root, std::vector<double>* poses7, long long first = 0, int stride = 1)
+  {
+    const bool receives = root < 0 || root == rank_;
+    const long long n = global_count_;
+    const long long room = (stride >= 1 && first >= 0 && first < n) ? (n - first + stride - 1) / stride : 0;
+    if (receives && poses7 && poses7->size() < (size_t)(7 * room + 7))
+      poses7->resize((size_t)(7 * room + 7));
+    int count = 0;
+    e().check(bpf_shard_get_pose_array(e().get(), root, first, stride, receives && poses7 ? poses7->data() : nullptr,
+                                       (int)room, &count));
+    if (poses7)
+      poses7->resize(receives ? (size_t)7 * (size_t)count : 0);
+    return receives;
   }
   // ParticleFilter::getClusterStats over the GLOBAL set
   bool getClusterStats(int cidx, double* weight, std::array<double, 3>* mean)

@@ -793,6 +793,44 @@ int bpf_shard_global_leaf_count(bpf_engine* e, int* leaf_count_out, int* bin_cou
 /* Diagnostic: exchanges this engine has issued since bpf_shard_bootstrap (or bpf_shard_mailbox_connect) set the
  * exchange up -- totals, draw windows, gathers and reduce rounds together. */
 int bpf_shard_exchange_count(bpf_engine* e, long long* out);
+
+/* ------------------------------------------------------------------ the particle cloud, formed on the device
+ * Node::publishParticleCloud (node.cpp:335-357) loops over set->sample_count samples after every scanner update
+ * (node_2d.cpp:384-385, node_3d.cpp:363-364), q.setRPY(0, 0, theta) and one geometry_msgs::Pose each.  These calls
+ * replace that loop: PoseArray entries {x, y, 0, qx, qy, qz, qw} = {x, y, 0, 0, 0, sin(theta / 2), cos(theta / 2)}, the
+ * layout and the arithmetic of bpf_wire_samples_to_pose_array, written by one kernel and read back in one copy.  x and y
+ * are the set's bits, the three zeros are +0.0, sin / cos are the device's (within a few units in the last place of
+ * libm's).  The header (stamp, frame id) stays with the caller.
+ *
+ * For all four: stride < 1, first < 0, a root outside [-1, world) or a null output on a receiving rank return
+ * BPF_ERR_INVALID_ARGUMENT; capacity (in poses) < count returns BPF_ERR_CAPACITY and leaves poses7_out alone; without a
+ * filter (the sharded one-call form: or without an exchange) BPF_ERR_NOT_CONFIGURED; an empty selection is BPF_OK with
+ * count 0.  Read-only for the filter: set, weights, statistics in force, tree counts, the CDF hand-over and the
+ * drand48 state stay as they were, and no buffer of another stage is borrowed.  poses7_out inside a
+ * bpf_host_buffer_register'ed range is written by the copy engine directly (keep one PoseArray alive and register
+ * its storage once); pageable memory goes through the engine's pinned bounce buffer.  On return the copy is complete. */
+/* Node::publishParticleCloud's poses from the RESIDENT set: pose k = sample first + k * stride, k = 0 .. count-1,
+ * count = first < n ? (n - first + stride - 1) / stride : 0.  first = 0, stride = 1 is the reference's message.   */
+int bpf_pf_get_pose_array(bpf_engine* e, int first, int stride, double* poses7_out, int capacity, int* count_out);
+/* Stage forms for a host with its own transport (node.cpp:335-357 over a sharded set).  rows: the x / y / theta bits
+ * of the samples of THIS slice (which starts at global index global_first) that the selection first, first + stride,
+ * ... of the GLOBAL index space picks, as int64[3][n_rows] with row stride n_rows, in index order (engine memory,
+ * valid until the next pose-array call).  The caller concatenates the ranks' rows in rank order ... */
+int bpf_shard_pose_rows_dev(bpf_engine* e, long long global_first, long long first, int stride,
+                            void** rows_dev, int* n_rows_out);          /* int64[3][n_rows] of this slice        */
+/* ... and any engine forms the n poses from the gathered rows int64[3][n] with row stride row_stride (device memory) */
+int bpf_pose_array_from_rows_dev(bpf_engine* e, const void* rows_dev, long long row_stride, int n,
+                                 double* poses7_out, int capacity);     /* any engine; no filter needed          */
+/* One call over the engine's own exchange (after bpf_shard_bootstrap); collective: every rank calls it with the
+ * same root / first / stride.  root >= 0: that rank receives, the others may pass poses7_out = NULL;
+ * root = -1: every rank receives.  count_out is set on every rank.  (node.cpp:335-357 on the publishing rank.)
+ * Two exchanges: the local sample counts, from which every rank derives every rank's share of the selection, then
+ * one ragged gather of the rows (3 words per selected pose); every rank takes part in both, only receivers form and
+ * read back.  Legal wherever bpf_shard_get_max_weight_pose is; makes no exchange for an empty selection beyond the
+ * counts.  BPF_ERR_EXCHANGE after a mailbox wait that ran out, BPF_ERR_CAPACITY when the rows exceed the mailbox's
+ * window region: the output is untouched. */
+int bpf_shard_get_pose_array(bpf_engine* e, int root, long long first, int stride, double* poses7_out,
+                             int capacity, int* count_out);
 /* insert every key of the window into the engine's histogram tree (no stop rule): the tree of a systematic
  * resample, or of an initial set (keys as bpf_kld_feed / bpf_kld_feed_dev take them) */
 int bpf_kld_insert(bpf_engine* e, const void* keys, int keys_are_int64, int stride, int n_keys);
