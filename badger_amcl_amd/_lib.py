@@ -145,6 +145,10 @@ SIGNATURES = {
     "bpf_shard_mailbox_error_stage": (C.c_int, [_vp, _ip, _ip]),
     "bpf_shard_bootstrap": (C.c_int, [_vp, C.c_int, C.c_int, C.c_char_p, C.c_longlong, C.c_int, _ip]),
     "bpf_shard_shutdown": (C.c_int, [_vp]),
+    "bpf_shard_connect_local": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int]),
+    "bpf_shard_exchange_mode": (C.c_int, [_vp, _ip]),
+    "bpf_shard_local_selftest": (C.c_int, [_vp, C.c_int]),
+    "bpf_shard_exchange_probe": (C.c_int, [_vp, C.c_int, C.c_longlong, C.c_int, _dp]),
     "bpf_shard_update_sensor_planar": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, C.c_longlong]),
     "bpf_shard_update_resample": (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip, _ip]),
     "bpf_shard_update_sensor_cloud": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, C.c_longlong]),

@@ -213,6 +213,9 @@ void collective_release(bpf_engine* e)
     (void)c.fn.destroy(c.comm);
   c.comm = nullptr;
   c.active = false;
+  if (c.local)
+    c.fn = bpf_engine::Collective::Fn{};  // the in-process table: collective_load resolves RCCL's again
+  c.local = false;
   // the library stays loaded for the life of the process (RCCL does not like being unloaded)
 }
 
@@ -220,7 +223,7 @@ void collective_release(bpf_engine* e)
 int collective_load(bpf_engine* e)
 {
   bpf_engine::Collective& c = e->coll;
-  if (c.lib)
+  if (c.lib && c.fn.init)
     return BPF_OK;
   std::string dir;
   Dl_info info;
@@ -231,7 +234,8 @@ int collective_load(bpf_engine* e)
     dir = (slash == std::string::npos) ? std::string() : dir.substr(0, slash + 1);
   }
   const std::string path = dir + "libbadger_pf_rccl.so";
-  c.lib = ::dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+  if (!c.lib)
+    c.lib = ::dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
   if (!c.lib)
     return e->fail(BPF_ERR_NOT_CONFIGURED, std::string("cannot load ") + path + ": " + ::dlerror());
   auto sym = [&](const char* name) { return ::dlsym(c.lib, name); };

@@ -534,13 +534,12 @@ int bpf_shard_converged_dev(bpf_engine* e, const void* x_all_dev, const void* y_
 
 uint64_t bpf_drand48_skip(uint64_t state48, uint64_t n)
 {
-  static LcgJump J;
-  static bool init = false;
-  if (!init)
-  {
-    lcg_tables(J);
-    init = true;
-  }
+  // (a function-local static with an initialiser: built once, also when several rank threads come here together)
+  static const LcgJump J = [] {
+    LcgJump j;
+    lcg_tables(j);
+    return j;
+  }();
   return lcg_skip_host(state48 & ((1ull << 48) - 1), n, J);
 }
 

@@ -4,6 +4,8 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <condition_variable>
+#include <mutex>
 #include <functional>
 #include <queue>
 #include <cmath>
@@ -71,5 +73,6 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_shard_node.inl"
 #include "abi_pose_array.inl"
 #include "abi_bootstrap.inl"
+#include "abi_shard_local.inl"
 #include "abi_measure.inl"
 }  // extern "C"

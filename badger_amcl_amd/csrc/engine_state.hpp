@@ -392,6 +392,7 @@ struct bpf_engine
   struct Collective
   {
     bool active = false;
+    bool local = false;             // fn is the in-process table of abi_shard_local.inl, comm a seat of its world
     void* lib = nullptr;
     void* comm = nullptr;
     struct Fn

@@ -1,0 +1,346 @@
+"""A sharded filter with ALL its ranks in this process (include/badger_pf.h, bpf_shard_connect_local).
+
+LocalShardedFilter owns W engines' filters and W worker threads, one per engine, and carries ShardedFilter's public
+method names: every collective member fans out to the workers -- each enters the engine's one-call form
+(bpf_shard_update_sensor_planar, bpf_shard_update_resample, ...) for its rank, ctypes releases the GIL for the length
+of the call, and the ranks meet inside the library at the exchanges -- and joins them.  The ranks' status codes must
+agree (a RuntimeError otherwise); the figures returned are rank 0's.  There is no torch.distributed process group, no
+socket and no child process behind it."""
+import ctypes as C
+import queue
+import threading
+
+import numpy as np
+
+from .pf import BpfError
+from .sharded import ShardedState
+
+EXCHANGE_NONE, EXCHANGE_MAILBOX, EXCHANGE_RCCL, EXCHANGE_LOCAL = 0, 1, 2, 3
+STATS_ROUTES = {1: "gathered", 2: "distributed", 3: "host"}
+TREE_ROUTES = {1: "device", 2: "host", 3: "bins", 4: "keys"}
+_dp = C.POINTER(C.c_double)
+
+
+class _Worker(threading.Thread):
+    """The host thread of one rank: runs what it is handed, in order."""
+
+    def __init__(self, rank):
+        super().__init__(name="bpf-local-rank-%d" % rank, daemon=True)
+        self.jobs = queue.Queue()
+        self.start()
+
+    def run(self):
+        while True:
+            job = self.jobs.get()
+            if job is None:
+                return
+            fn, box, done = job
+            try:
+                box.append((True, fn()))
+            except BaseException as err:  # handed to the caller of run()
+                box.append((False, err))
+            done.set()
+
+    def submit(self, fn):
+        box, done = [], threading.Event()
+        self.jobs.put((fn, box, done))
+        return box, done
+
+
+class LocalShardedFilter:
+    """pfs[r]: the pf.ParticleFilter of rank r, each on an engine of its own, created with the GLOBAL min / max sample
+    counts and holding rank r's contiguous slice (or nothing yet, when an init follows)."""
+
+    def __init__(self, pfs, first_window=4096, timeout_ms=None, kld_count=None, connect=True):
+        self.pfs = list(pfs)
+        self.world = len(self.pfs)
+        self.engines = [p.e for p in self.pfs]
+        self.lib = self.engines[0].lib
+        self.max_global = self.pfs[0].max_samples
+        self._workers = [_Worker(r) for r in range(self.world)]
+        self._first_window = first_window
+        self.window_hint = [first_window] * self.world
+        self.sample_count = 0
+        self.leaf_count = self.bin_count = 0
+        self.windows_used = 0
+        self.cdf_miss = False
+        self.stats_route = self.tree_route = None
+        self.counts = [0] * self.world
+        if kld_count is not None:
+            for p in self.pfs:
+                p.setKldCount(int(kld_count))
+        modes = [p.getKldCount() for p in self.pfs]
+        if len(set(modes)) != 1:
+            raise ValueError("LocalShardedFilter: the ranks use different KLD count modes %s" % modes)
+        self.kld_count = modes[0]
+        if timeout_ms is not None:
+            self.set_timeout_ms(timeout_ms)
+        if connect:
+            self.connect()
+
+    # ---- the world
+    def connect(self):
+        """bpf_shard_connect_local over the engines (again after a broken world: the old one is released)."""
+        arr = (C.c_void_p * self.world)(*[e.h for e in self.engines])
+        rc = self.lib.bpf_shard_connect_local(arr, self.world, 0)
+        if rc != 0:
+            raise BpfError(rc, "bpf_shard_connect_local: " + self.lib.bpf_error_string(rc).decode())
+
+    def set_timeout_ms(self, ms):
+        for e in self.engines:
+            e.check(self.lib.bpf_shard_mailbox_set_timeout_ms(e.h, int(ms)))
+
+    def exchange_mode(self):
+        out = []
+        for e in self.engines:
+            m = C.c_int(-1)
+            e.check(self.lib.bpf_shard_exchange_mode(e.h, C.byref(m)))
+            out.append(m.value)
+        return out
+
+    def exchange_counts(self):
+        out = []
+        for e in self.engines:
+            n = C.c_longlong(-1)
+            e.check(self.lib.bpf_shard_exchange_count(e.h, C.byref(n)))
+            out.append(n.value)
+        return out
+
+    def shutdown(self):
+        for e in self.engines:
+            if e.h:
+                self.lib.bpf_shard_shutdown(e.h)
+
+    def close(self):
+        """Ends the worker threads (the engines stay with their owner)."""
+        for w in self._workers:
+            w.jobs.put(None)
+        for w in self._workers:
+            w.join()
+        self._workers = []
+
+    # ---- fan out and join
+    def run(self, fn, ranks=None):
+        """fn(rank) on the worker thread of every rank in `ranks` (default: all) at once; the results in that order.
+        An exception raised on a worker is raised here (the first one by rank) after all have finished."""
+        ranks = list(range(self.world)) if ranks is None else list(ranks)
+        pending = [self._workers[r].submit(lambda r=r: fn(r)) for r in ranks]
+        out = []
+        for box, done in pending:
+            done.wait()
+            out.append(box[0])
+        for ok, val in out:
+            if not ok:
+                raise val
+        return [val for _, val in out]
+
+    def for_each_rank(self, fn):
+        """fn(rank, pf) on every rank's thread: map / scanner / model set-up of the engines, in parallel."""
+        return self.run(lambda r: fn(r, self.pfs[r]))
+
+    def codes(self, call, ranks=None):
+        """call(rank, engine handle, lib) -> status code, on the ranks' threads; the codes as they came back."""
+        return self.run(lambda r: int(call(r, self.engines[r].h, self.lib)), ranks)
+
+    def _collective(self, call):
+        rcs = self.codes(call)
+        if len(set(rcs)) != 1:
+            raise RuntimeError("LocalShardedFilter: the ranks' statuses differ: %s" % rcs)
+        if rcs[0] != 0:
+            self.engines[0].check(rcs[0])
+
+    # ---- starting the set
+    def _even_share(self, n):
+        W = self.world
+        self.counts = [(n * (q + 1)) // W - (n * q) // W for q in range(W)]
+        self.sample_count = n
+
+    def _first(self, r):
+        return sum(self.counts[:r])
+
+    def _after_init(self):
+        self._even_share(self.max_global)
+        self.leaf_count, self.bin_count = self._global_leaf_count()
+        self.window_hint = [self._first_window] * self.world
+        self.windows_used = 0
+        r = C.c_int()
+        self.engines[0].check(self.lib.bpf_shard_tree_last_route(self.engines[0].h, C.byref(r)))
+        self.tree_route = TREE_ROUTES.get(r.value)
+
+    def init_with_gaussian(self, mean, rotation, sigma):
+        m, rot, d = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (mean, rotation, sigma))
+        assert m.size == 3 and rot.size == 9 and d.size == 3
+        self._collective(lambda r, h, lib: lib.bpf_shard_init_with_gaussian_all(
+            h, m.ctypes.data_as(_dp), rot.ctypes.data_as(_dp), d.ctypes.data_as(_dp)))
+        self._after_init()
+
+    def init_with_random_poses(self):
+        self._collective(lambda r, h, lib: lib.bpf_shard_init_with_random_poses_all(h))
+        self._after_init()
+
+    def load(self, slices, tree=True):
+        """Slices loaded by hand: slices[r] = [n_r, 4] samples of rank r (n_r = 0 allowed), in global order.  tree: the
+        leaf and bin counts of the global set's tree come over the exchange (the systematic resampler reads them
+        before the first resample); without it they read 0 until a resample installs them."""
+        assert len(slices) == self.world
+        self.counts = [int(np.asarray(s).shape[0]) for s in slices]
+        self.sample_count = sum(self.counts)
+        total = self.sample_count
+
+        def put(r, pf):
+            if self.counts[r] > 0:
+                return pf.initWithSamples(np.asarray(slices[r], dtype=np.float64).reshape(-1, 4))
+            # a shard without samples (bpf_pf_set_samples takes none): adopt an empty slice of the global set
+            pf.e.check(self.lib.bpf_shard_adopt_dev(pf.e.h, None, None, None, 0, total, 0, 0))
+        self.for_each_rank(put)
+        self.leaf_count, self.bin_count = self._global_leaf_count() if tree else (0, 0)
+        self.window_hint = [self._first_window] * self.world
+
+    def restore(self, counts, leaf_count=0):
+        """The shards were put back by pf.restore(): reset the bookkeeping (ShardedFilter.restore)."""
+        self.counts = list(counts)
+        self.sample_count = sum(counts)
+        self.leaf_count = leaf_count
+
+    def _global_leaf_count(self):
+        got = [None] * self.world
+
+        def call(r, h, lib):
+            a, b = C.c_int(), C.c_int()
+            rc = lib.bpf_shard_global_leaf_count(h, C.byref(a), C.byref(b))
+            got[r] = (a.value, b.value)
+            return rc
+        self._collective(call)
+        if len(set(got)) != 1:
+            raise RuntimeError("LocalShardedFilter: the ranks disagree on the global tree: %s" % got)
+        return got[0]
+
+    # ---- the steps
+    def update_action(self, odom, data):
+        """odom: the pf.Odom of every rank (a list), or one pf.Odom whose model every engine already carries."""
+        def call(r, h, lib):
+            return lib.bpf_shard_update_action(h, data.pose.ctypes.data_as(_dp), data.delta.ctypes.data_as(_dp),
+                                               data.absolute_motion.ctypes.data_as(_dp), self._first(r),
+                                               self.sample_count)
+        self._collective(call)
+
+    def update_sensor(self, data):
+        """pf.PlanarData (beam skipping of the prob model included) or pf.PointCloudData."""
+        n = self.sample_count
+        if hasattr(data, "points_"):
+            pts = data.points_
+            ptr = pts.ctypes.data_as(C.POINTER(C.c_float))
+            return self._collective(lambda r, h, lib: lib.bpf_shard_update_sensor_cloud(h, ptr, pts.shape[0], n))
+        ranges, angles = data.pointers()
+        self._collective(lambda r, h, lib: lib.bpf_shard_update_sensor_planar(h, ranges, angles, data.range_count_,
+                                                                               data.range_max_, n))
+
+    def update_resample(self):
+        got = [None] * self.world
+
+        def call(r, h, lib):
+            m, leaf, bins = C.c_int(self.sample_count), C.c_int(self.leaf_count), C.c_int(0)
+            wins, hint, miss = C.c_int(0), C.c_int(self.window_hint[r]), C.c_int(0)
+            rc = lib.bpf_shard_update_resample(h, C.byref(m), C.byref(leaf), C.byref(bins), C.byref(wins), C.byref(hint),
+                                               C.byref(miss))
+            got[r] = (m.value, leaf.value, bins.value, wins.value, hint.value, miss.value)
+            return rc
+        self._collective(call)
+        if len(set(g[:3] for g in got)) != 1:
+            raise RuntimeError("LocalShardedFilter: the ranks resampled to different sets: %s" % got)
+        m, self.leaf_count, self.bin_count, self.windows_used = got[0][:4]
+        self.window_hint = [g[4] for g in got]
+        self.cdf_miss = any(g[5] for g in got)
+        self._even_share(m)
+
+    # ---- the global pose and the particle cloud
+    def compute_cluster_stats(self):
+        """(cluster_count, set_mean[3], set_cov[5]) of the global set, the same bits on every rank."""
+        got = [None] * self.world
+
+        def call(r, h, lib):
+            n, route = C.c_int(), C.c_int()
+            mean, cov = np.zeros(3), np.zeros(5)
+            rc = lib.bpf_shard_compute_cluster_stats(h, C.byref(n), mean.ctypes.data_as(_dp), cov.ctypes.data_as(_dp),
+                                                     C.byref(route))
+            got[r] = (n.value, mean, cov, route.value)
+            return rc
+        self._collective(call)
+        for g in got[1:]:
+            if g[0] != got[0][0] or g[1].tobytes() != got[0][1].tobytes() or g[2].tobytes() != got[0][2].tobytes():
+                raise RuntimeError("LocalShardedFilter: the ranks' statistics differ")
+        self.stats_route = STATS_ROUTES.get(got[0][3])
+        return got[0][:3]
+
+    def get_cluster(self, k):
+        """(weight, mean[3], count, cov[5]) of cluster k of the global set, None past the last cluster."""
+        self.compute_cluster_stats()
+        return self.pfs[0].getClusterStats(k)
+
+    def get_max_weight_pose(self):
+        got = [None] * self.world
+
+        def call(r, h, lib):
+            w, pose = C.c_double(), np.zeros(3)
+            rc = lib.bpf_shard_get_max_weight_pose(h, C.byref(w), pose.ctypes.data_as(_dp))
+            got[r] = (w.value, pose)
+            return rc
+        self._collective(call)
+        for g in got[1:]:
+            if g[0] != got[0][0] or g[1].tobytes() != got[0][1].tobytes():
+                raise RuntimeError("LocalShardedFilter: the ranks' max-weight poses differ")
+        return got[0]
+
+    def get_pose_array(self, root=0, first=0, stride=1):
+        """[count, 7] float64 rows of the global samples first, first + stride, ... as rank `root` receives them
+        (root = -1: every rank receives; rank 0's copy is returned after they were compared)."""
+        if not -1 <= root < self.world:
+            raise ValueError("get_pose_array: root in [-1, world)")
+        n = self.sample_count
+        room = (n - first + stride - 1) // stride if stride >= 1 and 0 <= first < n else 0
+        got = [None] * self.world
+
+        def call(r, h, lib):
+            receives = root < 0 or root == r
+            out = np.empty((max(room, 1), 7), dtype=np.float64) if receives else None
+            cnt = C.c_int()
+            rc = lib.bpf_shard_get_pose_array(h, int(root), int(first), int(stride),
+                                              out.ctypes.data_as(_dp) if receives else None, int(room), C.byref(cnt))
+            got[r] = out[:cnt.value] if receives and rc == 0 else None
+            return rc
+        self._collective(call)
+        if root >= 0:
+            return got[root]
+        for g in got[1:]:
+            if g.tobytes() != got[0].tobytes():
+                raise RuntimeError("LocalShardedFilter: the ranks' pose arrays differ")
+        return got[0]
+
+    def selftest(self, rounds=1):
+        """bpf_shard_local_selftest on every rank."""
+        self._collective(lambda r, h, lib: lib.bpf_shard_local_selftest(h, int(rounds)))
+
+    def set_random_pose_generator(self, mode):
+        for p in self.pfs:
+            p.setRandomPoseGenerator(mode)
+
+    def set_uniform_pose_check(self, threshold, multiplier, scoring=0):
+        for p in self.pfs:
+            p.setUniformPoseCheck(threshold, multiplier, scoring)
+
+    def rank_states(self):
+        return [p.getState() for p in self.pfs]
+
+    def rng_states(self):
+        return [p.getRngState() for p in self.pfs]
+
+    def local_sets(self):
+        """The ranks' slices on the host, [n_r, 4] each, in rank order."""
+        return self.for_each_rank(lambda r, pf: pf.getCurrentSet().samples)
+
+    def state(self):
+        st = self.pfs[0].getState()
+        return ShardedState(sample_count=self.sample_count, local_count=st.sample_count, leaf_count=self.leaf_count,
+                            bin_count=self.bin_count, converged=st.converged,
+                            percent_converged=st.percent_converged, w_slow=st.w_slow, w_fast=st.w_fast,
+                            total=st.total, cdf_miss=self.cdf_miss, windows=self.windows_used)

@@ -7,17 +7,24 @@
 //   badger_amcl_amd::ParticleFilter    <- ParticleFilter    (include/amcl/pf/particle_filter.h:92-184)
 //   badger_amcl_amd::PFSample / PFSampleSet                 (include/amcl/pf/particle_filter.h:41-87)
 //   badger_amcl_amd::OdomData / Odom   <- OdomData / Odom   (include/amcl/sensors/odom.h:43-90)
+//   badger_amcl_amd::ShardedParticleFilter       one rank of a filter sharded over several engines (one process each)
+//   badger_amcl_amd::LocalShardedParticleFilter  all ranks of it in this process (bpf_shard_connect_local)
 //
 // Same method names, argument meaning and return conventions (false / 0.0 on the reference's
 // silent failures); conditions the reference asserts on or hangs in surface as std::runtime_error.
 // No Eigen / ROS / PCL dependency: poses are plain double[3].
 #pragma once
 #include <array>
+#include <condition_variable>
 #include <cstdint>
 #include <cmath>
+#include <exception>
+#include <functional>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../badger_pf.h"
@@ -514,7 +521,14 @@ public:
     e().check(bpf_shard_compute_cluster_stats(e().get(), &count, nullptr, nullptr, &route_));
     return pf_->getClusterStats(cidx, weight, mean);
   }
+  // instead of bootstrap(): this rank's engine was connected from outside (bpf_shard_connect_local)
+  void joined(int rank, int world)
+  {
+    rank_ = rank;
+    world_ = world;
+  }
   void shutdown() { e().check(bpf_shard_shutdown(e().get())); }
+  ParticleFilter& filter() { return *pf_; }
   int globalSampleCount() const { return global_count_; }
   int leafCount() const { return leaf_count_; }
   int binCount() const { return bin_count_; }
@@ -544,6 +558,203 @@ private:
   long long global_first_;
   int bin_count_ = 0, windows_ = 0, cdf_miss_ = 0, route_ = 0, tree_route_ = 0;
   int rank_ = 0, world_ = 1;
+};
+
+// The same filter with ALL its ranks in this process -- a single-process node with several engines (badger_pf.h,
+// bpf_shard_connect_local).  Owns the W rank filters and W worker threads, one per engine; every member below fans
+// out to the workers, each of which makes the collective call for its rank (the ranks meet inside the library at the
+// exchanges), and joins them.  Same member names as ShardedParticleFilter.  When some ranks fail and others do not it
+// throws "the ranks' statuses differ"; when all fail, rank 0's error; otherwise it returns rank 0's figures.  The
+// object itself is driven from one thread.
+class LocalShardedParticleFilter
+{
+public:
+  // pfs[r]: rank r's filter on an engine of its own, created with the GLOBAL min / max sample counts.  counts[r]:
+  // samples of the slice loaded into it by hand (leaf_count: of the whole set's tree, as for ShardedParticleFilter);
+  // empty when initWithGaussian / initWithRandomPoses follows.
+  explicit LocalShardedParticleFilter(std::vector<std::shared_ptr<ParticleFilter>> pfs, std::vector<int> counts = {},
+                                      int leaf_count = 1, int first_window = 4096)
+  {
+    const int W = (int)pfs.size();
+    if (W < 1 || (!counts.empty() && (int)counts.size() != W))
+      throw std::invalid_argument("LocalShardedParticleFilter: one filter (and one count) per rank");
+    std::vector<bpf_engine*> engines;
+    for (auto& p : pfs)
+      engines.push_back(p->engine().get());
+    const int rc = bpf_shard_connect_local(engines.data(), W, 0);
+    if (rc != BPF_OK)
+      throw std::runtime_error(std::string("bpf_shard_connect_local: ") + bpf_error_string(rc));
+    long long total = 0, first = 0;
+    for (int c : counts)
+      total += c;
+    for (int r = 0; r < W; ++r)
+    {
+      ranks_.emplace_back(new ShardedParticleFilter(pfs[(size_t)r], (int)total, leaf_count, first_window, first));
+      ranks_.back()->joined(r, W);
+      first += counts.empty() ? 0 : counts[(size_t)r];
+    }
+    workers_.resize((size_t)W);
+    for (int r = 0; r < W; ++r)
+      workers_[(size_t)r].thread = std::thread([this, r] { work(r); });
+  }
+  ~LocalShardedParticleFilter()
+  {
+    {
+      std::lock_guard<std::mutex> lk(m_);
+      stop_ = true;
+    }
+    wake_.notify_all();
+    for (auto& w : workers_)
+      w.thread.join();
+  }
+  LocalShardedParticleFilter(const LocalShardedParticleFilter&) = delete;
+  LocalShardedParticleFilter& operator=(const LocalShardedParticleFilter&) = delete;
+
+  // fn(rank, filter of that rank) on every rank's thread at once: map / scanner / model set-up, dumps
+  void forEachRank(const std::function<void(int, ParticleFilter&)>& fn)
+  {
+    fanOut([&](int r) { fn(r, ranks_[(size_t)r]->filter()); });
+  }
+  void initWithGaussian(const std::array<double, 3>& mean, const std::array<double, 9>& rotation,
+                        const std::array<double, 3>& sigma)
+  {
+    fanOut([&](int r) { ranks_[(size_t)r]->initWithGaussian(mean, rotation, sigma); });
+  }
+  void initWithRandomPoses()
+  {
+    fanOut([&](int r) { ranks_[(size_t)r]->initWithRandomPoses(); });
+  }
+  bool updateAction(std::shared_ptr<OdomData> data)
+  {
+    fanOut([&](int r) { ranks_[(size_t)r]->updateAction(data); });
+    return true;
+  }
+  bool updateSensor(std::shared_ptr<PlanarData> data)
+  {
+    fanOut([&](int r) { ranks_[(size_t)r]->updateSensor(data); });
+    return true;
+  }
+  bool updateSensorCloud(const float* xyz, int n)
+  {
+    fanOut([&](int r) { ranks_[(size_t)r]->updateSensorCloud(xyz, n); });
+    return true;
+  }
+  void updateResample()
+  {
+    fanOut([&](int r) { ranks_[(size_t)r]->updateResample(); });
+    for (auto& s : ranks_)
+      if (s->globalSampleCount() != ranks_[0]->globalSampleCount() || s->leafCount() != ranks_[0]->leafCount() ||
+          s->binCount() != ranks_[0]->binCount())
+        throw std::runtime_error("LocalShardedParticleFilter: the ranks resampled to different sets");
+  }
+  void getMaxWeightPose(double* max_weight_out, std::array<double, 3>* max_pose)
+  {
+    std::vector<double> w(ranks_.size());
+    std::vector<std::array<double, 3>> p(ranks_.size());
+    fanOut([&](int r) { ranks_[(size_t)r]->getMaxWeightPose(&w[(size_t)r], &p[(size_t)r]); });
+    *max_weight_out = w[0];
+    *max_pose = p[0];
+  }
+  bool getClusterStats(int cidx, double* weight, std::array<double, 3>* mean)
+  {
+    std::vector<double> w(ranks_.size());
+    std::vector<std::array<double, 3>> m(ranks_.size());
+    std::vector<char> ok(ranks_.size());
+    fanOut([&](int r) { ok[(size_t)r] = ranks_[(size_t)r]->getClusterStats(cidx, &w[(size_t)r], &m[(size_t)r]); });
+    if (ok[0])
+    {
+      *weight = w[0];
+      *mean = m[0];
+    }
+    return ok[0] != 0;
+  }
+  // Node::publishParticleCloud's poses of the GLOBAL set, received by rank 0's engine
+  bool getPoseArray(std::vector<double>* poses7, long long first = 0, int stride = 1)
+  {
+    fanOut([&](int r) { ranks_[(size_t)r]->getPoseArray(0, r == 0 ? poses7 : nullptr, first, stride); });
+    return true;
+  }
+  void shutdown()
+  {
+    for (auto& s : ranks_)
+      s->shutdown();
+  }
+  ShardedParticleFilter& rank(int r) { return *ranks_[(size_t)r]; }
+  int world() const { return (int)ranks_.size(); }
+  int globalSampleCount() const { return ranks_[0]->globalSampleCount(); }
+  int leafCount() const { return ranks_[0]->leafCount(); }
+  int binCount() const { return ranks_[0]->binCount(); }
+  int windowsUsed() const { return ranks_[0]->windowsUsed(); }
+  int statsRoute() const { return ranks_[0]->statsRoute(); }
+  bool cdfMiss() const
+  {
+    for (auto& s : ranks_)
+      if (s->cdfMiss())
+        return true;
+    return false;
+  }
+
+private:
+  struct Worker
+  {
+    std::thread thread;
+    bool has_job = false;
+    std::exception_ptr error;
+  };
+  void work(int r)
+  {
+    std::unique_lock<std::mutex> lk(m_);
+    for (;;)
+    {
+      wake_.wait(lk, [&] { return stop_ || workers_[(size_t)r].has_job; });
+      if (stop_)
+        return;
+      lk.unlock();
+      std::exception_ptr err;
+      try
+      {
+        job_(r);
+      }
+      catch (...)
+      {
+        err = std::current_exception();
+      }
+      lk.lock();
+      workers_[(size_t)r].error = err;
+      workers_[(size_t)r].has_job = false;
+      if (--pending_ == 0)
+        done_.notify_all();
+    }
+  }
+  void fanOut(const std::function<void(int)>& fn)
+  {
+    std::unique_lock<std::mutex> lk(m_);
+    job_ = fn;
+    pending_ = (int)workers_.size();
+    for (auto& w : workers_)
+    {
+      w.has_job = true;
+      w.error = nullptr;
+    }
+    wake_.notify_all();
+    done_.wait(lk, [&] { return pending_ == 0; });
+    int failed = 0;
+    for (auto& w : workers_)
+      failed += w.error ? 1 : 0;
+    if (failed == 0)
+      return;
+    if (failed != (int)workers_.size())
+      throw std::runtime_error("LocalShardedParticleFilter: the ranks' statuses differ (" + std::to_string(failed) +
+                               " of " + std::to_string(workers_.size()) + " failed)");
+    std::rethrow_exception(workers_[0].error);
+  }
+  std::vector<std::unique_ptr<ShardedParticleFilter>> ranks_;
+  std::vector<Worker> workers_;
+  std::mutex m_;
+  std::condition_variable wake_, done_;
+  std::function<void(int)> job_;
+  int pending_ = 0;
+  bool stop_ = false;
 };
 
 }  // namespace badger_amcl_amd

@@ -727,7 +727,8 @@ int bpf_shard_mailbox_window(bpf_engine* e, void** window_dev, int* stride);
 enum
 {
   BPF_SHARD_EXCHANGE_MAILBOX = 1,
-  BPF_SHARD_EXCHANGE_RCCL = 2
+  BPF_SHARD_EXCHANGE_RCCL = 2,
+  BPF_SHARD_EXCHANGE_LOCAL = 3
 };
 enum
 {
@@ -737,6 +738,34 @@ enum
 int bpf_shard_bootstrap(bpf_engine* e, int rank, int world, const char* host_port, long long max_window, int flags,
                         int* mode_out);
 int bpf_shard_shutdown(bpf_engine* e);
+/* All ranks of ONE sharded filter inside this process (a single-process node with several engines): engines[r] becomes
+ * rank r of `world`.  One thread calls it, once; no sockets, no IPC handles, no RCCL.  1 <= world <= 16, the engines
+ * distinct, each after bpf_pf_create with the same (GLOBAL) min / max sample counts, on one device or on devices with
+ * peer access both ways (which the call enables); flags must be 0.  Anything else returns BPF_ERR_INVALID_ARGUMENT or
+ * BPF_ERR_UNSUPPORTED (no peer access) and leaves every engine as it was.  A mailbox or RCCL set-up on the engines is
+ * released first, as bpf_shard_bootstrap does; an earlier local world too.
+ * Afterwards every collective one-call form (bpf_shard_update_*, bpf_shard_*_all, bpf_shard_compute_cluster_stats,
+ * bpf_shard_get_*, bpf_shard_global_leaf_count) works unchanged, with this calling convention: all `world` ranks
+ * enter the same call concurrently, ONE HOST THREAD PER ENGINE (an engine itself stays single-threaded).  The ranks
+ * meet at a host barrier inside every exchange; the data moves by one launch per rank that reads the peers' buffers,
+ * ordered by events between the engines' streams -- no kernel waits for another rank.  bpf_shard_exchange_count counts
+ * as on the RCCL path.  A rank that does not arrive within bpf_shard_mailbox_set_timeout_ms (default 5 s) breaks the
+ * world: the waiting ranks return BPF_ERR_EXCHANGE with their destinations untouched, and every later exchange fails at
+ * once until the next bpf_shard_connect_local.  bpf_shard_shutdown and bpf_destroy detach an engine (the world is
+ * broken for the ranks that stay); the last one out frees the world. */
+int bpf_shard_connect_local(bpf_engine* const* engines, int world, int flags);
+/* *mode_out: 0 (no exchange set up), BPF_SHARD_EXCHANGE_MAILBOX, _RCCL or _LOCAL */
+int bpf_shard_exchange_mode(const bpf_engine* e, int* mode_out);
+/* Self-test of the local transport (collective, like bpf_shard_mailbox_selftest): ragged int64 gathers with one rank
+ * contributing nothing and spans off the 16-byte grid, f64 all-gathers, int64 and int32 all-reduces in place at every
+ * offset within 16 bytes, each at 0, 1, 255, 256, 257 and 6 * 4096 + 3 words, every cell and the guard words around
+ * the destinations compared on the host.  BPF_ERR_EXCHANGE on a difference (the world is then broken). */
+int bpf_shard_local_selftest(bpf_engine* e, int rounds);
+/* Measurement (tools/time_local_world.py): `reps` exchanges of one kind back to back over the engine's collective
+ * provider (the local world, or RCCL after the bootstrap's fallback), the host's wall time per exchange between two
+ * stream synchronisations.  kind 0: f64 all-gather of `words` words per rank (1 = the totals); kind 1: int64
+ * all-reduce(sum) of `words` words (6 * 4096 = a draw window).  Collective: every rank, the same arguments. */
+int bpf_shard_exchange_probe(bpf_engine* e, int kind, long long words, int reps, double* ms_per_exchange_out);
 /* The sharded sensor update and resample as one call each, over whichever exchange bpf_shard_bootstrap (or
  * bpf_shard_mailbox_connect) set up; arguments as bpf_shard_mailbox_update_sensor_planar / _update_resample, with the
  * CDF-miss flag word owned by the engine (*cdf_miss_out, nullable, reads it back).
