@@ -639,6 +639,7 @@ int bpf_pf_update_sensor_cloud(bpf_engine* e, const float* points_xyz, int n_poi
   SampleSet& s = e->sets[e->cur];
   const int n = e->sample_count;
   e->weights_overwritten();
+  e->weights_changed();  // (from here on, also when a later stage fails)
   int rc = score_cloud(e, s.dev(), n, points_xyz, n_points);
   if (rc != BPF_OK)
     return rc;

@@ -22,8 +22,8 @@ int bpf_pf_create(bpf_engine* e, int min_samples, int max_samples, double alpha_
   for (int k = 0; k < 2; ++k)
     HIPCHK(e, e->sets[k].reserve((size_t)max_samples));
   // ctor state (particle_filter.cpp:62-89): max_samples particles at the origin, weight 1/max
-  e->cur = 0;
-  e->sample_count = max_samples;
+  e->filter_created(max_samples);
+  e->snap_count = 0;  // an earlier filter's snapshot is not this one's to restore
   HIPCHK(e, hipMemsetAsync(e->sets[0].x.p, 0, (size_t)max_samples * sizeof(double), e->stream));
   HIPCHK(e, hipMemsetAsync(e->sets[0].y.p, 0, (size_t)max_samples * sizeof(double), e->stream));
   HIPCHK(e, hipMemsetAsync(e->sets[0].th.p, 0, (size_t)max_samples * sizeof(double), e->stream));
@@ -31,7 +31,6 @@ int bpf_pf_create(bpf_engine* e, int min_samples, int max_samples, double alpha_
                      1.0 / max_samples, max_samples);
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipMemsetAsync(e->d_scalars.p, 0, sizeof(FilterScalars), e->stream));
-  e->filter_created();
   e->window_hint = 4096;
   e->have_pf = true;
   return BPF_OK;
@@ -168,6 +167,7 @@ int bpf_pf_snapshot(bpf_engine* e)
   e->snap_count = e->sample_count;
   e->snap_leaf = e->tree.leaf_count;
   e->snap_bins = e->tree.bin_count;
+  e->snap_kld_mode = e->kld_count_mode;
   return BPF_OK;
 }
 
@@ -180,7 +180,9 @@ int bpf_pf_restore(bpf_engine* e)
   hipLaunchKernelGGL(k_copy4, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, e->sets[e->cur].dev(),
                      e->snap.dev(), n);
   HIPCHK(e, hipGetLastError());
-  e->new_set(n, false, e->tree.counted(e->snap_leaf, e->snap_bins));
+  // (counts taken in the other KLD count mode are not this mode's: computed again when they are needed)
+  e->new_set(n, false, e->snap_kld_mode == e->kld_count_mode ? e->tree.counted(e->snap_leaf, e->snap_bins)
+                                                              : e->tree.pending());
   return BPF_OK;
 }
 

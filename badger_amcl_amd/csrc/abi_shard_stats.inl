@@ -14,6 +14,7 @@ void install_device_stats(bpf_engine* e, const StatsResult& r)
   e->clusters.clear();
   e->stats_clusters_fetched = false;
   e->stats_on_device = true;
+  e->stats_own_set = false;  // the GLOBAL set's: no host evaluation of this rank's slice may stand in for them
   e->stats_epoch = e->set_epoch;
 }
 

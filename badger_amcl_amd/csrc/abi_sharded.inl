@@ -134,7 +134,10 @@ int bpf_shard_normalize_dev(bpf_engine* e, const void* totals_dev, int world, in
   const int n = e->sample_count;
   const int nb = std::max(1, blocks_for(n, BPF_RED_TILE));
   HIPCHK(e, e->d_tile_sums.reserve((size_t)nb));
-  e->weights_changed();  // rescaled
+  // rescaled: a CDF, its subsample or tile sums left for the weights before this call (a normalisation without a
+  // scoring stage in between) describe them no longer; the launch below leaves its own
+  e->weights_overwritten();
+  e->weights_changed();
   // totals that are this engine's mailbox slots: the kernel itself waits for the peers' posts of this update
   MailboxDev wait{};
   const double* fold = nullptr;

@@ -53,6 +53,7 @@ int stats_block_evaluate(bpf_engine* e, ParticlesDev p, int n, int* status)
     e->clusters.clear();
     e->stats_clusters_fetched = false;
     e->stats_on_device = true;
+    e->stats_own_set = false;  // (the caller knows whose set this was: compute_cluster_stats_device says so)
     e->stats_epoch = e->set_epoch;
   }
   *status = e->h_stats_block.p[1];
@@ -78,6 +79,7 @@ int compute_cluster_stats_device(bpf_engine* e, bool* handled)
       return rcb;
     if (status == 0)
     {
+      e->stats_own_set = true;
       *handled = true;
       return BPF_OK;
     }
@@ -163,10 +165,13 @@ int compute_cluster_stats_device(bpf_engine* e, bool* handled)
   e->clusters.clear();
   e->stats_clusters_fetched = false;
   e->stats_on_device = true;
+  e->stats_own_set = true;
   e->stats_epoch = e->set_epoch;
   *handled = true;
   return BPF_OK;
 }
+
+int compute_cluster_stats_host(bpf_engine* e);
 
 // the cluster array itself, only when somebody asks for a cluster
 int fetch_device_clusters(bpf_engine* e)
@@ -182,6 +187,31 @@ int fetch_device_clusters(bpf_engine* e)
     HIPCHK(e, hipStreamSynchronize(e->stream));
   }
   e->stats_clusters_fetched = true;
+  // The device sums are 32.96 fixed point (kernels_stats.hpp): every term is cut below 2^-96, so a cluster's sums are
+  // off by up to count * 2^-96 absolute.  Where that is not below 1e-12 of the cluster's weight (a set scored several
+  // times without a resample, or once with the prob model) its means have lost their digits -- NaN where the weight
+  // sum was cut to 0 -- and the CLUSTERS are evaluated again on the host, in the reference's own arithmetic.  Only
+  // for statistics of the engine's own set: a sharded filter's describe the global set, of which this engine holds a
+  // slice (their light clusters stay as the device left them).  The set's own mean / covariance and the heaviest
+  // cluster stay the device's, so what computeClusterStats and getMaxWeightPose answer does not depend on whether a
+  // getClusterStats came first.
+  if (!e->stats_own_set)
+    return BPF_OK;
+  for (const bpf_cluster& c : e->clusters)
+    if (c.count > 0 && !(c.weight >= 4.0e12 * (double)c.count * 1.2621774483536189e-29))
+    {
+      double mean[3], cov[5];
+      std::memcpy(mean, e->set_mean, sizeof(mean));
+      std::memcpy(cov, e->set_cov, sizeof(cov));
+      const int rc = compute_cluster_stats_host(e);  // e->clusters, in the same order (labels are creation order)
+      std::memcpy(e->set_mean, mean, sizeof(mean));
+      std::memcpy(e->set_cov, cov, sizeof(cov));
+      e->stats_on_device = true;
+      e->stats_clusters_fetched = true;
+      if (rc == BPF_OK && (int)e->clusters.size() != e->stats_cluster_count)
+        return e->fail(BPF_ERR_HIP, "host and device cluster counts differ (internal error)");
+      return rc;
+    }
   return BPF_OK;
 }
 
@@ -217,16 +247,20 @@ int host_cluster_stats(bpf_engine* e, const double* s, int n, KdHistogram& hist,
     a.weight += w;
     a.m[0] += w * p[0];
     a.m[1] += w * p[1];
-    a.m[2] += w * std::cos(p[2]);
-    a.m[3] += w * std::sin(p[2]);
+    // cos and sin of one argument: g++ -O2 (the reference's build, and the oracle's) evaluates the pair with ONE
+    // sincos call, whose sine differs from sin()'s by an ulp for a few arguments; hipcc's host pass keeps two calls
+    double sn, cs;
+    ::sincos(p[2], &sn, &cs);
+    a.m[2] += w * cs;
+    a.m[3] += w * sn;
     for (int j = 0; j < 2; ++j)
       for (int k = 0; k < 2; ++k)
         a.c[2 * j + k] += w * p[j] * p[k];
     weight += w;
     m[0] += w * p[0];
     m[1] += w * p[1];
-    m[2] += w * std::cos(p[2]);
-    m[3] += w * std::sin(p[2]);
+    m[2] += w * cs;
+    m[3] += w * sn;
     for (int j = 0; j < 2; ++j)
       for (int k = 0; k < 2; ++k)
         c[2 * j + k] += w * p[j] * p[k];
@@ -271,6 +305,11 @@ int compute_cluster_stats(bpf_engine* e)
     if (handled)
       return BPF_OK;
   }
+  return compute_cluster_stats_host(e);
+}
+
+int compute_cluster_stats_host(bpf_engine* e)
+{
   e->stats_on_device = false;
   const int n = e->sample_count;
   std::vector<double> s((size_t)n * 4);

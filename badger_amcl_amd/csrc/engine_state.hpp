@@ -139,9 +139,10 @@ struct FieldScan
 // What the last weight pass left behind for the passes that follow it.  Invariant: a field that is set describes the
 // weights of the CURRENT set (sets[cur].w, sample_count of them) as they are now; whoever rewrites weights -- of any
 // set, the buffers are shared -- drops them first (bpf_engine::weights_overwritten and the transitions on top of it),
-// and only the launch that produced a buffer sets its field.  The two flags are not dropped: cdf_guide_valid is read
-// only behind a build_cdf that has either found cdf_ready_n set by the producer of both or rewritten it, and
-// shard_cdf_valid is honoured only together with cdf_ready_n == sample_count.
+// and only the launch that produced a buffer sets its field.  cdf_guide_valid is not dropped: it is read only behind
+// a build_cdf that has either found cdf_ready_n set by the producer of both or rewritten it.  shard_cdf_valid goes
+// with the CDF it describes: a single-filter update that leaves a CDF of its own for the same n must not be taken
+// for the sharded one (its sum is not in scalars[7]).
 struct WeightCaches
 {
   int fused_partials = 0;        // > 0: the last scoring launch left that many per-block weight partials
@@ -154,6 +155,7 @@ struct WeightCaches
   {
     fused_partials = 0;
     tile_sums_n = cdf_ready_n = cdf_coarse_n = -1;
+    shard_cdf_valid = false;
   }
   // k_normalize_cdf / k_normalize_gathered_cdf: the normalised weights' CDF and its subsample (the tile sums went
   // into them); `sharded`: it is the local CDF a bpf_shard_build_cdf may take
@@ -338,6 +340,7 @@ struct bpf_engine
   SampleSet scratch;  // Seam A host-buffer path
   SampleSet snap;
   int snap_count = 0, snap_leaf = 0, snap_bins = 0;
+  int snap_kld_mode = 0;  // the KLD count mode snap_leaf was counted in
 
   // ---- w_diff > 0: random free-space poses (Node::randomFreeSpacePose) and the draw chain
   int random_pose_mode = BPF_RANDOM_POSE_NONE;
@@ -473,6 +476,7 @@ struct bpf_engine
   // ---- cluster statistics on the device (kernels_stats.hpp)
   bool stats_host = false;          // BPF_OPT_STATS_HOST: the bit-exact host evaluation instead
   bool stats_on_device = false;     // the current statistics came from the device
+  bool stats_own_set = false;       // ... and describe this engine's own set (not a sharded filter's global one)
   bool stats_clusters_fetched = false;
   int stats_cluster_count = 0, stats_best = -1;
   double stats_best_weight = 0.0, stats_best_pose[3] = { 0, 0, 0 };
@@ -613,11 +617,13 @@ struct bpf_engine
     converged_pending = false;
     return BPF_OK;
   }
-  // ParticleFilter's constructor (particle_filter.cpp:62-89).  Not a new_set: bpf_pf_create has never invalidated
-  // what an earlier filter on this engine left
-  void filter_created()
+  // ParticleFilter's constructor (particle_filter.cpp:62-89): n samples at the origin in buffer 0, no tree yet
+  // (counts 0).  A new_set like any other, so nothing an earlier filter on this engine left -- its CDF, statistics,
+  // pending tree, host histogram, spread flag -- is served for this one
+  void filter_created(int n)
   {
-    tree.leaf_count = tree.bin_count = 0;
+    new_set(n, cur != 0, TreeCounts{ 0, 0, 0, false });
+    spread_init = false;
     converged = 0;
     converged_pending = false;
   }
