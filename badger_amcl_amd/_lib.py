@@ -173,6 +173,14 @@ SIGNATURES = {
     "bpf_pf_resample_limit": (C.c_int, [_vp, C.c_int, _ip]),
     "bpf_shard_systematic_window_dev": (C.c_int, [_vp, C.c_uint64, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp,
                                                   C.c_int, _vp]),
+    "bpf_shard_set_resample_form": (C.c_int, [_vp, C.c_int, C.c_double]),
+    "bpf_shard_get_resample_form": (C.c_int, [_vp, _ip, _dp]),
+    "bpf_shard_slice": (C.c_int, [_vp, C.POINTER(C.c_longlong), _ip, _ip]),
+    "bpf_shard_inplace_select_dev": (C.c_int, [_vp, C.c_uint64, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _ip,
+                                               C.POINTER(C.c_longlong), _ip]),
+    "bpf_shard_inplace_xy_sums_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    "bpf_shard_inplace_converged_dev": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_vp)]),
+    "bpf_shard_inplace_converged_finish": (C.c_int, [_vp, _vp, C.c_int]),
     "bpf_kld_insert": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int]),
     "bpf_kld_insert_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "bpf_kld_stop_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _ip, _ip, _ip, _ip]),

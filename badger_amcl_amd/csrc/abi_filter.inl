@@ -183,6 +183,7 @@ int bpf_pf_restore(bpf_engine* e)
   // (counts taken in the other KLD count mode are not this mode's: computed again when they are needed)
   e->new_set(n, false, e->snap_kld_mode == e->kld_count_mode ? e->tree.counted(e->snap_leaf, e->snap_bins)
                                                               : e->tree.pending());
+  e->slice_first = -1;  // (a restored set: where it sits in a sharded set is the caller's knowledge again)
   return BPF_OK;
 }
 
@@ -380,6 +381,7 @@ int bpf_pf_update_resample(bpf_engine* e)
   // k_resample_block already wrote the weights and counted the converged particles, the single-block tail below
   // does; a larger set gets launch_converged
   e->new_set(M, true, e->tree.counted(leaf, bins), (e->fused_used || M <= 8192) ? M : 0);
+  e->slice_first = -1;  // (an unsharded resample: the set is no slice of a sharded one)
   // the device tree leaves no host histogram behind, nor does the host replay in BINS mode
   if (!e->kld_device_used && !kld_bins(e))
     e->hist_built();

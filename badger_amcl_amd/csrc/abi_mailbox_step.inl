@@ -260,6 +260,13 @@ int bpf_shard_mailbox_update_sensor_planar(bpf_engine* e, const double* ranges, 
   return shard_update_sensor_planar(e, ranges, angles, range_count, range_max, global_count, false);
 }
 
+namespace
+{
+// abi_shard_inplace.inl: the systematic resample with BPF_SHARD_RESAMPLE_IN_PLACE set
+int shard_update_resample_in_place(bpf_engine* e, void* flags_dev, uint64_t rng, int count, bool* done, int* leaf_out,
+                                   int* bins_out);
+}  // namespace
+
 int bpf_shard_mailbox_update_resample(bpf_engine* e, void* flags_dev, int* global_count_io, int* leaf_count_io,
                                       int* bin_count_out, int* windows_out, int* window_hint_io)
 {
@@ -277,8 +284,6 @@ int bpf_shard_mailbox_update_resample(bpf_engine* e, void* flags_dev, int* globa
   ShardExchange X{ e };
   const int rank = e->shard_rank, W = e->shard_world;
   const int max_global = e->max_samples;  // engines of a sharded filter carry the GLOBAL bounds
-  if (!X.collective() && max_global > e->mb.max_window)
-    return e->fail(BPF_ERR_CAPACITY, "mailbox windows are smaller than max_samples");
   rc = bpf_shard_build_cdf(e, flags_dev);
   if (rc != BPF_OK)
     return rc;
@@ -301,7 +306,22 @@ int bpf_shard_mailbox_update_resample(bpf_engine* e, void* flags_dev, int* globa
       return r2;
     return bpf_shard_converged_dev(e, x, y, M);
   };
-  if (e->resample_model == BPF_RESAMPLE_SYSTEMATIC)
+  bool in_place = false;
+  if (e->resample_model == BPF_RESAMPLE_SYSTEMATIC && e->shard_form == BPF_SHARD_RESAMPLE_IN_PLACE)
+  {
+    // every rank resamples its own slice into its own slice; the imbalance cap hands this resample to the window below
+    rc = shard_update_resample_in_place(e, flags_dev, rng, sys_count, &in_place, &leaf, &bins);
+    if (rc != BPF_OK)
+      return rc;
+    M = sys_count;
+  }
+  if (in_place)
+  {
+    // nothing left to do: the slice is current, with the global set's tree counts and updateConverged's count
+  }
+  else if (!X.collective() && max_global > e->mb.max_window)  // (the in-place form needs no window of that size)
+    return e->fail(BPF_ERR_CAPACITY, "mailbox windows are smaller than max_samples");
+  else if (e->resample_model == BPF_RESAMPLE_SYSTEMATIC)
   {
     long long* window = X.next_window(sys_count, &stride);
     if (!window)
@@ -478,6 +498,13 @@ int bpf_shard_mailbox_update_resample(bpf_engine* e, void* flags_dev, int* globa
     return rc;
   e->rng = rng_after;
   e->mb_totals_valid = false;  // the weights are 1/M now
+  if (!in_place)
+  {
+    // the window forms leave the even split
+    e->slice_first = ((long long)M * rank) / W;
+    e->slice_global = M;
+    e->shard_form_used = BPF_SHARD_RESAMPLE_WINDOW;
+  }
   *global_count_io = M;
   *leaf_count_io = leaf;
   *bin_count_out = bins;

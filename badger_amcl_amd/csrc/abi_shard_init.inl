@@ -262,7 +262,10 @@ int bpf_shard_init_with_gaussian(bpf_engine* e, const double mean[3], const doub
   rc = shard_init_gaussian_write(e, mean, rotation, sigma, global_first, local_count, global_count, &rng_after);
   if (rc != BPF_OK)
     return rc;
-  return shard_init_commit(e, local_count, rng_after, false);
+  rc = shard_init_commit(e, local_count, rng_after, false);
+  e->slice_first = rc == BPF_OK ? global_first : -1;
+  e->slice_global = global_count;
+  return rc;
 }
 
 int bpf_shard_init_with_random_poses(bpf_engine* e, long long global_first, int local_count, long long global_count)
@@ -277,7 +280,10 @@ int bpf_shard_init_with_random_poses(bpf_engine* e, long long global_first, int 
   rc = shard_init_random_write(e, global_first, local_count, global_count, &rng_after);
   if (rc != BPF_OK)
     return rc;
-  return shard_init_commit(e, local_count, rng_after, true);  // uniform over the free space: scored in tile order
+  rc = shard_init_commit(e, local_count, rng_after, true);  // uniform over the free space: scored in tile order
+  e->slice_first = rc == BPF_OK ? global_first : -1;
+  e->slice_global = global_count;
+  return rc;
 }
 
 int bpf_shard_tree_local_bins_dev(bpf_engine* e, long long global_first, void** bins_dev, int* n_bins_out,

@@ -317,6 +317,8 @@ int shard_init_all(bpf_engine* e, bool spread, const std::function<int(long long
   if (rc != BPF_OK)
     return rc;
   tree_install(e, leaf, bins, route);
+  e->slice_first = first;
+  e->slice_global = G;
   return BPF_OK;
 }
 }  // namespace

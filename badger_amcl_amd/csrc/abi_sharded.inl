@@ -385,6 +385,7 @@ int bpf_shard_adopt_dev(bpf_engine* e, const void* x_dev, const void* y_dev, con
     HIPCHK(e, hipGetLastError());
   }
   e->new_set(count, true, e->tree.counted(leaf_count, bin_count));
+  e->slice_first = -1;  // (the caller knows where the adopted samples sit in the global set; the one-call form records it)
   return BPF_OK;
 }
 
@@ -406,6 +407,9 @@ int bpf_shard_tail_small_dev(bpf_engine* e, const void* x_all_dev, const void* y
   }
   HIPCHK(e, hipGetLastError());
   e->new_set(hi - lo, true, e->tree.counted(leaf_count, bin_count), global_count);
+  e->slice_first = lo;
+  e->slice_global = global_count;
+  e->shard_form_used = BPF_SHARD_RESAMPLE_WINDOW;
   return BPF_OK;
 }
 

@@ -33,6 +33,7 @@
 #include "kernels_stats.hpp"
 #include "kernels_shard_stats.hpp"
 #include "kernels_shard_init.hpp"
+#include "kernels_shard_inplace.hpp"
 #include "kernels_score.hpp"
 #include "kernels_window.hpp"
 
@@ -71,6 +72,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_shard_init.inl"
 #include "abi_mailbox_step.inl"
 #include "abi_shard_node.inl"
+#include "abi_shard_inplace.inl"
 #include "abi_pose_array.inl"
 #include "abi_bootstrap.inl"
 #include "abi_shard_local.inl"

@@ -507,6 +507,16 @@ struct bpf_engine
   DevBuf<int> d_gt_tmin, d_gt_eslot, d_gt_tiles, d_gt_flags;
   PinnedBuf<int> h_gt_flags;
 
+  // ---- the systematic resample of a sharded set in place (kernels_shard_inplace.hpp, abi_shard_inplace.inl)
+  int shard_form = BPF_SHARD_RESAMPLE_WINDOW;       // bpf_shard_set_resample_form
+  double shard_max_share = 2.0;                     //   and its imbalance cap
+  int shard_form_used = BPF_SHARD_RESAMPLE_WINDOW;  // of the last resample
+  long long slice_first = -1;       // global index of this slice's first sample as the last init / resample left it
+  long long slice_global = 0;       //   (-1: nobody has told the engine) and the samples of the whole set
+  int ip_stage = 0;                 // 0 none, 1 selected, 2 sums exported, 3 counted
+  long long ip_epoch = -1;          // set_epoch the stages in progress belong to
+  DevBuf<long long> d_ip_words;     // [kInplaceSumWords] limbs + flag, [16] the count, [24 .. 25] / [28 .. 29] acc hi / lo
+
   // ---- cluster statistics (host, lazy)
   std::vector<bpf_cluster> clusters;
   double set_mean[3] = { 0, 0, 0 }, set_cov[5] = { 0, 0, 0, 0, 0 };
@@ -611,6 +621,7 @@ struct bpf_engine
   int fresh_filter(int n, bool flip, const TreeCounts& t, bool spread)
   {
     new_set(n, flip, t);
+    slice_first = -1;  // (a sharded init records its share behind this)
     spread_init = spread;
     HIPCHK(this, hipMemsetAsync(d_scalars.p, 0, sizeof(FilterScalars), stream));
     converged = 0;
@@ -623,6 +634,7 @@ struct bpf_engine
   void filter_created(int n)
   {
     new_set(n, cur != 0, TreeCounts{ 0, 0, 0, false });
+    slice_first = -1;
     spread_init = false;
     converged = 0;
     converged_pending = false;

@@ -13,7 +13,7 @@ import threading
 import numpy as np
 
 from .pf import BpfError
-from .sharded import ShardedState
+from .sharded import RESAMPLE_FORMS, ShardedState
 
 EXCHANGE_NONE, EXCHANGE_MAILBOX, EXCHANGE_RCCL, EXCHANGE_LOCAL = 0, 1, 2, 3
 STATS_ROUTES = {1: "gathered", 2: "distributed", 3: "host"}
@@ -51,7 +51,10 @@ class LocalShardedFilter:
     """pfs[r]: the pf.ParticleFilter of rank r, each on an engine of its own, created with the GLOBAL min / max sample
     counts and holding rank r's contiguous slice (or nothing yet, when an init follows)."""
 
-    def __init__(self, pfs, first_window=4096, timeout_ms=None, kld_count=None, connect=True):
+    def __init__(self, pfs, first_window=4096, timeout_ms=None, kld_count=None, connect=True, resample_form="window",
+                 max_share=2.0):
+        """resample_form, max_share: as for ShardedFilter ("in_place": the systematic resampler resamples every slice
+        into itself, self.counts is uneven afterwards, self.form_used tells which form a resample took)."""
         self.pfs = list(pfs)
         self.world = len(self.pfs)
         self.engines = [p.e for p in self.pfs]
@@ -66,6 +69,11 @@ class LocalShardedFilter:
         self.cdf_miss = False
         self.stats_route = self.tree_route = None
         self.counts = [0] * self.world
+        if resample_form not in RESAMPLE_FORMS:
+            raise ValueError("resample_form: window or in_place")
+        self.resample_form, self.max_share, self.form_used = resample_form, float(max_share), "window"
+        for e in self.engines:
+            e.check(self.lib.bpf_shard_set_resample_form(e.h, RESAMPLE_FORMS[resample_form], self.max_share))
         if kld_count is not None:
             for p in self.pfs:
                 p.setKldCount(int(kld_count))
@@ -252,6 +260,23 @@ class LocalShardedFilter:
         self.window_hint = [g[4] for g in got]
         self.cdf_miss = any(g[5] for g in got)
         self._even_share(m)
+        self.form_used = "window"
+        if self.resample_form == "in_place":
+            # the split is the engines' record: uneven after a resample that stayed in place
+            slices = [self.slice(r) for r in range(self.world)]
+            if len(set(sl[2] for sl in slices)) != 1:
+                raise RuntimeError("LocalShardedFilter: the ranks took different resample forms: %s" % slices)
+            if slices[0][2] == RESAMPLE_FORMS["in_place"]:
+                self.counts = [sl[1] for sl in slices]
+                self.form_used = "in_place"
+                if [sl[0] for sl in slices] != [self._first(r) for r in range(self.world)] or sum(self.counts) != m:
+                    raise RuntimeError("LocalShardedFilter: the ranks' slices do not tile the set: %s" % slices)
+
+    def slice(self, r):
+        """(global_first, local_count, form_used) of rank r's engine (bpf_shard_slice)."""
+        first, n, form = C.c_longlong(), C.c_int(), C.c_int()
+        self.engines[r].check(self.lib.bpf_shard_slice(self.engines[r].h, C.byref(first), C.byref(n), C.byref(form)))
+        return first.value, n.value, form.value
 
     # ---- the global pose and the particle cloud
     def compute_cluster_stats(self):

@@ -14,6 +14,12 @@ xGMI) carries the three small exchanges the path really has:
                    Recovery draws (w_diff > 0): every rank resolves the same draw chain and shard 0 writes
                    the random free-space poses -- no further exchange.
 
+                   resample_form="in_place" (systematic only, opt-in): no window.  Every rank resamples its own slice
+                   into its own slice (the teeth of the comb that fall into its slice of the global CDF); what crosses
+                   is the bin lists of the new tree (16 B per occupied bin), nine int64 words (limb sums of x and y,
+                   all-reduced) and one int64 count (all-reduced) for updateConverged.  The slices come out uneven
+                   and concatenate to the single engine's set with the wrapped teeth moved to the front.
+
   init             (init_with_gaussian / init_with_random_poses: every rank writes its even share of the set ONE
                    engine would produce and ends on the same drand48 state -- no exchange for the poses) then the
                    histogram tree of the GLOBAL set, whose leaf count the systematic resampler reads first: all-gather
@@ -241,6 +247,48 @@ class HipShardBackend:
                                                       int(sums_are_totals), rank, world,
                                                       C.c_void_p(window.data_ptr()), window.shape[1],
                                                       C.c_void_p(flags.data_ptr())))
+
+    # ---- the systematic resample in place (include/badger_pf.h, bpf_shard_inplace_*)
+    def set_resample_form(self, form, max_share):
+        self.e.check(self.e.lib.bpf_shard_set_resample_form(self.e.h, int(form), float(max_share)))
+
+    def resample_form(self):
+        f, s = C.c_int(), C.c_double()
+        self.e.check(self.e.lib.bpf_shard_get_resample_form(self.e.h, C.byref(f), C.byref(s)))
+        return f.value, s.value
+
+    def slice(self):
+        """(global_first, local_count, form_used) as the last sharded init or resample left this engine's slice."""
+        first, n, form = C.c_longlong(), C.c_int(), C.c_int()
+        self.e.check(self.e.lib.bpf_shard_slice(self.e.h, C.byref(first), C.byref(n), C.byref(form)))
+        return first.value, n.value, form.value
+
+    def inplace_select(self, rng, count, sums, sums_are_totals, rank, world, flags):
+        """(counts of every rank, this rank's global_first, form used); RESAMPLE_WINDOW: the cap applies, nothing
+        was changed."""
+        counts, first, form = (C.c_int * world)(), C.c_longlong(), C.c_int()
+        self.e.check(self.e.lib.bpf_shard_inplace_select_dev(
+            self.e.h, C.c_uint64(rng), int(count), C.c_void_p(sums.data_ptr()), int(sums_are_totals), rank, world,
+            C.c_void_p(flags.data_ptr()), counts, C.byref(first), C.byref(form)))
+        return [int(v) for v in counts], first.value, form.value
+
+    def inplace_xy_sums(self):
+        """int64 limb words of the new slice's x / y sums and the flag (engine memory; reduced in place by the
+        caller)."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self.e.check(self.e.lib.bpf_shard_inplace_xy_sums_dev(self.e.h, C.byref(p), C.byref(n)))
+        return torch.as_tensor(_DevArray(p.value, (n.value,), "<i8"), device=self.device)
+
+    def inplace_converged(self, reduced, global_count):
+        """one int64 word: this slice's particles near the mean of the reduced sums (reduced in place by the caller)"""
+        p = C.c_void_p()
+        self.e.check(self.e.lib.bpf_shard_inplace_converged_dev(self.e.h, C.c_void_p(reduced.data_ptr()),
+                                                                int(global_count), C.byref(p)))
+        return torch.as_tensor(_DevArray(p.value, (1,), "<i8"), device=self.device)
+
+    def inplace_converged_finish(self, reduced_count, global_count):
+        self.e.check(self.e.lib.bpf_shard_inplace_converged_finish(self.e.h, C.c_void_p(reduced_count.data_ptr()),
+                                                                   int(global_count)))
 
     def kld_insert_window(self, window, n):
         self.e.check(self.e.lib.bpf_kld_insert_dev(self.e.h, C.c_void_p(window.data_ptr()), window.shape[1], n))
@@ -487,6 +535,10 @@ def pose_selection(counts, first, stride):
     return out
 
 
+RESAMPLE_WINDOW, RESAMPLE_IN_PLACE = 0, 1  # BPF_SHARD_RESAMPLE_*
+RESAMPLE_FORMS = {"window": RESAMPLE_WINDOW, "in_place": RESAMPLE_IN_PLACE}
+
+
 class ShardedState:
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -496,8 +548,13 @@ class ShardedFilter:
     """ParticleFilter::updateSensor / updateResample over W shards (see module docstring)."""
 
     def __init__(self, backend, dist, rank=None, world=None, first_window=4096, exchange="auto",
-                 mailbox_timeout_ms=None, kld_count=None, init_follows=False):
-        """init_follows: the caller starts the set with init_with_gaussian / init_with_random_poses next, so the tree
+                 mailbox_timeout_ms=None, kld_count=None, init_follows=False, resample_form="window", max_share=2.0):
+        """resample_form: "window" (every rank receives the draw window and keeps an even cut) or "in_place": the
+        systematic resampler resamples every slice into itself (include/badger_pf.h, bpf_shard_set_resample_form) --
+        self.counts is uneven afterwards, the concatenation of the slices is the reference's set with the wrapped
+        teeth moved to the front.  When the largest slice would exceed max_share * ceil(M / W) that resample takes the
+        window form; self.form_used tells.  The multinomial resampler ignores the setting.  Every rank passes the same.
+        init_follows: the caller starts the set with init_with_gaussian / init_with_random_poses next, so the tree
         of whatever the engines hold now is not built (it matters to the systematic resampler only).
         kld_count: what the KLD stop rule counts, pf.KLD_COUNT_LEAVES or pf.KLD_COUNT_BINS (None: the backend's
         current mode).  Every rank must use the same mode; the constructor checks it over the process group."""
@@ -523,6 +580,18 @@ class ShardedFilter:
         modes = self._all_gather(torch.tensor([self.kld_count], dtype=torch.int64, device=self.device)).cpu().tolist()
         if len(set(int(m) for m in modes)) != 1:
             raise ValueError("ShardedFilter: the ranks use different KLD count modes %s" % modes)
+        if resample_form not in RESAMPLE_FORMS:
+            raise ValueError("resample_form: window or in_place")
+        self.resample_form, self.max_share = resample_form, float(max_share)
+        self.form_used = "window"  # of the last resample
+        if resample_form != "window" or hasattr(backend, "set_resample_form"):
+            backend.set_resample_form(RESAMPLE_FORMS[resample_form], self.max_share)
+        # ranks that took different forms would wait in different exchanges: every rank must pass the same
+        mine = torch.tensor([float(RESAMPLE_FORMS[resample_form]), self.max_share], dtype=torch.float64,
+                            device=self.device)
+        forms = self._all_gather(mine).reshape(self.world, 2).cpu().tolist()
+        if any(f != forms[0] for f in forms):
+            raise ValueError("ShardedFilter: the ranks use different resample forms / max_share %s" % forms)
         self.window_hint = self._first_window = first_window
         self.tree_route = None  # how the last init found the global leaf count: "device", "host", "bins" or "keys"
         self.out = torch.zeros((3, self.max_global), dtype=torch.float64, device=self.device)
@@ -804,6 +873,9 @@ class ShardedFilter:
             sums, sums_are_totals = self.totals, True
         else:
             sums, sums_are_totals = self._all_gather(b.local_sum()), False
+        self.form_used = "window"
+        if self.resample_form == "in_place" and self._resample_in_place(rng, count, sums, sums_are_totals):
+            return
         window = self._window((count, "sys"), count)
         b.systematic_window(rng, count, sums, sums_are_totals, self.rank, W, window, self.flags)
         self._assemble(window)
@@ -824,6 +896,31 @@ class ShardedFilter:
         self.leaf_count, self.bin_count = leaf, bins
         self.windows_used = 1
         self.totals = None
+
+    def _resample_in_place(self, rng, count, sums, sums_are_totals):
+        """Every rank resamples its slice into its slice (bpf_shard_inplace_*); False: the imbalance cap sends this
+        resample to the window form, nothing was changed.  Three small exchanges: the bin lists of the new tree, the
+        limb words of the x / y sums, the count of updateConverged."""
+        b = self.b
+        counts, _, form = b.inplace_select(rng, count, sums, sums_are_totals, self.rank, self.world, self.flags)
+        if form != RESAMPLE_IN_PLACE:
+            return False
+        M = count
+        self.counts, self.sample_count = counts, M
+        leaf, bins = self._global_tree()
+        words = b.inplace_xy_sums()
+        self._all_reduce_sum(words)  # limb form: the lane-wise int64 sum is exact
+        near = b.inplace_converged(words, M)
+        self._all_reduce_sum(near)
+        b.inplace_converged_finish(near, M)
+        b.set_rng_state(b.end_resample(M))
+        self.leaf_count, self.bin_count = leaf, bins
+        self.windows_used = 0
+        self.totals = None
+        self.form_used = "in_place"
+        if hasattr(b, "tree_last_route"):
+            self.tree_route = self.TREE_ROUTES.get(b.tree_last_route())
+        return True
 
     # ---- Seam B (multinomial, w_diff == 0)
     def update_resample(self):
@@ -847,6 +944,12 @@ class ShardedFilter:
                 self._finish_recovery()
                 return
             self.counts = [(M * (r + 1)) // W - (M * r) // W for r in range(W)]
+            self.form_used = "window"
+            if self.resample_form == "in_place" and b.slice()[2] == RESAMPLE_IN_PLACE:
+                # the slices are uneven: every rank's count (the engines hold them; one small gather tells the host)
+                n = torch.tensor([b.n_local()], dtype=torch.int64, device=self.device)
+                self.counts = [int(v) for v in self._all_gather(n).cpu().tolist()]
+                self.form_used = "in_place"
             self.sample_count, self.leaf_count, self.bin_count = M, leaf, bins
             self.windows_used, self.window_hint = wins, hint
             self.totals = None

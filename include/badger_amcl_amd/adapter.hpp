@@ -483,12 +483,19 @@ public:
     e().check(bpf_shard_update_sensor_cloud(e().get(), xyz, n, global_count_));
     return true;
   }
-  // ParticleFilter::updateResample over the shards; this rank adopts its even share of the new set
+  // BPF_SHARD_RESAMPLE_WINDOW (the default) or BPF_SHARD_RESAMPLE_IN_PLACE: the systematic resampler resamples this
+  // rank's slice into itself (badger_pf.h, bpf_shard_set_resample_form); every rank sets the same values
+  void setResampleForm(int form, double max_share = 2.0)
+  {
+    e().check(bpf_shard_set_resample_form(e().get(), form, max_share));
+  }
+  // ParticleFilter::updateResample over the shards; this rank adopts its even share of the new set, or -- in place --
+  // keeps the teeth of its own slice: where the slice sits afterwards is the engine's record
   void updateResample()
   {
     e().check(bpf_shard_update_resample(e().get(), &global_count_, &leaf_count_, &bin_count_, &windows_, &window_hint_,
                                         &cdf_miss_));
-    global_first_ = evenFirst(global_count_);
+    e().check(bpf_shard_slice(e().get(), &global_first_, &local_count_, &form_used_));
   }
   // Node2D::getMaxWeightPose over the GLOBAL set, the same bits on every rank
   void getMaxWeightPose(double* max_weight_out, std::array<double, 3>* max_pose)
@@ -537,6 +544,8 @@ public:
   int statsRoute() const { return route_; }  // BPF_SHARD_STATS_ROUTE_* of the last getClusterStats
   int treeRoute() const { return tree_route_; }  // BPF_SHARD_TREE_ROUTE_* of the last init
   long long globalFirst() const { return global_first_; }
+  int localCount() const { return local_count_; }  // samples of this rank's slice after the last resample
+  int formUsed() const { return form_used_; }      // BPF_SHARD_RESAMPLE_* of the last resample
   int rank() const { return rank_; }
   int world() const { return world_; }
 
@@ -557,6 +566,7 @@ private:
   int global_count_, leaf_count_, window_hint_, first_window_;
   long long global_first_;
   int bin_count_ = 0, windows_ = 0, cdf_miss_ = 0, route_ = 0, tree_route_ = 0;
+  int local_count_ = 0, form_used_ = BPF_SHARD_RESAMPLE_WINDOW;
   int rank_ = 0, world_ = 1;
 };
 
@@ -639,12 +649,17 @@ public:
     fanOut([&](int r) { ranks_[(size_t)r]->updateSensorCloud(xyz, n); });
     return true;
   }
+  void setResampleForm(int form, double max_share = 2.0)
+  {
+    for (auto& s : ranks_)
+      s->setResampleForm(form, max_share);
+  }
   void updateResample()
   {
     fanOut([&](int r) { ranks_[(size_t)r]->updateResample(); });
     for (auto& s : ranks_)
       if (s->globalSampleCount() != ranks_[0]->globalSampleCount() || s->leafCount() != ranks_[0]->leafCount() ||
-          s->binCount() != ranks_[0]->binCount())
+          s->binCount() != ranks_[0]->binCount() || s->formUsed() != ranks_[0]->formUsed())
         throw std::runtime_error("LocalShardedParticleFilter: the ranks resampled to different sets");
   }
   void getMaxWeightPose(double* max_weight_out, std::array<double, 3>* max_pose)
@@ -685,6 +700,7 @@ public:
   int leafCount() const { return ranks_[0]->leafCount(); }
   int binCount() const { return ranks_[0]->binCount(); }
   int windowsUsed() const { return ranks_[0]->windowsUsed(); }
+  int formUsed() const { return ranks_[0]->formUsed(); }
   int statsRoute() const { return ranks_[0]->statsRoute(); }
   bool cdfMiss() const
   {

@@ -660,6 +660,70 @@ int bpf_pf_resample_limit(bpf_engine* e, int leaf_count, int* count_out);
 int bpf_shard_systematic_window_dev(bpf_engine* e, uint64_t rng_state48, int count, const void* sums_dev,
                                     int sums_are_totals, int rank, int world, void* window_dev, int stride,
                                     void* flags_dev);
+/* Systematic resampling of a sharded set IN PLACE: every rank resamples its own slice into its own slice, and no draw
+ * window crosses.  Opt-in (bpf_shard_set_resample_form); the default, BPF_SHARD_RESAMPLE_WINDOW, is the form above.
+ * The multinomial resampler ignores the setting: its stop rule ties every draw to every earlier one.
+ *
+ * Parity: a rotation of the reference's set.  Let S be the set ONE engine produces by resampleSystematic
+ * (particle_filter.cpp:269-354) from the concatenation of the slices: n_random random poses first, then the teeth
+ * i = 0 .. n - 1, whose targets the reference's serial chain forms (target += delta; if (target > 1.0) target -= 1.0)
+ * exactly as bpf_shard_systematic_window_dev forms them.  With i_wrap the first tooth formed after the subtraction
+ * (n when there is none), the in-place set is S[:n_random] + teeth[i_wrap:] + teeth[:i_wrap] -- the random poses, then
+ * the teeth by ascending target -- as the concatenation of the new slices in rank order; every weight is 1 / M.
+ *   ownership   shard q holds the teeth whose target lies in its slice [T_q, T_q+1) of the global CDF: the quotients
+ *               and the ownership test of bpf_shard_draw_window_dev / bpf_shard_systematic_window_dev, so every tooth's
+ *               source particle is the one the single engine picks (the shard's last particle absorbs the slice's
+ *               rounding, the last shard whatever lies beyond the CDF, with the same miss flag).  Shard 0 also holds
+ *               the random poses, at its head.  The slices come out uneven; a shard may end up empty.
+ *   counts      every rank derives all W local counts from the totals and the targets: no exchange.
+ *   drand48     bpf_shard_begin_resample / bpf_shard_end_resample as for the window form.
+ *   tree        the leaf and bin counts of the new GLOBAL set by the bin-list route: bpf_shard_tree_local_bins_dev with
+ *               the rank's new global_first, an all-gather of the lists, bpf_shard_tree_merge_dev (the keys route and
+ *               BPF_KLD_COUNT_BINS included).
+ *   converged   updateConverged over the global set: each rank forms exact 32.96 fixed-point sums of its x and y
+ *               (order-independent), an integer all-reduce(sum) of the limb words, the mean from the reduced integers
+ *               -- the same bits on every rank --, each rank's count within dist_threshold, a second integer all-reduce,
+ *               then the single engine's float percentage test.  A non-finite or out-of-range term on any rank travels
+ *               as a flag word in the first reduce and gives a count of 0, as the reference's comparisons against a NaN
+ *               mean do.  (The single engine rounds its mean from a double sum; a particle within rounding of the
+ *               threshold may be counted differently.)
+ *   cap         max_share is a condition, not a measurement: when the largest local count would exceed
+ *               max_share * ceil(M / W), every rank -- deciding alike from the redundant counts -- takes the window form
+ *               for this resample, which re-splits evenly.  Default 2.0; max_share >= 1.
+ * What crosses between the ranks: the W totals (there already), 16 B per occupied bin, and ten integer words; the window
+ * form sends 48 B per new sample to every rank.  That is a byte and operation count, not a measurement: nothing here
+ * has run between two GPUs.
+ *
+ * Stage functions for a host with its own transport, after bpf_shard_build_cdf and bpf_shard_begin_resample:
+ *   select      counts_out[world]: every rank's new local count; *global_first_out: this rank's first global index;
+ *               *form_used_out: BPF_SHARD_RESAMPLE_IN_PLACE -- the new slice is current, its tree counts read -1 until
+ *               the bin-list stages install them -- or BPF_SHARD_RESAMPLE_WINDOW: the cap applies, nothing was changed
+ *               (the counts are the ones that were refused), go on with bpf_shard_systematic_window_dev.  Arguments as
+ *               for bpf_shard_systematic_window_dev; sums_dev is read by the host (one small copy).
+ *   xy_sums     *words_dev: n_words int64 words in engine memory (8 limbs and the flag) to all-reduce(sum) in place
+ *   converged   reduced_words_dev: those words after the reduce; *count_dev: one int64 word to all-reduce(sum)
+ *   finish      installs the reduced count; bpf_pf_get_state then reports converged.  Then bpf_shard_end_resample.
+ * bpf_shard_update_resample takes the in-place form when it is set, over the mailbox, RCCL and the local exchange (four
+ * small exchanges per resample whatever M is; *windows_out = 0); every exchange is finished before the new slice becomes
+ * current, so BPF_ERR_EXCHANGE leaves the set as it was.
+ * bpf_shard_slice: where this engine's slice sits in the global set as the last sharded init, bpf_shard_tail_small_dev,
+ * in-place select or one-call resample left it, and the form the last resample used; BPF_ERR_NOT_CONFIGURED when the
+ * set came from somewhere else (bpf_pf_set_samples, bpf_shard_adopt_dev, bpf_pf_restore, an unsharded
+ * bpf_pf_update_resample). */
+enum
+{
+  BPF_SHARD_RESAMPLE_WINDOW = 0,
+  BPF_SHARD_RESAMPLE_IN_PLACE = 1
+};
+int bpf_shard_set_resample_form(bpf_engine* e, int form, double max_share);
+int bpf_shard_get_resample_form(const bpf_engine* e, int* form_out, double* max_share_out);
+int bpf_shard_slice(bpf_engine* e, long long* global_first_out, int* local_count_out, int* form_used_out);
+int bpf_shard_inplace_select_dev(bpf_engine* e, uint64_t rng_state48, int count, const void* sums_dev,
+                                 int sums_are_totals, int rank, int world, void* flags_dev, int* counts_out,
+                                 long long* global_first_out, int* form_used_out);
+int bpf_shard_inplace_xy_sums_dev(bpf_engine* e, void** words_dev, size_t* n_words_out);
+int bpf_shard_inplace_converged_dev(bpf_engine* e, const void* reduced_words_dev, int global_count, void** count_dev);
+int bpf_shard_inplace_converged_finish(bpf_engine* e, const void* reduced_count_dev, int global_count);
 /* Mailbox exchange: the two small exchanges of the sharded path (W weight totals; one draw window whose every
  * column has exactly one writer) without a collective library.  Every engine of the node owns one uncached device
  * allocation, exported by IPC handle and mapped by the W - 1 others; a producer kernel stores its values into the
