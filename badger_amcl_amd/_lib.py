@@ -181,6 +181,15 @@ SIGNATURES = {
     "bpf_shard_inplace_xy_sums_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "bpf_shard_inplace_converged_dev": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_vp)]),
     "bpf_shard_inplace_converged_finish": (C.c_int, [_vp, _vp, C.c_int]),
+    "bpf_shard_set_rebalance": (C.c_int, [_vp, C.c_int, C.c_double]),
+    "bpf_shard_get_rebalance": (C.c_int, [_vp, _ip, _dp]),
+    "bpf_shard_rebalance_last": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
+    "bpf_shard_resample_committed": (C.c_int, [_vp, _ip]),
+    "bpf_shard_rebalance": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
+    "bpf_shard_rebalance_plan": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.c_int, C.c_int, C.POINTER(C.c_longlong),
+                                           C.POINTER(C.c_longlong), _ip]),
+    "bpf_shard_rebalance_export_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_longlong)]),
+    "bpf_shard_rebalance_import_dev": (C.c_int, [_vp, _vp, C.POINTER(C.c_longlong), C.c_longlong]),
     "bpf_kld_insert": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int]),
     "bpf_kld_insert_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "bpf_kld_stop_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _ip, _ip, _ip, _ip]),

@@ -265,6 +265,8 @@ namespace
 // abi_shard_inplace.inl: the systematic resample with BPF_SHARD_RESAMPLE_IN_PLACE set
 int shard_update_resample_in_place(bpf_engine* e, void* flags_dev, uint64_t rng, int count, bool* done, int* leaf_out,
                                    int* bins_out);
+// abi_shard_rebalance.inl: BPF_SHARD_REBALANCE_AUTO behind an in-place resample
+int shard_rebalance_auto(bpf_engine* e);
 }  // namespace
 
 int bpf_shard_mailbox_update_resample(bpf_engine* e, void* flags_dev, int* global_count_io, int* leaf_count_io,
@@ -272,6 +274,7 @@ int bpf_shard_mailbox_update_resample(bpf_engine* e, void* flags_dev, int* globa
 {
   if (!e || !flags_dev || !global_count_io || !leaf_count_io || !bin_count_out || !windows_out || !window_hint_io)
     return BPF_ERR_INVALID_ARGUMENT;
+  e->resample_committed = false;
   if (!e->have_pf)
     return e->fail(BPF_ERR_NOT_CONFIGURED, "bpf_pf_create first");
   int rc = shard_step_ready(e);
@@ -508,5 +511,9 @@ int bpf_shard_mailbox_update_resample(bpf_engine* e, void* flags_dev, int* globa
   *global_count_io = M;
   *leaf_count_io = leaf;
   *bin_count_out = bins;
+  e->resample_committed = true;
+  // the resample is complete and committed: a rebalance that fails from here on leaves the uneven set current and valid
+  if (in_place && e->shard_rebalance == BPF_SHARD_REBALANCE_AUTO)
+    return shard_rebalance_auto(e);
   return BPF_OK;
 }

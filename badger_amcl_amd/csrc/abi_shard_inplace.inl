@@ -77,7 +77,9 @@ int inplace_plan(bpf_engine* e, uint64_t rng_state48, int count, const void* sum
     largest = std::max(largest, P->counts[q]);
   }
   const long long even = ((long long)count + world - 1) / world;
-  P->in_place = !((double)largest > e->shard_max_share * (double)even);
+  // BPF_SHARD_REBALANCE_AUTO: the select always runs in place (a slice never exceeds count <= max_samples) and the
+  // rebalance behind the resample evens the slices out; otherwise the cap decides
+  P->in_place = e->shard_rebalance == BPF_SHARD_REBALANCE_AUTO || !((double)largest > e->shard_max_share * (double)even);
   return BPF_OK;
 }
 
@@ -247,6 +249,8 @@ int shard_update_resample_in_place(bpf_engine* e, void* flags_dev, uint64_t rng,
   if (rc != BPF_OK)
     return rc;
   inplace_commit(e, n_new, first, count);
+  for (int r = 0; r < W; ++r)
+    e->ip_counts[r] = P.counts[r];
   tree_install(e, leaf, bins, route);
   rc = inplace_converged_install(e, e->d_ip_words.p + 16, count);
   if (rc != BPF_OK)

@@ -516,6 +516,19 @@ struct bpf_engine
   int ip_stage = 0;                 // 0 none, 1 selected, 2 sums exported, 3 counted
   long long ip_epoch = -1;          // set_epoch the stages in progress belong to
   DevBuf<long long> d_ip_words;     // [kInplaceSumWords] limbs + flag, [16] the count, [24 .. 25] / [28 .. 29] acc hi / lo
+  int ip_counts[kMailboxMaxWorld] = { 0 };  // every rank's new count of the last one-call in-place resample
+
+  // ---- rebalancing the slices of a sharded set (kernels_shard_rebalance.hpp, abi_shard_rebalance.inl)
+  int shard_rebalance = BPF_SHARD_REBALANCE_OFF;    // bpf_shard_set_rebalance
+  double shard_trigger_share = 1.5;                 //   a policy condition, not a measurement
+  RebalancePlan rb_plan;            // bpf_shard_rebalance_plan's record
+  int rb_rank = -1;                 //   for this rank (-1: none)
+  long long rb_epoch = -1;          //   of the set with this set_epoch
+  long long rb_last_moved = 0;      // T of the last rebalance that completed (bpf_shard_rebalance_last)
+  bool resample_committed = false;  // the last one-call sharded resample made its new set current (even when the AUTO
+                                    //   rebalance behind it then failed): bpf_shard_resample_committed
+  DevBuf<long long> d_rb_rows;      // int64[4][out[rank]]: this rank's outgoing samples
+  DevBuf<long long> d_rb_gather;    // int64[4][T]: every rank's, compact (the one-call form)
 
   // ---- cluster statistics (host, lazy)
   std::vector<bpf_cluster> clusters;
@@ -615,6 +628,22 @@ struct bpf_engine
       converged_pending = true;
       conv_n = converged_of;
     }
+  }
+  // A sharded set's slices went back to the even split (abi_shard_rebalance.inl): this rank's n samples from global
+  // index `first` of `global` are in the other buffer, poses and weights copied bit for bit.  What describes the
+  // GLOBAL set or the filter stays: tree (pending counts stay pending), converged and its pending count, d_scalars,
+  // the drand48 state, spread_init, shard_form_used.  What described the old slice goes: the CDF and partials, the
+  // statistics (epoch), the host histogram, and the W totals of the last sensor update, which belong to the old split.
+  void slice_rebalanced(int n, long long first, long long global)
+  {
+    cur ^= 1;
+    sample_count = n;
+    slice_first = first;
+    slice_global = global;
+    wc.drop();
+    set_epoch++;
+    hist_matches_set = false;
+    mb_totals_valid = false;
   }
   // initWithGaussian / initWithPoseFn / a set given by the caller (particle_filter.cpp:126-131,157-168): a new set,
   // w_slow = w_fast = 0, converged = false; `spread`: the poses are uniform over the free space

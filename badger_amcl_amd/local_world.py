@@ -13,7 +13,7 @@ import threading
 import numpy as np
 
 from .pf import BpfError
-from .sharded import RESAMPLE_FORMS, ShardedState
+from .sharded import REBALANCE_MODES, RESAMPLE_FORMS, ShardedState
 
 EXCHANGE_NONE, EXCHANGE_MAILBOX, EXCHANGE_RCCL, EXCHANGE_LOCAL = 0, 1, 2, 3
 STATS_ROUTES = {1: "gathered", 2: "distributed", 3: "host"}
@@ -52,9 +52,12 @@ class LocalShardedFilter:
     counts and holding rank r's contiguous slice (or nothing yet, when an init follows)."""
 
     def __init__(self, pfs, first_window=4096, timeout_ms=None, kld_count=None, connect=True, resample_form="window",
-                 max_share=2.0):
+                 max_share=2.0, rebalance="off", trigger_share=1.5):
         """resample_form, max_share: as for ShardedFilter ("in_place": the systematic resampler resamples every slice
-        into itself, self.counts is uneven afterwards, self.form_used tells which form a resample took)."""
+        into itself, self.counts is uneven afterwards, self.form_used tells which form a resample took).
+        rebalance, trigger_share: as for ShardedFilter ("auto": an in-place resample never falls back to the window
+        form, and slices more uneven than trigger_share * ceil(M / W) go back to the even split behind it;
+        self.rebalanced tells how many samples moved)."""
         self.pfs = list(pfs)
         self.world = len(self.pfs)
         self.engines = [p.e for p in self.pfs]
@@ -74,6 +77,11 @@ class LocalShardedFilter:
         self.resample_form, self.max_share, self.form_used = resample_form, float(max_share), "window"
         for e in self.engines:
             e.check(self.lib.bpf_shard_set_resample_form(e.h, RESAMPLE_FORMS[resample_form], self.max_share))
+        if rebalance not in REBALANCE_MODES:
+            raise ValueError("rebalance: off or auto")
+        self.rebalance_mode, self.trigger_share, self.rebalanced = rebalance, float(trigger_share), 0
+        for e in self.engines:
+            e.check(self.lib.bpf_shard_set_rebalance(e.h, REBALANCE_MODES[rebalance], self.trigger_share))
         if kld_count is not None:
             for p in self.pfs:
                 p.setKldCount(int(kld_count))
@@ -253,7 +261,23 @@ class LocalShardedFilter:
                                                C.byref(miss))
             got[r] = (m.value, leaf.value, bins.value, wins.value, hint.value, miss.value)
             return rc
-        self._collective(call)
+        try:
+            self._collective(call)
+        except (BpfError, RuntimeError):
+            # rebalance="auto": the call can fail AFTER its resample became current, in the rebalance behind it.  The
+            # books then follow the new, uneven set before the error goes up: the resample must not be run again;
+            # rebalance() may be
+            if all(self._resample_committed(r) for r in range(self.world)) and None not in got:
+                self._after_resample(got)
+            raise
+        self._after_resample(got)
+
+    def _resample_committed(self, r):
+        c = C.c_int()
+        self.engines[r].check(self.lib.bpf_shard_resample_committed(self.engines[r].h, C.byref(c)))
+        return bool(c.value)
+
+    def _after_resample(self, got):
         if len(set(g[:3] for g in got)) != 1:
             raise RuntimeError("LocalShardedFilter: the ranks resampled to different sets: %s" % got)
         m, self.leaf_count, self.bin_count, self.windows_used = got[0][:4]
@@ -271,6 +295,34 @@ class LocalShardedFilter:
                 self.form_used = "in_place"
                 if [sl[0] for sl in slices] != [self._first(r) for r in range(self.world)] or sum(self.counts) != m:
                     raise RuntimeError("LocalShardedFilter: the ranks' slices do not tile the set: %s" % slices)
+                self.rebalanced = self._rebalance_last() if self.rebalance_mode == "auto" else 0
+
+    def _rebalance_last(self):
+        got = []
+        for e in self.engines:
+            t = C.c_longlong(-1)
+            e.check(self.lib.bpf_shard_rebalance_last(e.h, C.byref(t)))
+            got.append(t.value)
+        if len(set(got)) != 1:
+            raise RuntimeError("LocalShardedFilter: the ranks moved different numbers of samples: %s" % got)
+        return got[0]
+
+    def rebalance(self):
+        """The slices back to the even split in global order (bpf_shard_rebalance on every rank): only the samples on
+        the wrong rank move.  Returns the number moved over all ranks; 0: the split was even already."""
+        got = [None] * self.world
+
+        def call(r, h, lib):
+            t = C.c_longlong(-1)
+            rc = lib.bpf_shard_rebalance(h, C.byref(t))
+            got[r] = t.value
+            return rc
+        self._collective(call)
+        if len(set(got)) != 1:
+            raise RuntimeError("LocalShardedFilter: the ranks moved different numbers of samples: %s" % got)
+        self._even_share(sum(self.counts))
+        self.rebalanced = got[0]
+        return got[0]
 
     def slice(self, r):
         """(global_first, local_count, form_used) of rank r's engine (bpf_shard_slice)."""

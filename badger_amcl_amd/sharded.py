@@ -20,6 +20,10 @@ xGMI) carries the three small exchanges the path really has:
                    all-reduced) and one int64 count (all-reduced) for updateConverged.  The slices come out uneven
                    and concatenate to the single engine's set with the wrapped teeth moved to the front.
 
+                   rebalance() / rebalance="auto": the slices back to the even split in global order; only the
+                   samples on the wrong rank move, one ragged all-gather of their x / y / theta / w bits (32 B per moved
+                   sample into every rank: the gather is a broadcast, no point-to-point form is built).
+
   init             (init_with_gaussian / init_with_random_poses: every rank writes its even share of the set ONE
                    engine would produce and ends on the same drand48 state -- no exchange for the poses) then the
                    histogram tree of the GLOBAL set, whose leaf count the systematic resampler reads first: all-gather
@@ -107,10 +111,19 @@ class HipShardBackend:
             self._engine_device_min = self.kld_device_min
         g, lf, bn, wn, hint = (C.c_int(int(global_n)), C.c_int(int(leaf_count)), C.c_int(0), C.c_int(0),
                                C.c_int(int(window_hint)))
-        self.e.check(self.e.lib.bpf_shard_mailbox_update_resample(self.e.h, C.c_void_p(flags.data_ptr()), C.byref(g),
-                                                                  C.byref(lf), C.byref(bn), C.byref(wn),
-                                                                  C.byref(hint)))
-        return g.value, lf.value, bn.value, wn.value, hint.value
+        rc = self.e.lib.bpf_shard_mailbox_update_resample(self.e.h, C.c_void_p(flags.data_ptr()), C.byref(g),
+                                                          C.byref(lf), C.byref(bn), C.byref(wn), C.byref(hint))
+        # (kept for resample_committed(): the engine wrote them before an AUTO rebalance that failed behind the resample)
+        self.last_resample = (g.value, lf.value, bn.value, wn.value, hint.value)
+        self.e.check(rc)
+        return self.last_resample
+
+    def resample_committed(self):
+        """True when the last one-call resample made its new set current, whatever it returned (an error then came
+        from the AUTO rebalance behind it: the resample must not be run again)."""
+        c = C.c_int()
+        self.e.check(self.e.lib.bpf_shard_resample_committed(self.e.h, C.byref(c)))
+        return bool(c.value)
 
     def mailbox_selftest(self, rounds=4):
         """Full window exchanges with a payload every rank verifies (both parities, twice)."""
@@ -289,6 +302,47 @@ class HipShardBackend:
     def inplace_converged_finish(self, reduced_count, global_count):
         self.e.check(self.e.lib.bpf_shard_inplace_converged_finish(self.e.h, C.c_void_p(reduced_count.data_ptr()),
                                                                    int(global_count)))
+
+    # ---- rebalancing the slices (include/badger_pf.h, bpf_shard_rebalance_*)
+    def set_rebalance(self, mode, trigger_share):
+        self.e.check(self.e.lib.bpf_shard_set_rebalance(self.e.h, int(mode), float(trigger_share)))
+
+    def rebalance_setting(self):
+        m, t = C.c_int(), C.c_double()
+        self.e.check(self.e.lib.bpf_shard_get_rebalance(self.e.h, C.byref(m), C.byref(t)))
+        return m.value, t.value
+
+    def rebalance_last(self):
+        """Samples the last rebalance of this engine moved over all ranks (0: the last AUTO resample found none)."""
+        t = C.c_longlong()
+        self.e.check(self.e.lib.bpf_shard_rebalance_last(self.e.h, C.byref(t)))
+        return t.value
+
+    def rebalance_plan(self, counts, rank, world):
+        """(out[] of every rank, this rank's new global_first, its new count); the plan is recorded in the engine."""
+        c = (C.c_longlong * len(counts))(*[int(v) for v in counts])
+        out, first, n = (C.c_longlong * max(int(world), 1))(), C.c_longlong(), C.c_int()
+        self.e.check(self.e.lib.bpf_shard_rebalance_plan(self.e.h, c, int(rank), int(world), out, C.byref(first),
+                                                         C.byref(n)))
+        return [int(v) for v in out][:int(world)], first.value, n.value
+
+    def rebalance_export(self):
+        """int64 [4, out[rank]] device view: the bits of x / y / theta / w of this rank's outgoing samples."""
+        p, n = C.c_void_p(), C.c_longlong()
+        self.e.check(self.e.lib.bpf_shard_rebalance_export_dev(self.e.h, C.byref(p), C.byref(n)))
+        if n.value == 0:
+            return torch.empty((4, 0), dtype=torch.int64, device=self.device)
+        return torch.as_tensor(_DevArray(p.value, (4, n.value), "<i8"), device=self.device)
+
+    def rebalance_import(self, rows, rank_off, row_stride):
+        """rows: the gathered int64 rows (None when nothing moves anywhere); rank q's row k at
+        rank_off[q] + k * row_stride."""
+        if rows is None:
+            return self.e.check(self.e.lib.bpf_shard_rebalance_import_dev(self.e.h, None, None, 0))
+        assert rows.dtype == torch.int64 and rows.is_contiguous()
+        off = (C.c_longlong * len(rank_off))(*[int(v) for v in rank_off])
+        self.e.check(self.e.lib.bpf_shard_rebalance_import_dev(self.e.h, C.c_void_p(rows.data_ptr()), off,
+                                                               int(row_stride)))
 
     def kld_insert_window(self, window, n):
         self.e.check(self.e.lib.bpf_kld_insert_dev(self.e.h, C.c_void_p(window.data_ptr()), window.shape[1], n))
@@ -537,6 +591,7 @@ def pose_selection(counts, first, stride):
 
 RESAMPLE_WINDOW, RESAMPLE_IN_PLACE = 0, 1  # BPF_SHARD_RESAMPLE_*
 RESAMPLE_FORMS = {"window": RESAMPLE_WINDOW, "in_place": RESAMPLE_IN_PLACE}
+REBALANCE_MODES = {"off": 0, "auto": 1}  # BPF_SHARD_REBALANCE_*
 
 
 class ShardedState:
@@ -548,12 +603,16 @@ class ShardedFilter:
     """ParticleFilter::updateSensor / updateResample over W shards (see module docstring)."""
 
     def __init__(self, backend, dist, rank=None, world=None, first_window=4096, exchange="auto",
-                 mailbox_timeout_ms=None, kld_count=None, init_follows=False, resample_form="window", max_share=2.0):
+                 mailbox_timeout_ms=None, kld_count=None, init_follows=False, resample_form="window", max_share=2.0,
+                 rebalance="off", trigger_share=1.5):
         """resample_form: "window" (every rank receives the draw window and keeps an even cut) or "in_place": the
         systematic resampler resamples every slice into itself (include/badger_pf.h, bpf_shard_set_resample_form) --
         self.counts is uneven afterwards, the concatenation of the slices is the reference's set with the wrapped
         teeth moved to the front.  When the largest slice would exceed max_share * ceil(M / W) that resample takes the
         window form; self.form_used tells.  The multinomial resampler ignores the setting.  Every rank passes the same.
+        rebalance: "off", or "auto": an in-place resample is never sent to the window form, and when its largest slice
+        exceeds trigger_share * ceil(M / W) (a policy condition, default 1.5, >= 1) the slices go back to the even
+        split in global order (rebalance(); self.rebalanced tells how many samples moved).  form_used stays "in_place".
         init_follows: the caller starts the set with init_with_gaussian / init_with_random_poses next, so the tree
         of whatever the engines hold now is not built (it matters to the systematic resampler only).
         kld_count: what the KLD stop rule counts, pf.KLD_COUNT_LEAVES or pf.KLD_COUNT_BINS (None: the backend's
@@ -586,12 +645,19 @@ class ShardedFilter:
         self.form_used = "window"  # of the last resample
         if resample_form != "window" or hasattr(backend, "set_resample_form"):
             backend.set_resample_form(RESAMPLE_FORMS[resample_form], self.max_share)
+        if rebalance not in REBALANCE_MODES:
+            raise ValueError("rebalance: off or auto")
+        self.rebalance_mode, self.trigger_share = rebalance, float(trigger_share)
+        self.rebalanced = 0  # samples the last rebalance moved (0: the last resample needed none)
+        if rebalance != "off" or hasattr(backend, "set_rebalance"):
+            backend.set_rebalance(REBALANCE_MODES[rebalance], self.trigger_share)
         # ranks that took different forms would wait in different exchanges: every rank must pass the same
-        mine = torch.tensor([float(RESAMPLE_FORMS[resample_form]), self.max_share], dtype=torch.float64,
-                            device=self.device)
-        forms = self._all_gather(mine).reshape(self.world, 2).cpu().tolist()
+        mine = torch.tensor([float(RESAMPLE_FORMS[resample_form]), self.max_share, float(REBALANCE_MODES[rebalance]),
+                             self.trigger_share], dtype=torch.float64, device=self.device)
+        forms = self._all_gather(mine).reshape(self.world, 4).cpu().tolist()
         if any(f != forms[0] for f in forms):
-            raise ValueError("ShardedFilter: the ranks use different resample forms / max_share %s" % forms)
+            raise ValueError("ShardedFilter: the ranks use different resample forms / max_share / rebalance settings %s"
+                             % forms)
         self.window_hint = self._first_window = first_window
         self.tree_route = None  # how the last init found the global leaf count: "device", "host", "bins" or "keys"
         self.out = torch.zeros((3, self.max_global), dtype=torch.float64, device=self.device)
@@ -678,13 +744,18 @@ class ShardedFilter:
     def _is_exchange_error(self, err):
         return getattr(err, "code", None) == 9  # BPF_ERR_EXCHANGE
 
-    def _recover_exchange(self):
+    def _recover_exchange(self, committed=False):
         """Every rank gets here after its OWN wait has run out (the rank that stalled finds its peers gone one
         exchange later), so the collectives below are reached by all of them.  The engine's rule (badger_pf.h): after a
         failed wait for the totals the weights are scored but NOT normalised and the local total is in the scalars;
         a failed window wait has changed nothing of the current set.  So: drop the mailbox, all-gather the local
         totals, normalise where that was still due, and go on with the collectives -- the interrupted resample is
-        simply run again over them.  The mailbox is set up afresh after the step."""
+        simply run again over them.  The mailbox is set up afresh after the step.
+        One exception to "a failed window wait has changed nothing", with rebalance="auto": the one-call resample can
+        fail AFTER its resample became current, in the rebalance behind it (backend.resample_committed()).  Then
+        `committed` is passed: the resample is NOT run again -- it would draw from the new set with stale counts and
+        advance the rng a second time.  The weights are 1 / M and there are no totals to rebuild; the caller refreshes
+        the counts from the engines and runs only the staged rebalance()."""
         b = self.b
         totals_failed, _ = b.mailbox_error_stage()
         # meeting point of the ranks, and a check that they are recovering the same step (a time-out that fell
@@ -696,10 +767,13 @@ class ShardedFilter:
         self.mailbox = False
         self._windows.clear()
         self._pose_views.clear()
-        totals = self._all_gather(b.local_total()).clone()
-        if totals_failed:
-            b.normalize(totals, self.sample_count)
-        self.totals = totals
+        if committed:
+            self.totals = None
+        else:
+            totals = self._all_gather(b.local_total()).clone()
+            if totals_failed:
+                b.normalize(totals, self.sample_count)
+            self.totals = totals
         self._fused_totals = False
         self.recoveries += 1
         self._remake_mailbox = True
@@ -920,7 +994,33 @@ class ShardedFilter:
         self.form_used = "in_place"
         if hasattr(b, "tree_last_route"):
             self.tree_route = self.TREE_ROUTES.get(b.tree_last_route())
+        self.rebalanced = 0
+        if self.rebalance_mode == "auto" and max(counts) > self.trigger_share * ((M + self.world - 1) // self.world):
+            self.rebalance()  # every rank decides alike from the select's counts
         return True
+
+    # ---- the slices back to the even split, in global order (include/badger_pf.h, bpf_shard_rebalance_*)
+    def rebalance(self):
+        """Collective: every rank calls it.  Only the samples on the wrong rank move: one ragged all-gather of the
+        outgoing x / y / theta / w bits, 32 B per moved sample into every rank.  The concatenation of the slices is
+        unchanged bit for bit; tree counts, converged, w_slow / w_fast and the rng stay; the statistics are evaluated
+        again and the totals of a sensor update are dropped (the next resample gathers the local CDF sums).  Returns
+        the number of samples moved over all ranks (0: the split was even already, nothing crossed)."""
+        b, W = self.b, self.world
+        out, _, _ = b.rebalance_plan(self.counts, self.rank, W)
+        moved = sum(out)
+        if moved:
+            allr, pad = self._gather_ragged(b.rebalance_export(), out)
+            b.rebalance_import(allr.contiguous(), [r * 4 * pad for r in range(W)], pad)
+            self.totals = None
+            self._fused_totals = False
+            self._stats_valid = False
+        else:
+            b.rebalance_import(None, None, 0)
+        G = sum(self.counts)
+        self.counts = [(G * (r + 1)) // W - (G * r) // W for r in range(W)]
+        self.rebalanced = moved
+        return moved
 
     # ---- Seam B (multinomial, w_diff == 0)
     def update_resample(self):
@@ -937,25 +1037,44 @@ class ShardedFilter:
                 M, leaf, bins, wins, hint = b.mailbox_update_resample(self.flags, self.sample_count, leaf_in,
                                                                       self.window_hint)
             except Exception as err:  # noqa: BLE001 -- only the exchange time-out is handled, the rest goes up
+                committed = hasattr(b, "resample_committed") and b.resample_committed()
+                if committed:
+                    # the AUTO rebalance behind the resample failed: the new, uneven set is current.  Take it into the
+                    # books first (whatever the error), never resample again (see _recover_exchange)
+                    exchange = self._is_exchange_error(err)
+                    if exchange:
+                        self._recover_exchange(committed=True)
+                    self._after_one_call_resample(*b.last_resample)
+                    if not exchange:
+                        raise
+                    self.rebalance()
+                    self._finish_recovery()
+                    return
                 if not self._is_exchange_error(err):
                     raise
                 self._recover_exchange()
                 self._update_resample_stages()
                 self._finish_recovery()
                 return
-            self.counts = [(M * (r + 1)) // W - (M * r) // W for r in range(W)]
-            self.form_used = "window"
-            if self.resample_form == "in_place" and b.slice()[2] == RESAMPLE_IN_PLACE:
-                # the slices are uneven: every rank's count (the engines hold them; one small gather tells the host)
-                n = torch.tensor([b.n_local()], dtype=torch.int64, device=self.device)
-                self.counts = [int(v) for v in self._all_gather(n).cpu().tolist()]
-                self.form_used = "in_place"
-            self.sample_count, self.leaf_count, self.bin_count = M, leaf, bins
-            self.windows_used, self.window_hint = wins, hint
-            self.totals = None
-            self._fused_totals = False
+            self._after_one_call_resample(M, leaf, bins, wins, hint)
             return
         self._update_resample_stages()
+
+    def _after_one_call_resample(self, M, leaf, bins, wins, hint):
+        """The books after the engine's one-call resample made its new set current."""
+        b, W = self.b, self.world
+        self.counts = [(M * (r + 1)) // W - (M * r) // W for r in range(W)]
+        self.form_used = "window"
+        if self.resample_form == "in_place" and b.slice()[2] == RESAMPLE_IN_PLACE:
+            # the slices are uneven: every rank's count (the engines hold them; one small gather tells the host)
+            n = torch.tensor([b.n_local()], dtype=torch.int64, device=self.device)
+            self.counts = [int(v) for v in self._all_gather(n).cpu().tolist()]
+            self.form_used = "in_place"
+            self.rebalanced = b.rebalance_last() if self.rebalance_mode == "auto" else 0
+        self.sample_count, self.leaf_count, self.bin_count = M, leaf, bins
+        self.windows_used, self.window_hint = wins, hint
+        self.totals = None
+        self._fused_totals = False
 
     def _finish_recovery(self):
         if getattr(self, "_remake_mailbox", False):

@@ -489,13 +489,48 @@ public:
   {
     e().check(bpf_shard_set_resample_form(e().get(), form, max_share));
   }
+  // BPF_SHARD_REBALANCE_OFF (the default) or BPF_SHARD_REBALANCE_AUTO: an in-place resample never falls back to the
+  // window form, and slices more uneven than trigger_share * ceil(M / W) -- a policy condition -- go back to the even
+  // split behind it (badger_pf.h, bpf_shard_set_rebalance); every rank sets the same values
+  void setRebalance(int mode, double trigger_share = 1.5)
+  {
+    e().check(bpf_shard_set_rebalance(e().get(), mode, trigger_share));
+  }
+  // The slices back to the even split in global order; only the samples on the wrong rank move (one ragged gather of
+  // their x / y / theta / w bits).  Returns the samples moved over all ranks, the same on every rank; 0: the split was
+  // even already.  The totals of a sensor update are dropped: not between updateSensor and updateResample.
+  long long rebalance()
+  {
+    long long moved = 0;
+    moved_ = 0;
+    e().check(bpf_shard_rebalance(e().get(), &moved));
+    e().check(bpf_shard_slice(e().get(), &global_first_, &local_count_, &form_used_));
+    moved_ = moved;
+    return moved;
+  }
   // ParticleFilter::updateResample over the shards; this rank adopts its even share of the new set, or -- in place --
   // keeps the teeth of its own slice: where the slice sits afterwards is the engine's record
+  // With BPF_SHARD_REBALANCE_AUTO the call can fail AFTER its resample became current, in the rebalance behind it
+  // (bpf_shard_resample_committed): the figures below then describe the new, uneven set before the error is thrown,
+  // resampleCommitted() tells, and the caller must not resample again (rebalance() is the step that is left).
   void updateResample()
   {
-    e().check(bpf_shard_update_resample(e().get(), &global_count_, &leaf_count_, &bin_count_, &windows_, &window_hint_,
-                                        &cdf_miss_));
-    e().check(bpf_shard_slice(e().get(), &global_first_, &local_count_, &form_used_));
+    const int rc = bpf_shard_update_resample(e().get(), &global_count_, &leaf_count_, &bin_count_, &windows_,
+                                             &window_hint_, &cdf_miss_);
+    const std::string why = rc == BPF_OK ? std::string() : std::string(bpf_last_error_message(e().get()));
+    int committed = 0;
+    bpf_shard_resample_committed(e().get(), &committed);
+    committed_ = committed != 0;
+    moved_ = 0;
+    if (rc == BPF_OK || committed_)
+      e().check(bpf_shard_slice(e().get(), &global_first_, &local_count_, &form_used_));
+    if (rc != BPF_OK)
+      throw std::runtime_error("bpf: " + why + " (" + bpf_error_string(rc) + ")");
+    int mode = BPF_SHARD_REBALANCE_OFF;
+    double share = 0.0;
+    e().check(bpf_shard_get_rebalance(e().get(), &mode, &share));
+    if (mode == BPF_SHARD_REBALANCE_AUTO && form_used_ == BPF_SHARD_RESAMPLE_IN_PLACE)
+      e().check(bpf_shard_rebalance_last(e().get(), &moved_));
   }
   // Node2D::getMaxWeightPose over the GLOBAL set, the same bits on every rank
   void getMaxWeightPose(double* max_weight_out, std::array<double, 3>* max_pose)
@@ -546,6 +581,8 @@ public:
   long long globalFirst() const { return global_first_; }
   int localCount() const { return local_count_; }  // samples of this rank's slice after the last resample
   int formUsed() const { return form_used_; }      // BPF_SHARD_RESAMPLE_* of the last resample
+  long long rebalanced() const { return moved_; }  // samples the last rebalance() / AUTO resample moved over all ranks
+  bool resampleCommitted() const { return committed_; }  // the last updateResample made its new set current
   int rank() const { return rank_; }
   int world() const { return world_; }
 
@@ -567,6 +604,8 @@ private:
   long long global_first_;
   int bin_count_ = 0, windows_ = 0, cdf_miss_ = 0, route_ = 0, tree_route_ = 0;
   int local_count_ = 0, form_used_ = BPF_SHARD_RESAMPLE_WINDOW;
+  long long moved_ = 0;
+  bool committed_ = false;
   int rank_ = 0, world_ = 1;
 };
 
@@ -654,6 +693,19 @@ public:
     for (auto& s : ranks_)
       s->setResampleForm(form, max_share);
   }
+  void setRebalance(int mode, double trigger_share = 1.5)
+  {
+    for (auto& s : ranks_)
+      s->setRebalance(mode, trigger_share);
+  }
+  long long rebalance()
+  {
+    fanOut([&](int r) { ranks_[(size_t)r]->rebalance(); });
+    for (auto& s : ranks_)
+      if (s->rebalanced() != ranks_[0]->rebalanced())
+        throw std::runtime_error("LocalShardedParticleFilter: the ranks moved different numbers of samples");
+    return ranks_[0]->rebalanced();
+  }
   void updateResample()
   {
     fanOut([&](int r) { ranks_[(size_t)r]->updateResample(); });
@@ -701,6 +753,7 @@ public:
   int binCount() const { return ranks_[0]->binCount(); }
   int windowsUsed() const { return ranks_[0]->windowsUsed(); }
   int formUsed() const { return ranks_[0]->formUsed(); }
+  long long rebalanced() const { return ranks_[0]->rebalanced(); }
   int statsRoute() const { return ranks_[0]->statsRoute(); }
   bool cdfMiss() const
   {

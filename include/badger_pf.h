@@ -689,7 +689,8 @@ int bpf_shard_systematic_window_dev(bpf_engine* e, uint64_t rng_state48, int cou
  *               threshold may be counted differently.)
  *   cap         max_share is a condition, not a measurement: when the largest local count would exceed
  *               max_share * ceil(M / W), every rank -- deciding alike from the redundant counts -- takes the window form
- *               for this resample, which re-splits evenly.  Default 2.0; max_share >= 1.
+ *               for this resample, which re-splits evenly.  Default 2.0; max_share >= 1.  BPF_SHARD_REBALANCE_AUTO
+ *               (below) lifts the cap and evens the slices out behind the resample instead.
  * What crosses between the ranks: the W totals (there already), 16 B per occupied bin, and ten integer words; the window
  * form sends 48 B per new sample to every rank.  That is a byte and operation count, not a measurement: nothing here
  * has run between two GPUs.
@@ -724,6 +725,91 @@ int bpf_shard_inplace_select_dev(bpf_engine* e, uint64_t rng_state48, int count,
 int bpf_shard_inplace_xy_sums_dev(bpf_engine* e, void** words_dev, size_t* n_words_out);
 int bpf_shard_inplace_converged_dev(bpf_engine* e, const void* reduced_words_dev, int global_count, void** count_dev);
 int bpf_shard_inplace_converged_finish(bpf_engine* e, const void* reduced_count_dev, int global_count);
+/* Rebalancing the slices of a sharded set: the other half of the in-place form.  The slices go back to the even split
+ * in GLOBAL order -- the concatenation of the slices in rank order is the same before and after, bit for bit, x, y,
+ * theta and weight -- and only the samples that sit on the wrong rank move.  Opt-in; nothing calls it unless asked.
+ *
+ * The plan is a pure function of the W local counts (contiguous shards), so every rank derives the same one with no
+ * exchange.  With counts[0 .. W), G = sum(counts), W <= 16:
+ *   old prefix  P[r] = counts[0] + ... + counts[r - 1]; rank r holds the global indices [P[r], P[r + 1])
+ *   new prefix  Q[r] = (G r) / W in integer arithmetic -- the even split of every re-split here,
+ *               (M (r + 1)) / W - (M r) / W samples on rank r; rank r's new slice is [Q[r], Q[r + 1])
+ *   kept        rank r keeps [max(P[r], Q[r]), min(P[r + 1], Q[r + 1])); when that is empty, the empty range at P[r]
+ *   outgoing    the rest of its old slice in ascending global index, a head span and then a tail span:
+ *               out[r] = counts[r] - kept[r] samples; T = sum(out).  T = 0: the split is even already
+ *   sources     global index g of rank r's new slice is owned by the rank q with P[q] <= g < P[q + 1]; q = r: the
+ *               local sample g - P[r]; else entry g - P[q] of q's outgoing list when g lies below q's kept range and
+ *               entry g - P[q] - kept[q] when it lies above
+ * What crosses: one ragged all-gather of the outgoing rows, int64[4][out[r]] per rank (the bit patterns of x, y, theta,
+ * w).  The gather is a broadcast, so 32 T bytes enter EVERY rank.  A point-to-point form, in which a moved particle
+ * enters one rank only, is not built.  That is a byte count, not a measurement: nothing here has run between two GPUs.
+ *
+ * State (one transition): the other buffer becomes current with the new sample count, bpf_shard_slice answers with
+ * Q[rank], the new count and G; the CDF and partials, the cached statistics and the W totals of the last sensor update
+ * (they belong to the old split) are dropped.  What describes the GLOBAL set or the filter stays: leaf and bin counts
+ * and their route (pending counts stay pending), converged, w_slow / w_fast, the drand48 state, the form the last
+ * resample used.
+ *
+ * bpf_shard_rebalance: one collective call over the engine's own exchange (mailbox, RCCL, local): one gather of one
+ * word per rank for the local counts; if T > 0 the pack, a second gather of the rows into a compact int64[4][T], then
+ * the assemble and the transition.  *moved_out = T, the same on every rank.  bpf_shard_exchange_count rises by 2 when
+ * something moves and by 1 when nothing does.  T = 0: the set, its epoch and its caches are untouched, except that
+ * where the slice sits is recorded from the gathered counts (bpf_shard_slice then answers).
+ *   atomicity   every exchange is finished before the transition: on BPF_ERR_EXCHANGE or BPF_ERR_CAPACITY (mailbox:
+ *               the rows need 4 T <= 6 max_window words) the old slice stays current with all its state.
+ *
+ * Stage functions for a host with its own transport; no call waits for another rank:
+ *   plan        counts[world]: every rank's local count, the same array on every rank.  out_counts[world]: out[];
+ *               *new_first_out = Q[rank], *new_count_out = Q[rank + 1] - Q[rank].  Records the plan in the engine and
+ *               changes nothing else.  BPF_ERR_INVALID_ARGUMENT: world outside 1 .. 16, rank outside [0, world), a
+ *               negative count, counts[rank] != this engine's sample count, G > max_samples.
+ *   export      packs this rank's outgoing list: *rows_dev = int64[4][out[rank]] with row stride out[rank] (engine
+ *               memory, valid until the next rebalance call; a pointer even when *n_out = 0)
+ *   import      rows_dev: the gathered rows, rank q's row k (x, y, theta, w) at rank_off[q] + k * row_stride, in device
+ *               memory that stays as it is until the engine's stream has passed this call; assembles the new slice and
+ *               makes the transition.  out[] all zero: a no-op for the set (rows_dev may be null); the slice's place
+ *               is recorded as the one-call form does.
+ *   export and import belong to the plan of the CURRENT set: after anything that changed the set since
+ *   bpf_shard_rebalance_plan (a motion or sensor update, a resample, a rebalance) they return BPF_ERR_NOT_CONFIGURED.
+ *
+ * bpf_shard_set_rebalance, BPF_SHARD_REBALANCE_AUTO: applies to bpf_shard_update_resample (and the staged select) on
+ * the systematic in-place path only, BPF_SHARD_RESAMPLE_IN_PLACE set.  The max_share cap then no longer sends a
+ * resample to the window form: the select always runs in place (a new slice never exceeds count <= max_samples).  After
+ * the resample is complete and committed, if the largest new count exceeds trigger_share * ceil(M / W), the rebalance
+ * above runs -- every rank decides alike from the resample's own counts, so no count crosses: five exchanges per
+ * resample instead of four.  A rebalance whose exchange fails returns the error; the resampled, uneven set stays current
+ * and valid.  The staged select only lifts the cap; its host runs the stage functions above.  Default
+ * BPF_SHARD_REBALANCE_OFF: the behaviour without this section exactly, cap included.  trigger_share >= 1, default 1.5:
+ * a policy condition, not a measurement.  trigger_share < 1 or a NaN: BPF_ERR_INVALID_ARGUMENT.  The multinomial
+ * resampler and the window form re-split evenly themselves and are untouched.
+ * bpf_shard_rebalance_last: T of the last rebalance this engine completed (0 when the last AUTO resample found nothing
+ * to do, and 0 after a rebalance that failed: nothing has moved then; *moved_out of bpf_shard_rebalance likewise).
+ * bpf_shard_resample_committed: with AUTO, bpf_shard_update_resample can return an error AFTER its resample became
+ * current (the rebalance behind it failed).  *committed_out = 1 when the last bpf_shard_update_resample /
+ * bpf_shard_mailbox_update_resample of this engine made its new set current, whatever it returned; the count, leaf and
+ * bin outputs were written then.  A caller that sees an error with committed = 1 must NOT run the resample again: it
+ * refreshes its record of the split (bpf_shard_slice) and, if it wants even slices, calls a rebalance.  Without AUTO an
+ * error always means committed = 0.
+ *
+ * Between a sensor update and a resample a rebalance keeps the normalised weights (they are copied) but drops the W
+ * totals: the one-call bpf_shard_update_resample then answers BPF_ERR_NOT_CONFIGURED, as for any update without
+ * totals, and leaves the set alone; a staged host gathers the local CDF sums instead (sums_are_totals = 0).  AUTO never
+ * rebalances there. */
+enum
+{
+  BPF_SHARD_REBALANCE_OFF = 0,
+  BPF_SHARD_REBALANCE_AUTO = 1
+};
+int bpf_shard_set_rebalance(bpf_engine* e, int mode, double trigger_share);
+int bpf_shard_get_rebalance(const bpf_engine* e, int* mode_out, double* trigger_share_out);
+int bpf_shard_rebalance_last(const bpf_engine* e, long long* moved_out);
+int bpf_shard_resample_committed(const bpf_engine* e, int* committed_out);
+int bpf_shard_rebalance(bpf_engine* e, long long* moved_out);
+int bpf_shard_rebalance_plan(bpf_engine* e, const long long* counts, int rank, int world, long long* out_counts,
+                             long long* new_first_out, int* new_count_out);
+int bpf_shard_rebalance_export_dev(bpf_engine* e, void** rows_dev, long long* n_out);
+int bpf_shard_rebalance_import_dev(bpf_engine* e, const void* rows_dev, const long long* rank_off,
+                                   long long row_stride);
 /* Mailbox exchange: the two small exchanges of the sharded path (W weight totals; one draw window whose every
  * column has exactly one writer) without a collective library.  Every engine of the node owns one uncached device
  * allocation, exported by IPC handle and mapped by the W - 1 others; a producer kernel stores its values into the
