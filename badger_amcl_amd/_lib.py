@@ -181,6 +181,12 @@ SIGNATURES = {
     "bpf_shard_inplace_xy_sums_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "bpf_shard_inplace_converged_dev": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_vp)]),
     "bpf_shard_inplace_converged_finish": (C.c_int, [_vp, _vp, C.c_int]),
+    "bpf_shard_set_multinomial_form": (C.c_int, [_vp, C.c_int]),
+    "bpf_shard_get_multinomial_form": (C.c_int, [_vp, _ip]),
+    "bpf_shard_inplace_mn_select_dev": (C.c_int, [_vp, C.c_uint64, _vp, C.c_int, C.c_int, C.c_int, _vp, _ip]),
+    "bpf_shard_inplace_mn_bins_dev": (C.c_int, [_vp, C.POINTER(_vp), _ip, _ip]),
+    "bpf_shard_inplace_mn_stop_dev": (C.c_int, [_vp, _vp, _ip, C.c_int, C.c_int, _ip, _ip, _ip, _ip,
+                                                C.POINTER(C.c_longlong), _ip]),
     "bpf_shard_set_rebalance": (C.c_int, [_vp, C.c_int, C.c_double]),
     "bpf_shard_get_rebalance": (C.c_int, [_vp, _ip, _dp]),
     "bpf_shard_rebalance_last": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),

@@ -265,6 +265,9 @@ namespace
 // abi_shard_inplace.inl: the systematic resample with BPF_SHARD_RESAMPLE_IN_PLACE set
 int shard_update_resample_in_place(bpf_engine* e, void* flags_dev, uint64_t rng, int count, bool* done, int* leaf_out,
                                    int* bins_out);
+// abi_shard_inplace_mn.inl: the multinomial resample with bpf_shard_set_multinomial_form(BPF_SHARD_RESAMPLE_IN_PLACE)
+int shard_update_resample_in_place_mn(bpf_engine* e, void* flags_dev, uint64_t rng, bool* done, int* M_out, int* leaf_out,
+                                      int* bins_out);
 // abi_shard_rebalance.inl: BPF_SHARD_REBALANCE_AUTO behind an in-place resample
 int shard_rebalance_auto(bpf_engine* e);
 }  // namespace
@@ -317,6 +320,14 @@ int bpf_shard_mailbox_update_resample(bpf_engine* e, void* flags_dev, int* globa
     if (rc != BPF_OK)
       return rc;
     M = sys_count;
+  }
+  else if (e->resample_model == BPF_RESAMPLE_MULTINOMIAL && e->shard_mn_form == BPF_SHARD_RESAMPLE_IN_PLACE)
+  {
+    // every rank keeps the candidate draws of its own slice and finds the stop from the merged bin lists; the imbalance
+    // cap, or a key outside the packing, hands this resample to the windows below
+    rc = shard_update_resample_in_place_mn(e, flags_dev, rng, &in_place, &M, &leaf, &bins);
+    if (rc != BPF_OK)
+      return rc;
   }
   if (in_place)
   {

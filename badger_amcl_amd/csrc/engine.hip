@@ -34,6 +34,7 @@
 #include "kernels_shard_stats.hpp"
 #include "kernels_shard_init.hpp"
 #include "kernels_shard_inplace.hpp"
+#include "kernels_shard_inplace_mn.hpp"
 #include "kernels_shard_rebalance.hpp"
 #include "kernels_score.hpp"
 #include "kernels_window.hpp"
@@ -74,6 +75,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_mailbox_step.inl"
 #include "abi_shard_node.inl"
 #include "abi_shard_inplace.inl"
+#include "abi_shard_inplace_mn.inl"
 #include "abi_shard_rebalance.inl"
 #include "abi_pose_array.inl"
 #include "abi_bootstrap.inl"

@@ -518,6 +518,22 @@ struct bpf_engine
   DevBuf<long long> d_ip_words;     // [kInplaceSumWords] limbs + flag, [16] the count, [24 .. 25] / [28 .. 29] acc hi / lo
   int ip_counts[kMailboxMaxWorld] = { 0 };  // every rank's new count of the last one-call in-place resample
 
+  // ---- the multinomial resample of a sharded set in place (kernels_shard_inplace_mn.hpp, abi_shard_inplace_mn.inl)
+  int shard_mn_form = BPF_SHARD_RESAMPLE_WINDOW;    // bpf_shard_set_multinomial_form
+  // ip_stage of its stage calls: -1 selected, -2 bin list formed; the stop stage commits and leaves ip_stage = 1
+  struct MnStage
+  {
+    int rank = 0, world = 0;
+    int n_kept = 0;                      // candidates this rank keeps (the stop rule truncates them)
+    double edge[kMailboxMaxWorld + 1];   // the slices of the global CDF
+    void* flags_dev = nullptr;           // the caller's miss flag
+  } mn;
+  DevBuf<int> d_mn_idx;             // [max] draw index of every kept candidate, ascending
+  DevBuf<int> d_mn_mark;            // [max] list entry whose key first occurs at a draw
+  DevBuf<int> d_mn_t;               // [bins] first draw index of the merged keys, ascending (beside d_keys)
+  DevBuf<int> d_mn_tiles;           // [tiles] of the select and of the mark compaction
+  DevBuf<int> d_mn_words;           // [0] first miss, [1] stop j, [2 .. 4] M / leaf / bins, [5] check, [8 .. 23] owner counts, [24] scratch
+
   // ---- rebalancing the slices of a sharded set (kernels_shard_rebalance.hpp, abi_shard_rebalance.inl)
   int shard_rebalance = BPF_SHARD_REBALANCE_OFF;    // bpf_shard_set_rebalance
   double shard_trigger_share = 1.5;                 //   a policy condition, not a measurement

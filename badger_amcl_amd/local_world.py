@@ -52,8 +52,10 @@ class LocalShardedFilter:
     counts and holding rank r's contiguous slice (or nothing yet, when an init follows)."""
 
     def __init__(self, pfs, first_window=4096, timeout_ms=None, kld_count=None, connect=True, resample_form="window",
-                 max_share=2.0, rebalance="off", trigger_share=1.5):
-        """resample_form, max_share: as for ShardedFilter ("in_place": the systematic resampler resamples every slice
+                 max_share=2.0, rebalance="off", trigger_share=1.5, multinomial_form="window"):
+        """multinomial_form: as for ShardedFilter ("in_place": the multinomial resampler resamples every slice into
+        itself, the stop index from the ranks' bin lists; max_share and rebalance apply to it too).
+        resample_form, max_share: as for ShardedFilter ("in_place": the systematic resampler resamples every slice
         into itself, self.counts is uneven afterwards, self.form_used tells which form a resample took).
         rebalance, trigger_share: as for ShardedFilter ("auto": an in-place resample never falls back to the window
         form, and slices more uneven than trigger_share * ceil(M / W) go back to the even split behind it;
@@ -77,6 +79,11 @@ class LocalShardedFilter:
         self.resample_form, self.max_share, self.form_used = resample_form, float(max_share), "window"
         for e in self.engines:
             e.check(self.lib.bpf_shard_set_resample_form(e.h, RESAMPLE_FORMS[resample_form], self.max_share))
+        if multinomial_form not in RESAMPLE_FORMS:
+            raise ValueError("multinomial_form: window or in_place")
+        self.multinomial_form = multinomial_form
+        for e in self.engines:
+            e.check(self.lib.bpf_shard_set_multinomial_form(e.h, RESAMPLE_FORMS[multinomial_form]))
         if rebalance not in REBALANCE_MODES:
             raise ValueError("rebalance: off or auto")
         self.rebalance_mode, self.trigger_share, self.rebalanced = rebalance, float(trigger_share), 0
@@ -285,7 +292,7 @@ class LocalShardedFilter:
         self.cdf_miss = any(g[5] for g in got)
         self._even_share(m)
         self.form_used = "window"
-        if self.resample_form == "in_place":
+        if self.resample_form == "in_place" or self.multinomial_form == "in_place":
             # the split is the engines' record: uneven after a resample that stayed in place
             slices = [self.slice(r) for r in range(self.world)]
             if len(set(sl[2] for sl in slices)) != 1:

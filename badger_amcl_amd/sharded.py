@@ -303,6 +303,43 @@ class HipShardBackend:
         self.e.check(self.e.lib.bpf_shard_inplace_converged_finish(self.e.h, C.c_void_p(reduced_count.data_ptr()),
                                                                    int(global_count)))
 
+    # ---- the multinomial resample in place (include/badger_pf.h, bpf_shard_inplace_mn_*)
+    def set_multinomial_form(self, form):
+        self.e.check(self.e.lib.bpf_shard_set_multinomial_form(self.e.h, int(form)))
+
+    def multinomial_form(self):
+        f = C.c_int()
+        self.e.check(self.e.lib.bpf_shard_get_multinomial_form(self.e.h, C.byref(f)))
+        return f.value
+
+    def inplace_mn_select(self, rng, sums, sums_are_totals, rank, world, flags):
+        """The candidate draws this rank owns, into the set that is not current; returns how many it keeps."""
+        n = C.c_int()
+        self.e.check(self.e.lib.bpf_shard_inplace_mn_select_dev(
+            self.e.h, C.c_uint64(rng), C.c_void_p(sums.data_ptr()), int(sums_are_totals), rank, world,
+            C.c_void_p(flags.data_ptr()), C.byref(n)))
+        return n.value
+
+    def inplace_mn_bins(self):
+        """(int64 [2, n_bins] device tensor: packed keys, first draw indices; key-out-of-range flag)."""
+        p, n, oor = C.c_void_p(), C.c_int(), C.c_int()
+        self.e.check(self.e.lib.bpf_shard_inplace_mn_bins_dev(self.e.h, C.byref(p), C.byref(n), C.byref(oor)))
+        if n.value == 0:
+            return torch.empty((2, 0), dtype=torch.int64, device=self.device), bool(oor.value)
+        return torch.as_tensor(_DevArray(p.value, (2, n.value), "<i8"), device=self.device), bool(oor.value)
+
+    def inplace_mn_stop(self, all_bins, counts, pad):
+        """all_bins: int64 [world, 2, pad] gathered lists.  (M, leaf_count, bin_count, counts of every rank, this rank's
+        global_first, form used); RESAMPLE_WINDOW: the cap applies, nothing was changed."""
+        W = len(counts)
+        c = (C.c_int * W)(*[int(v) for v in counts])
+        m, leaf, bins, first, form = C.c_int(), C.c_int(), C.c_int(), C.c_longlong(), C.c_int()
+        out = (C.c_int * W)()
+        self.e.check(self.e.lib.bpf_shard_inplace_mn_stop_dev(
+            self.e.h, C.c_void_p(all_bins.data_ptr()), c, W, int(pad), C.byref(m), C.byref(leaf), C.byref(bins), out,
+            C.byref(first), C.byref(form)))
+        return m.value, leaf.value, bins.value, [int(v) for v in out], first.value, form.value
+
     # ---- rebalancing the slices (include/badger_pf.h, bpf_shard_rebalance_*)
     def set_rebalance(self, mode, trigger_share):
         self.e.check(self.e.lib.bpf_shard_set_rebalance(self.e.h, int(mode), float(trigger_share)))
@@ -604,8 +641,13 @@ class ShardedFilter:
 
     def __init__(self, backend, dist, rank=None, world=None, first_window=4096, exchange="auto",
                  mailbox_timeout_ms=None, kld_count=None, init_follows=False, resample_form="window", max_share=2.0,
-                 rebalance="off", trigger_share=1.5):
-        """resample_form: "window" (every rank receives the draw window and keeps an even cut) or "in_place": the
+                 rebalance="off", trigger_share=1.5, multinomial_form="window"):
+        """multinomial_form: "window" (the default) or "in_place": the MULTINOMIAL resampler resamples every slice into
+        itself (include/badger_pf.h, bpf_shard_set_multinomial_form): every rank keeps the candidate draws of its own
+        slice, the stop index comes from the ranks' bin lists, and the concatenation of the slices is the reference's
+        set sorted stably by the owner of each draw.  max_share and rebalance apply to it as to the systematic form;
+        a key outside the packing sends that resample to the window form too.  Every rank passes the same.
+        resample_form: "window" (every rank receives the draw window and keeps an even cut) or "in_place": the
         systematic resampler resamples every slice into itself (include/badger_pf.h, bpf_shard_set_resample_form) --
         self.counts is uneven afterwards, the concatenation of the slices is the reference's set with the wrapped
         teeth moved to the front.  When the largest slice would exceed max_share * ceil(M / W) that resample takes the
@@ -645,6 +687,11 @@ class ShardedFilter:
         self.form_used = "window"  # of the last resample
         if resample_form != "window" or hasattr(backend, "set_resample_form"):
             backend.set_resample_form(RESAMPLE_FORMS[resample_form], self.max_share)
+        if multinomial_form not in RESAMPLE_FORMS:
+            raise ValueError("multinomial_form: window or in_place")
+        self.multinomial_form = multinomial_form
+        if multinomial_form != "window" or hasattr(backend, "set_multinomial_form"):
+            backend.set_multinomial_form(RESAMPLE_FORMS[multinomial_form])
         if rebalance not in REBALANCE_MODES:
             raise ValueError("rebalance: off or auto")
         self.rebalance_mode, self.trigger_share = rebalance, float(trigger_share)
@@ -653,8 +700,9 @@ class ShardedFilter:
             backend.set_rebalance(REBALANCE_MODES[rebalance], self.trigger_share)
         # ranks that took different forms would wait in different exchanges: every rank must pass the same
         mine = torch.tensor([float(RESAMPLE_FORMS[resample_form]), self.max_share, float(REBALANCE_MODES[rebalance]),
-                             self.trigger_share], dtype=torch.float64, device=self.device)
-        forms = self._all_gather(mine).reshape(self.world, 4).cpu().tolist()
+                             self.trigger_share, float(RESAMPLE_FORMS[multinomial_form])], dtype=torch.float64,
+                            device=self.device)
+        forms = self._all_gather(mine).reshape(self.world, 5).cpu().tolist()
         if any(f != forms[0] for f in forms):
             raise ValueError("ShardedFilter: the ranks use different resample forms / max_share / rebalance settings %s"
                              % forms)
@@ -999,6 +1047,41 @@ class ShardedFilter:
             self.rebalance()  # every rank decides alike from the select's counts
         return True
 
+    def _resample_in_place_mn(self, rng, sums, sums_are_totals):
+        """The multinomial resample in place, stage by stage (bpf_shard_inplace_mn_*); False: this resample goes to the
+        window form -- the imbalance cap, or a key outside the packing -- and nothing was changed.  Four small
+        exchanges: the (bin count, flag) words, the bin lists, the limb words of the x / y sums, the count of
+        updateConverged."""
+        b, W = self.b, self.world
+        b.inplace_mn_select(rng, sums, sums_are_totals, self.rank, W, self.flags)
+        bins, out_of_range = b.inplace_mn_bins()
+        meta = torch.tensor([bins.shape[1], 1 if out_of_range else 0], dtype=torch.int64, device=self.device)
+        meta = self._all_gather(meta).reshape(W, 2).cpu().tolist()
+        if any(int(m[1]) for m in meta):
+            return False  # (the flag travelled with the counts: every rank turns off here together)
+        bin_counts = [int(m[0]) for m in meta]
+        all_bins, pad = self._gather_ragged(bins, bin_counts)
+        M, leaf, nbins, counts, _, form = b.inplace_mn_stop(all_bins.contiguous(), bin_counts, pad)
+        if form != RESAMPLE_IN_PLACE:
+            return False
+        self.counts, self.sample_count = counts, M
+        words = b.inplace_xy_sums()
+        self._all_reduce_sum(words)  # limb form: the lane-wise int64 sum is exact
+        near = b.inplace_converged(words, M)
+        self._all_reduce_sum(near)
+        b.inplace_converged_finish(near, M)
+        b.set_rng_state(b.end_resample(M))
+        self.leaf_count, self.bin_count = leaf, nbins
+        self.windows_used = 0
+        self.totals = None
+        self.form_used = "in_place"
+        if hasattr(b, "tree_last_route"):
+            self.tree_route = self.TREE_ROUTES.get(b.tree_last_route())
+        self.rebalanced = 0
+        if self.rebalance_mode == "auto" and max(counts) > self.trigger_share * ((M + W - 1) // W):
+            self.rebalance()  # every rank decides alike from the owners' counts
+        return True
+
     # ---- the slices back to the even split, in global order (include/badger_pf.h, bpf_shard_rebalance_*)
     def rebalance(self):
         """Collective: every rank calls it.  Only the samples on the wrong rank move: one ragged all-gather of the
@@ -1065,7 +1148,7 @@ class ShardedFilter:
         b, W = self.b, self.world
         self.counts = [(M * (r + 1)) // W - (M * r) // W for r in range(W)]
         self.form_used = "window"
-        if self.resample_form == "in_place" and b.slice()[2] == RESAMPLE_IN_PLACE:
+        if self._in_place_wanted() and b.slice()[2] == RESAMPLE_IN_PLACE:
             # the slices are uneven: every rank's count (the engines hold them; one small gather tells the host)
             n = torch.tensor([b.n_local()], dtype=torch.int64, device=self.device)
             self.counts = [int(v) for v in self._all_gather(n).cpu().tolist()]
@@ -1075,6 +1158,10 @@ class ShardedFilter:
         self.windows_used, self.window_hint = wins, hint
         self.totals = None
         self._fused_totals = False
+
+    def _in_place_wanted(self):
+        """The in-place form is set for the resampler in use."""
+        return (self.resample_form if self.b.resample_model() == 1 else self.multinomial_form) == "in_place"
 
     def _finish_recovery(self):
         if getattr(self, "_remake_mailbox", False):
@@ -1093,6 +1180,9 @@ class ShardedFilter:
             sums, sums_are_totals = self._all_gather(b.local_sum()), False
         rng = b.rng_state()
         b.begin_resample(rng, self.leaf_count)  # w_diff; with w_diff > 0 the draws follow the resolved chain
+        self.form_used = "window"
+        if self.multinomial_form == "in_place" and self._resample_in_place_mn(rng, sums, sums_are_totals):
+            return
         b.kld_reset()
         m0, stop = 0, -1
         win = max(1024, min(self.window_hint, self.max_global))

@@ -489,6 +489,13 @@ public:
   {
     e().check(bpf_shard_set_resample_form(e().get(), form, max_share));
   }
+  // BPF_SHARD_RESAMPLE_WINDOW (the default) or BPF_SHARD_RESAMPLE_IN_PLACE: the MULTINOMIAL resampler resamples this
+  // rank's slice into itself, the stop index from the ranks' bin lists (badger_pf.h, bpf_shard_set_multinomial_form);
+  // max_share and the rebalance setting apply to it as to the systematic form; every rank sets the same value
+  void setMultinomialForm(int form)
+  {
+    e().check(bpf_shard_set_multinomial_form(e().get(), form));
+  }
   // BPF_SHARD_REBALANCE_OFF (the default) or BPF_SHARD_REBALANCE_AUTO: an in-place resample never falls back to the
   // window form, and slices more uneven than trigger_share * ceil(M / W) -- a policy condition -- go back to the even
   // split behind it (badger_pf.h, bpf_shard_set_rebalance); every rank sets the same values
@@ -692,6 +699,11 @@ public:
   {
     for (auto& s : ranks_)
       s->setResampleForm(form, max_share);
+  }
+  void setMultinomialForm(int form)
+  {
+    for (auto& s : ranks_)
+      s->setMultinomialForm(form);
   }
   void setRebalance(int mode, double trigger_share = 1.5)
   {

@@ -662,7 +662,8 @@ int bpf_shard_systematic_window_dev(bpf_engine* e, uint64_t rng_state48, int cou
                                     void* flags_dev);
 /* Systematic resampling of a sharded set IN PLACE: every rank resamples its own slice into its own slice, and no draw
  * window crosses.  Opt-in (bpf_shard_set_resample_form); the default, BPF_SHARD_RESAMPLE_WINDOW, is the form above.
- * The multinomial resampler ignores the setting: its stop rule ties every draw to every earlier one.
+ * The multinomial resampler ignores the setting; it has an in-place form and a setting of its own
+ * (bpf_shard_set_multinomial_form, below).
  *
  * Parity: a rotation of the reference's set.  Let S be the set ONE engine produces by resampleSystematic
  * (particle_filter.cpp:269-354) from the concatenation of the slices: n_random random poses first, then the teeth
@@ -725,6 +726,69 @@ int bpf_shard_inplace_select_dev(bpf_engine* e, uint64_t rng_state48, int count,
 int bpf_shard_inplace_xy_sums_dev(bpf_engine* e, void** words_dev, size_t* n_words_out);
 int bpf_shard_inplace_converged_dev(bpf_engine* e, const void* reduced_words_dev, int global_count, void** count_dev);
 int bpf_shard_inplace_converged_finish(bpf_engine* e, const void* reduced_count_dev, int global_count);
+/* Multinomial resampling of a sharded set IN PLACE: every rank resamples its own slice into its own slice, and the KLD
+ * stop index comes from the ranks' bin lists.  Opt-in through a setting of its own (bpf_shard_set_multinomial_form;
+ * bpf_shard_set_resample_form means what it meant: with the multinomial resampler it changes nothing).  max_share and
+ * the rebalance setting are the ones of bpf_shard_set_resample_form / bpf_shard_set_rebalance.
+ *
+ * Model.  Draws are numbered m = 0 .. max_samples - 1; draw m reads fixed elements of the drand48 stream (2 m + 1 and
+ * 2 m + 2, or the recovery chain's when w_diff > 0), so every rank can evaluate every candidate draw.
+ *   candidates  a CDF draw belongs to the rank whose ownership test (bpf_shard_draw_window_dev's) accepts its uniform, a
+ *               random pose of w_diff > 0 to rank 0.  A rank keeps its owned draws in ascending draw index: pose bits
+ *               and the draw index.  Every rank evaluates max_samples candidates, not max_samples / W: that redundant
+ *               work is the price of having no window.
+ *   bin lists   the distinct keys of the kept draws, each with the smallest draw index under that key: 16 B per
+ *               occupied bin.  They cross once, with the (bin count, key-outside-the-packing flag) words.
+ *   stop        merged by key with the minimum draw index: B distinct keys with first draw indices t_0 < ... < t_{B-1},
+ *               t_B = max_samples.  The tree is a function of the distinct keys in first-occurrence order, so inserting
+ *               them in that order gives L_j, the leaf count after the j-th (BPF_KLD_COUNT_BINS: L_j = j + 1).  With
+ *               c_j = max(t_j + 1, resampleLimit(L_j) + 1), M is the smallest c_j <= t_{j+1}, and the leaf and bin
+ *               counts of the new set are L_j and j + 1 there; if no j qualifies M = max_samples with L_{B-1} and B.
+ *               (The first branch of c_j is the draw that adds key j itself: it decides where the leaf count falls
+ *               with a new key.)  Every rank computes this from the same merged list; B >= 8192 takes the device tree,
+ *               fewer keys -- or a list the device tree declines -- the host tree.
+ *   truncate    rank q's new slice is its kept draws with index < M, in draw order; weights 1 / M.  The concatenation
+ *               of the slices in rank order is the reference's S[0:M] sorted stably by (owner, draw index): the same
+ *               multiset, a permutation.  What follows (the motion update's per-index Gaussians, ...) follows the
+ *               permuted order.
+ *   counts      every rank derives all W local counts by counting the owners of draws 0 .. M - 1: no exchange.
+ *   cap         as for the systematic form: when the largest count exceeds max_share * ceil(M / W) nothing has been
+ *               changed and the window form takes this resample; BPF_SHARD_REBALANCE_AUTO lifts the cap and evens the
+ *               slices out behind the committed resample.
+ *   converged, drand48, w_slow / w_fast
+ *               as for the systematic form: the limb-word and count reduces, bpf_shard_end_resample(M).
+ *   miss        a candidate beyond the stop is a draw the reference never made: the miss flag is raised only when the
+ *               smallest draw index whose search failed lies below M.
+ *   keys route  a key outside the 64-bit packing would need the draw indices beside the raw keys; the one-call form
+ *               takes the window form for that resample instead, and a staged host does the same when
+ *               bpf_shard_inplace_mn_bins_dev reports *out_of_range_out = 1 on any rank.
+ * Four exchanges per resample whatever M is -- the count and flag words, the bin lists, the limb words, the converged
+ * count -- and a fifth when the AUTO rebalance runs; the window form sends 48 B per new sample to every rank and replays
+ * all M keys on every rank.  That is a byte and operation count, not a measurement: nothing here has run between two
+ * GPUs.
+ *
+ * Stage functions for a host with its own transport, after bpf_shard_build_cdf and bpf_shard_begin_resample; a stage
+ * called out of order answers BPF_ERR_NOT_CONFIGURED:
+ *   select   writes the kept candidates into the set that is not current; *n_kept_out of them.  Refuses the systematic
+ *            resampler and a resample that was not begun with this rng_state48 (BPF_ERR_INVALID_ARGUMENT).
+ *   bins     *bins_dev = int64[2][*n_bins_out] in engine memory: packed keys, first draw indices
+ *   stop     all_bins_dev = the gathered lists int64[world][2][pad], counts[world] their lengths.  Merges, finds the
+ *            stop, counts the owners (counts_out[world]) and applies the cap: *form_used_out =
+ *            BPF_SHARD_RESAMPLE_WINDOW means nothing was changed (go on with bpf_shard_draw_window_dev), else the new
+ *            slice is current with the global set's tree counts.
+ *   then bpf_shard_inplace_xy_sums_dev / _converged_dev / _converged_finish and bpf_shard_end_resample(M).
+ * bpf_shard_update_resample takes this form for the multinomial resampler when the setting is
+ * BPF_SHARD_RESAMPLE_IN_PLACE, over the mailbox, RCCL and the local exchange (*windows_out = 0; the mailbox windows may
+ * be smaller than max_samples); every exchange is finished before the new slice becomes current, so BPF_ERR_EXCHANGE
+ * leaves the set as it was.  bpf_shard_slice reports form_used = BPF_SHARD_RESAMPLE_IN_PLACE. */
+int bpf_shard_set_multinomial_form(bpf_engine* e, int form);
+int bpf_shard_get_multinomial_form(const bpf_engine* e, int* form_out);
+int bpf_shard_inplace_mn_select_dev(bpf_engine* e, uint64_t rng_state48, const void* sums_dev, int sums_are_totals,
+                                    int rank, int world, void* flags_dev, int* n_kept_out);
+int bpf_shard_inplace_mn_bins_dev(bpf_engine* e, void** bins_dev, int* n_bins_out, int* out_of_range_out);
+int bpf_shard_inplace_mn_stop_dev(bpf_engine* e, const void* all_bins_dev, const int* counts, int world, int pad,
+                                  int* sample_count_out, int* leaf_count_out, int* bin_count_out, int* counts_out,
+                                  long long* global_first_out, int* form_used_out);
 /* Rebalancing the slices of a sharded set: the other half of the in-place form.  The slices go back to the even split
  * in GLOBAL order -- the concatenation of the slices in rank order is the same before and after, bit for bit, x, y,
  * theta and weight -- and only the samples that sit on the wrong rank move.  Opt-in; nothing calls it unless asked.

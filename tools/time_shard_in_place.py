@@ -1,16 +1,18 @@
-"""Times the two forms of the sharded systematic resample -- the draw window and the resample in place
-(include/badger_pf.h, bpf_shard_set_resample_form) -- back to back, on ONE GPU:
+"""Times the two forms of the sharded resample -- the draw window and the resample in place (include/badger_pf.h,
+bpf_shard_set_resample_form for the systematic resampler, bpf_shard_set_multinomial_form for the multinomial one:
+--resampler) -- back to back, on ONE GPU:
 
   step   restore, sensor update, resample of ONE filter of 100 k particles x 1081 beams on the 2000 x 2000 map
-         (bench.py's headline workload, systematic resampler), split evenly over W = 1, 2, 4 ranks in this process
+         (bench.py's headline workload with the resampler asked for), split evenly over W = 1, 2, 4 ranks in this process
          (badger_amcl_amd.local_world.LocalShardedFilter), for a converged and a spread cloud
 
-Medians over --repeats runs, with the spread of the runs beside them, written to profiles/shard_in_place.json.  With
+Medians over --repeats runs, with the spread of the runs beside them, written to profiles/shard_in_place.json
+(--resampler multinomial: profiles/shard_in_place_multinomial.json).  With
 every rank on one GPU the numbers bound the launch and host cost of the two protocols only.  What the in-place form is
 for -- 48 B per new sample into every rank that no longer cross -- costs nothing here: nothing has run between two
 GPUs, and that figure stays unmeasured.
 
-usage: python tools/time_shard_in_place.py [--out profiles/shard_in_place.json] [--repeats 5] [--steps 20]"""
+usage: python tools/time_shard_in_place.py [--resampler systematic|multinomial] [--out FILE] [--repeats 5] [--steps 20]"""
 import argparse
 import json
 import os
@@ -24,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def make_world(W, wl, samples, lut, form):
+def make_world(W, wl, samples, lut, form, resampler="systematic"):
     import badger_amcl_amd as bpf
     from badger_amcl_amd import synth
     from badger_amcl_amd.local_world import LocalShardedFilter
@@ -43,12 +45,12 @@ def make_world(W, wl, samples, lut, form):
         sc.setMapFactors(*synth.MAP_FACTORS)
         sc.setPlanarScannerPose(synth.SCANNER_POSE)
         pf = bpf.ParticleFilter(e, 100, n, 0.0, 0.0, 85.0)
-        pf.setResampleModel(1)  # systematic
+        pf.setResampleModel(1 if resampler == "systematic" else 0)
         pf.srand48(42)
         engines.append(e)
         keep.append((m, sc))
         pfs.append(pf)
-    f = LocalShardedFilter(pfs, resample_form=form)
+    f = LocalShardedFilter(pfs, **{"resample_form" if resampler == "systematic" else "multinomial_form": form})
     cuts = [(n * r) // W for r in range(W + 1)]
     f.load([samples[cuts[r]:cuts[r + 1]] for r in range(W)])
     f.for_each_rank(lambda r, pf: pf.snapshot())
@@ -78,11 +80,15 @@ def time_steps(f, data, steps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "shard_in_place.json"))
+    ap.add_argument("--resampler", choices=("systematic", "multinomial"), default="systematic")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--worlds", default="1,2,4")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "shard_in_place.json" if args.resampler == "systematic"
+                                else "shard_in_place_multinomial.json")
     import torch  # noqa: F401 -- before the engine library
     import badger_amcl_amd as bpf
     from badger_amcl_amd import synth
@@ -105,7 +111,7 @@ def main():
         for cloud, samples in clouds.items():
             row = {"world": W, "cloud": cloud, "particles_total": n}
             # the two forms in turn within every repeat: same box, same minute
-            worlds = {form: make_world(W, wl, np.ascontiguousarray(samples), lut, form)
+            worlds = {form: make_world(W, wl, np.ascontiguousarray(samples), lut, form, args.resampler)
                       for form in ("window", "in_place")}
             ms = {form: [] for form in worlds}
             for _ in range(args.repeats):
@@ -123,7 +129,9 @@ def main():
             rows.append(row)
             print(json.dumps(row), flush=True)
     result = {
-        "what": "sharded systematic resample, draw window against in place (bpf_shard_set_resample_form, max_share 2.0), "
+        "what": "sharded %s resample, draw window against in place (%s, max_share 2.0), " % (
+                    args.resampler, "bpf_shard_set_resample_form" if args.resampler == "systematic"
+                    else "bpf_shard_set_multinomial_form") +
                 "every rank on ONE MI355X in one process (badger_amcl_amd.local_world.LocalShardedFilter); step: restore "
                 "+ sensor update + resample, %d steps per run, medians of %d runs, the two forms alternating within every "
                 "repeat; 2-D likelihood field, 1081 beams, 2000x2000 map, 100 k particles in all" %
