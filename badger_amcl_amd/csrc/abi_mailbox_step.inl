@@ -9,7 +9,9 @@
 //
 // ShardExchange also carries the two general small exchanges of the one-call forms (abi_shard_node.inl, the beam-skip
 // counts below): a ragged all-gather and an integer all-reduce(sum), over the mailbox's window region
-// (k_mailbox_post_words / k_mailbox_take_ragged / k_mailbox_take_sum) or over RCCL.
+// (k_mailbox_post_words / k_mailbox_take_ragged / k_mailbox_take_sum) or over RCCL.  The sequences of such exchanges
+// that several one-call forms share (sample counts, bin lists, the global tree) are at the head of abi_shard_node.inl,
+// and the in-place resamples' common tail, inplace_finish, is in abi_shard_inplace.inl.
 namespace
 {
 struct ShardExchange

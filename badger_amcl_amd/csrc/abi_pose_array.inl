@@ -118,16 +118,13 @@ int bpf_shard_get_pose_array(bpf_engine* e, int root, long long first, int strid
   HIPCHK(e, hipSetDevice(e->device));
   ShardExchange X{ e };
   // the local sample counts; every rank derives every rank's first global index and contribution from them
-  long long counts[kMailboxMaxWorld] = { 0 };
-  const long long mine = e->sample_count;
-  rc = shard_gather_host_words(e, X, &mine, 1, counts);
+  long long counts[kMailboxMaxWorld] = { 0 }, my_first = 0, n_global = 0;
+  rc = shard_gather_counts(e, X, "pose array", counts, &my_first, &n_global);
   if (rc != BPF_OK)
     return rc;
   long long sel[kMailboxMaxWorld] = { 0 }, offs[kMailboxMaxWorld] = { 0 }, my_i0 = 0, at = 0, total = 0;
   for (int r = 0; r < W; ++r)
   {
-    if (counts[r] < 0)
-      return e->fail(BPF_ERR_EXCHANGE, "pose array: a negative sample count arrived");
     long long i0 = 0;
     pose_selection(at, counts[r], first, stride, &i0, &sel[r]);
     if (r == rank)

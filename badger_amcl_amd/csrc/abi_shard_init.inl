@@ -94,9 +94,7 @@ int tree_local_bins(bpf_engine* e, SampleSet& s, int n, long long global_first, 
   if (n == 0)
     return BPF_OK;
   HIPCHK(e, hipMemsetAsync(e->d_gt_flags.p, 0, 4 * sizeof(int), e->stream));
-  unsigned table = 1024;
-  while (table < 2u * (unsigned)n)
-    table <<= 1;
+  const unsigned table = hash_table_size(n);
   const int tiles = blocks_for(n, kStatTile);
   HIPCHK(e, e->d_keys.reserve((size_t)n * 3));
   HIPCHK(e, e->d_kld_hkey.reserve(table));
@@ -147,27 +145,20 @@ void tree_install(bpf_engine* e, int leaf, int bins, int route)
   e->tree_installed(kld_bins(e) ? bins : leaf, bins, route);
 }
 
-// the merge stage and the tree on the merged keys
-int tree_merge(bpf_engine* e, const long long* all, const int* counts, int world, int pad, int* leaf_out, int* bins_out)
+// What the two merges of gathered bin lists share (tree_merge, and mn_merge_stop of abi_shard_inplace_mn.inl): the
+// checked lists, the cleared table of the merged keys and the cleared flags on the stream, and *G filled but for
+// tile_sums, which is the caller's (G->cap: the lists' total)
+int gtree_merge_begin(bpf_engine* e, const long long* all, const int* counts, int world, int pad, const char* prefix,
+                      GlobalTreeArgs* G)
 {
   long long total_bins = 0;
-  for (int r = 0; r < world; ++r)
-  {
-    if (counts[r] < 0 || counts[r] > pad)
-      return e->fail(BPF_ERR_INVALID_ARGUMENT, "global tree: a bin count outside [0, pad]");
-    total_bins += counts[r];
-  }
-  const long long flat = (long long)world * pad;
-  if (total_bins <= 0 || flat >= (1ll << 30) || total_bins > (long long)e->max_samples)
-    return e->fail(BPF_ERR_INVALID_ARGUMENT, "global tree: no bins, or more than max_samples");
-  unsigned table = 1024;
-  while (table < 2ull * (unsigned long long)total_bins)
-    table <<= 1;
-  const int tiles = blocks_for((int)flat, kStatTile);
+  unsigned table = 0;
+  int rc = bin_lists_check(e, counts, world, pad, e->max_samples, prefix, &total_bins, &table);
+  if (rc != BPF_OK)
+    return rc;
   HIPCHK(e, e->d_gt_key.reserve(table));
   HIPCHK(e, e->d_gt_tmin.reserve(table));
-  HIPCHK(e, e->d_gt_eslot.reserve((size_t)flat));
-  HIPCHK(e, e->d_gt_tiles.reserve((size_t)tiles));
+  HIPCHK(e, e->d_gt_eslot.reserve((size_t)world * (size_t)pad));
   HIPCHK(e, e->d_gt_flags.reserve(4));
   HIPCHK(e, e->d_keys.reserve((size_t)total_bins * 3));
   // d_keys is about to hold the merged keys: statistics stages in progress would read it as the slice's keys, so
@@ -176,34 +167,46 @@ int tree_merge(bpf_engine* e, const long long* all, const int* counts, int world
   HIPCHK(e, hipMemsetAsync(e->d_gt_key.p, 0xFF, (size_t)table * sizeof(unsigned long long), e->stream));
   HIPCHK(e, hipMemsetAsync(e->d_gt_tmin.p, 0x7F, (size_t)table * sizeof(int), e->stream));
   HIPCHK(e, hipMemsetAsync(e->d_gt_flags.p, 0, 4 * sizeof(int), e->stream));
-  GlobalTreeArgs G{};
-  G.all = all;
-  G.world = world;
-  G.pad = pad;
+  *G = GlobalTreeArgs{};
+  G->all = all;
+  G->world = world;
+  G->pad = pad;
   for (int r = 0; r < world; ++r)
-    G.counts[r] = counts[r];
-  G.g_key = e->d_gt_key.p;
-  G.g_tmin = e->d_gt_tmin.p;
-  G.g_mask = table - 1;
-  G.eslot = e->d_gt_eslot.p;
+    G->counts[r] = counts[r];
+  G->g_key = e->d_gt_key.p;
+  G->g_tmin = e->d_gt_tmin.p;
+  G->g_mask = table - 1;
+  G->eslot = e->d_gt_eslot.p;
+  G->flags = e->d_gt_flags.p;
+  G->keys_out = e->d_keys.p;
+  G->cap = (int)total_bins;
+  return BPF_OK;
+}
+
+// the merge stage and the tree on the merged keys
+int tree_merge(bpf_engine* e, const long long* all, const int* counts, int world, int pad, int* leaf_out, int* bins_out)
+{
+  GlobalTreeArgs G;
+  int rc = gtree_merge_begin(e, all, counts, world, pad, "global tree", &G);
+  if (rc != BPF_OK)
+    return rc;
+  const int flat = world * pad, tiles = blocks_for(flat, kStatTile);
+  HIPCHK(e, e->d_gt_tiles.reserve((size_t)tiles));
   G.tile_sums = e->d_gt_tiles.p;
-  G.flags = e->d_gt_flags.p;
-  G.keys_out = e->d_keys.p;
-  G.cap = (int)total_bins;
   {
     ProfScope ps(e, BPF_K_DRAW);
-    hipLaunchKernelGGL(k_gtree_insert, dim3(blocks_for((int)flat, 256)), dim3(256), 0, e->stream, G);
+    hipLaunchKernelGGL(k_gtree_insert, dim3(blocks_for(flat, 256)), dim3(256), 0, e->stream, G);
     hipLaunchKernelGGL(k_gtree_first_count, dim3(tiles), dim3(256), 0, e->stream, G);
     hipLaunchKernelGGL(k_stats_scan_offsets, dim3(1), dim3(1024), 0, e->stream, e->d_gt_tiles.p, tiles,
                        e->d_gt_flags.p);
     hipLaunchKernelGGL(k_gtree_compact, dim3(tiles), dim3(256), 0, e->stream, G);
     HIPCHK(e, hipGetLastError());
   }
-  int rc = gtree_flags(e);
+  rc = gtree_flags(e);
   if (rc != BPF_OK)
     return rc;
   const int n_distinct = e->h_gt_flags.p[2];
-  if (n_distinct <= 0 || n_distinct > total_bins)
+  if (n_distinct <= 0 || n_distinct > G.cap)
     return e->fail(BPF_ERR_HIP, "global tree: distinct key count outside the lists (internal error)");
   int leaf = n_distinct, route = BPF_SHARD_TREE_ROUTE_BIN_COUNT;
   if (!kld_bins(e))

@@ -200,6 +200,40 @@ int inplace_converged_install(bpf_engine* e, const void* reduced_count_dev, int 
   return BPF_OK;
 }
 
+// The tail of both in-place forms over the engine's exchange (the multinomial one: abi_shard_inplace_mn.inl).  The spare
+// set holds this rank's counts[rank] samples of the new set of `count`: the converged test's two reductions, and --
+// every exchange finished -- the slice becomes current with the counts of the global set's tree.
+int inplace_finish(bpf_engine* e, ShardExchange& X, const int* counts, int count, int leaf, int bins, int route,
+                   int* leaf_out, int* bins_out)
+{
+  const int rank = e->shard_rank, W = e->shard_world, n_new = counts[rank];
+  long long first = 0;
+  for (int r = 0; r < rank; ++r)
+    first += counts[r];
+  SampleSet& s = e->sets[e->cur ^ 1];
+  int rc = inplace_xy_sums(e, s, n_new);
+  if (rc == BPF_OK)
+    rc = X.reduce_sum(e->d_ip_words.p, (size_t)kInplaceSumWords, false);  // limb form: the lane-wise sum is exact
+  if (rc == BPF_OK)
+    rc = inplace_count(e, s, n_new, e->d_ip_words.p, count);
+  if (rc == BPF_OK)
+    rc = X.reduce_sum(e->d_ip_words.p + 16, 1, false);
+  if (rc == BPF_OK)
+    rc = X.finish();
+  if (rc != BPF_OK)
+    return rc;
+  inplace_commit(e, n_new, first, count);
+  for (int r = 0; r < W; ++r)
+    e->ip_counts[r] = counts[r];
+  tree_install(e, leaf, bins, route);
+  rc = inplace_converged_install(e, e->d_ip_words.p + 16, count);
+  if (rc != BPF_OK)
+    return rc;
+  *leaf_out = e->tree.leaf_count;
+  *bins_out = e->tree.bin_count;
+  return BPF_OK;
+}
+
 // bpf_shard_update_resample's systematic branch with the in-place form set: *done = false when the imbalance cap sends
 // this resample to the window form (nothing was changed).  Every exchange is finished before the new slice becomes
 // current, so a wait that runs out leaves the set as it was, as the window form does.
@@ -228,37 +262,12 @@ int shard_update_resample_in_place(bpf_engine* e, void* flags_dev, uint64_t rng,
     if (r < rank)
       first += P.counts[r];
   }
-  SampleSet& s = e->sets[e->cur ^ 1];
-  const int n_new = P.counts[rank];
-  const TreeCounts before = e->tree;
-  int leaf = 0, bins = 0;
-  rc = shard_global_tree(e, X, s, n_new, first, counts, &leaf, &bins);
-  const int route = e->tree.gt_route;
-  e->tree = before;  // (the counts describe the set that is not current yet)
-  if (rc != BPF_OK)
-    return rc;
-  rc = inplace_xy_sums(e, s, n_new);
+  int leaf = 0, bins = 0, route = 0;
+  rc = shard_spare_tree(e, X, P.counts[rank], first, counts, &leaf, &bins, &route);
   if (rc == BPF_OK)
-    rc = X.reduce_sum(e->d_ip_words.p, (size_t)kInplaceSumWords, false);  // limb form: the lane-wise sum is exact
-  if (rc == BPF_OK)
-    rc = inplace_count(e, s, n_new, e->d_ip_words.p, count);
-  if (rc == BPF_OK)
-    rc = X.reduce_sum(e->d_ip_words.p + 16, 1, false);
-  if (rc == BPF_OK)
-    rc = X.finish();
-  if (rc != BPF_OK)
-    return rc;
-  inplace_commit(e, n_new, first, count);
-  for (int r = 0; r < W; ++r)
-    e->ip_counts[r] = P.counts[r];
-  tree_install(e, leaf, bins, route);
-  rc = inplace_converged_install(e, e->d_ip_words.p + 16, count);
-  if (rc != BPF_OK)
-    return rc;
-  *leaf_out = e->tree.leaf_count;
-  *bins_out = e->tree.bin_count;
-  *done = true;
-  return BPF_OK;
+    rc = inplace_finish(e, X, P.counts, count, leaf, bins, route, leaf_out, bins_out);
+  *done = rc == BPF_OK;
+  return rc;
 }
 }  // namespace
 

@@ -152,51 +152,20 @@ int mn_merge_stop(bpf_engine* e, const long long* all, const int* counts, int wo
                   int* bins_out, int* route_out)
 {
   const int maxs = e->max_samples;
-  long long total_bins = 0;
-  for (int r = 0; r < world; ++r)
-  {
-    if (counts[r] < 0 || counts[r] > pad)
-      return e->fail(BPF_ERR_INVALID_ARGUMENT, "in-place resample: a bin count outside [0, pad]");
-    total_bins += counts[r];
-  }
-  const long long flat = (long long)world * pad;
-  if (total_bins <= 0 || flat >= (1ll << 30) || total_bins > (long long)maxs)
-    return e->fail(BPF_ERR_INVALID_ARGUMENT, "in-place resample: no bins, or more than max_samples");
-  unsigned table = 1024;
-  while (table < 2ull * (unsigned long long)total_bins)
-    table <<= 1;
-  int rc = mn_buffers(e);
+  GlobalTreeArgs G;
+  int rc = gtree_merge_begin(e, all, counts, world, pad, "in-place resample", &G);
+  if (rc == BPF_OK)
+    rc = mn_buffers(e);
   if (rc != BPF_OK)
     return rc;
-  const int tiles = blocks_for(maxs, kMnTile);
-  HIPCHK(e, e->d_gt_key.reserve(table));
-  HIPCHK(e, e->d_gt_tmin.reserve(table));
-  HIPCHK(e, e->d_gt_eslot.reserve((size_t)flat));
-  HIPCHK(e, e->d_keys.reserve((size_t)total_bins * 3));
-  HIPCHK(e, e->d_mn_t.reserve((size_t)total_bins));
-  e->ss_stage = 0;  // d_keys is about to hold the merged keys (see tree_merge)
-  HIPCHK(e, hipMemsetAsync(e->d_gt_key.p, 0xFF, (size_t)table * sizeof(unsigned long long), e->stream));
-  HIPCHK(e, hipMemsetAsync(e->d_gt_tmin.p, 0x7F, (size_t)table * sizeof(int), e->stream));
-  HIPCHK(e, hipMemsetAsync(e->d_gt_flags.p, 0, 4 * sizeof(int), e->stream));
+  const int flat = world * pad, tiles = blocks_for(maxs, kMnTile);
+  HIPCHK(e, e->d_mn_t.reserve((size_t)G.cap));
   HIPCHK(e, hipMemsetAsync(e->d_mn_mark.p, 0, (size_t)maxs * sizeof(int), e->stream));
-  GlobalTreeArgs G{};
-  G.all = all;
-  G.world = world;
-  G.pad = pad;
-  for (int r = 0; r < world; ++r)
-    G.counts[r] = counts[r];
-  G.g_key = e->d_gt_key.p;
-  G.g_tmin = e->d_gt_tmin.p;
-  G.g_mask = table - 1;
-  G.eslot = e->d_gt_eslot.p;
   G.tile_sums = e->d_mn_tiles.p;
-  G.flags = e->d_gt_flags.p;
-  G.keys_out = e->d_keys.p;
-  G.cap = (int)total_bins;
   {
     ProfScope ps(e, BPF_K_DRAW);
-    hipLaunchKernelGGL(k_gtree_insert, dim3(blocks_for((int)flat, 256)), dim3(256), 0, e->stream, G);
-    hipLaunchKernelGGL(k_mn_mark, dim3(blocks_for((int)flat, 256)), dim3(256), 0, e->stream, G, e->d_mn_mark.p, maxs);
+    hipLaunchKernelGGL(k_gtree_insert, dim3(blocks_for(flat, 256)), dim3(256), 0, e->stream, G);
+    hipLaunchKernelGGL(k_mn_mark, dim3(blocks_for(flat, 256)), dim3(256), 0, e->stream, G, e->d_mn_mark.p, maxs);
     hipLaunchKernelGGL(k_mn_mark_count, dim3(tiles), dim3(kMnTile), 0, e->stream, (const int*)e->d_mn_mark.p, maxs,
                        e->d_mn_tiles.p);
     hipLaunchKernelGGL(k_stats_scan_offsets, dim3(1), dim3(1024), 0, e->stream, e->d_mn_tiles.p, tiles, e->d_gt_flags.p);
@@ -208,7 +177,7 @@ int mn_merge_stop(bpf_engine* e, const long long* all, const int* counts, int wo
   if (rc != BPF_OK)
     return rc;
   const int B = e->h_gt_flags.p[2];
-  if (B <= 0 || B > total_bins)
+  if (B <= 0 || B > G.cap)
     return e->fail(BPF_ERR_HIP, "in-place resample: distinct key count outside the lists (internal error)");
   const bool bins_mode = kld_bins(e);
   bool done = false;
@@ -389,34 +358,12 @@ int shard_update_resample_in_place_mn(bpf_engine* e, void* flags_dev, uint64_t r
     return rc;
   if (!mn_cap_allows(e, counts, W, M))
     return BPF_OK;
-  const int n_new = counts[rank];
-  long long first = 0;
-  for (int r = 0; r < rank; ++r)
-    first += counts[r];
-  SampleSet& s = e->sets[e->cur ^ 1];
-  rc = mn_fill_weights(e, n_new, M);
+  rc = mn_fill_weights(e, counts[rank], M);
   if (rc == BPF_OK)
-    rc = inplace_xy_sums(e, s, n_new);
-  if (rc == BPF_OK)
-    rc = X.reduce_sum(e->d_ip_words.p, (size_t)kInplaceSumWords, false);  // limb form: the lane-wise sum is exact
-  if (rc == BPF_OK)
-    rc = inplace_count(e, s, n_new, e->d_ip_words.p, M);
-  if (rc == BPF_OK)
-    rc = X.reduce_sum(e->d_ip_words.p + 16, 1, false);
-  if (rc == BPF_OK)
-    rc = X.finish();
-  if (rc != BPF_OK)
-    return rc;
-  inplace_commit(e, n_new, first, M);
-  for (int r = 0; r < W; ++r)
-    e->ip_counts[r] = counts[r];
-  tree_install(e, leaf, bins, route);
-  rc = inplace_converged_install(e, e->d_ip_words.p + 16, M);
+    rc = inplace_finish(e, X, counts, M, leaf, bins, route, leaf_out, bins_out);
   if (rc != BPF_OK)
     return rc;
   *M_out = M;
-  *leaf_out = e->tree.leaf_count;
-  *bins_out = e->tree.bin_count;
   *done = true;
   return BPF_OK;
 }

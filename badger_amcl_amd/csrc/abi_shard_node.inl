@@ -2,6 +2,11 @@
 // the statistics of the GLOBAL set -- as one collective call each.  Every exchange goes through ShardExchange
 // (abi_mailbox_step.inl): the mailbox's peer stores, or RCCL after the bootstrap's fallback.  The stage functions run
 // in the order badger_amcl_amd/sharded.py runs them (update_sensor, _ensure_stats); there is no arithmetic here.
+// The sequences that more than one of the one-call forms runs are written once, here: shard_gather_counts (the sample
+// counts, this rank's first index, the total), shard_gather_slices_host, shard_exchange_bin_lists
+// (ShardedFilter._exchange_bin_lists), shard_global_tree and shard_spare_tree (ShardedFilter._global_tree).  The checks
+// of gathered bin lists are bin_lists_check (abi_shard_stats.inl) and gtree_merge_begin (abi_shard_init.inl); the tail
+// of both in-place resamples is inplace_finish (abi_shard_inplace.inl: ShardedFilter._finish_in_place).
 namespace
 {
 // a few int64 words of every rank into host memory: all[r * n_each + k], in rank order (waits for the stream)
@@ -37,6 +42,27 @@ int shard_gather_host_words(bpf_engine* e, ShardExchange& X, const long long* mi
   return BPF_OK;
 }
 
+// every rank's sample count (one exchange), this rank's first global index and the total; the bound on the total is
+// the caller's
+int shard_gather_counts(bpf_engine* e, ShardExchange& X, const std::string& prefix, long long* counts, long long* first,
+                        long long* total)
+{
+  const long long mine = e->sample_count;
+  int rc = shard_gather_host_words(e, X, &mine, 1, counts);
+  if (rc != BPF_OK)
+    return rc;
+  *first = *total = 0;
+  for (int r = 0; r < e->shard_world; ++r)
+  {
+    if (counts[r] < 0)
+      return e->fail(BPF_ERR_EXCHANGE, prefix + ": a negative sample count arrived");
+    if (r < e->shard_rank)
+      *first += counts[r];
+    *total += counts[r];
+  }
+  return BPF_OK;
+}
+
 // x / y / theta / weight of every slice, concatenated in rank order: d_x_gather = double[4][n]
 int shard_gather_slices(bpf_engine* e, ShardExchange& X, const long long* counts, int n, SampleSet* set = nullptr)
 {
@@ -52,6 +78,18 @@ int shard_gather_slices(bpf_engine* e, ShardExchange& X, const long long* counts
     at += counts[r];
   }
   return X.gather(src, 4, counts, e->d_x_gather.p, offs, n);
+}
+
+// the same, and the first `rows` of the four in host memory behind X.finish(): soa = double[rows][n]
+int shard_gather_slices_host(bpf_engine* e, ShardExchange& X, const long long* counts, int n, int rows,
+                             std::vector<double>* soa, SampleSet* set = nullptr)
+{
+  int rc = shard_gather_slices(e, X, counts, n, set);
+  if (rc != BPF_OK)
+    return rc;
+  soa->resize((size_t)rows * (size_t)n);
+  HIPCHK(e, hipMemcpyAsync(soa->data(), e->d_x_gather.p, soa->size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  return X.finish();
 }
 
 // The ranks' bin lists of a merge stage (statistics labels, the global tree).  Every rank's (n_bins, flag) pair crosses
@@ -105,21 +143,11 @@ int shard_ensure_stats(bpf_engine* e)
     return BPF_OK;  // no slice has changed since the global figures were installed: no exchange
   HIPCHK(e, hipSetDevice(e->device));
   ShardExchange X{ e };
-  const int W = e->shard_world, rank = e->shard_rank;
-  long long counts[kMailboxMaxWorld] = { 0 };
-  const long long mine = e->sample_count;
-  rc = shard_gather_host_words(e, X, &mine, 1, counts);
+  const int W = e->shard_world;
+  long long counts[kMailboxMaxWorld] = { 0 }, total = 0, first = 0;
+  rc = shard_gather_counts(e, X, "sharded statistics", counts, &first, &total);
   if (rc != BPF_OK)
     return rc;
-  long long total = 0, first = 0;
-  for (int r = 0; r < W; ++r)
-  {
-    if (counts[r] < 0)
-      return e->fail(BPF_ERR_EXCHANGE, "sharded statistics: a negative sample count arrived");
-    if (r < rank)
-      first += counts[r];
-    total += counts[r];
-  }
   if (total <= 0 || total >= (1ll << 30))
     return e->fail(BPF_ERR_INVALID_ARGUMENT, "sharded statistics: the global set is empty, or beyond 2^30 samples");
   const int n = (int)total;
@@ -182,12 +210,8 @@ int shard_ensure_stats(bpf_engine* e)
   }
   if (route == BPF_SHARD_STATS_ROUTE_HOST)
   {
-    rc = shard_gather_slices(e, X, counts, n);
-    if (rc != BPF_OK)
-      return rc;
-    std::vector<double> soa((size_t)4 * (size_t)n), all((size_t)4 * (size_t)n);
-    HIPCHK(e, hipMemcpyAsync(soa.data(), e->d_x_gather.p, soa.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    rc = X.finish();
+    std::vector<double> soa, all((size_t)4 * (size_t)n);
+    rc = shard_gather_slices_host(e, X, counts, n, 4, &soa);
     if (rc != BPF_OK)
       return rc;
     for (int i = 0; i < n; ++i)
@@ -268,12 +292,8 @@ int shard_global_tree(bpf_engine* e, ShardExchange& X, SampleSet& s, int n, long
     for (int r = 0; r < W; ++r)
       total += counts[r];
     const int N = (int)total;
-    rc = shard_gather_slices(e, X, counts, N, &s);
-    if (rc != BPF_OK)
-      return rc;
-    std::vector<double> soa((size_t)3 * (size_t)N);
-    HIPCHK(e, hipMemcpyAsync(soa.data(), e->d_x_gather.p, soa.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    rc = X.finish();
+    std::vector<double> soa;
+    rc = shard_gather_slices_host(e, X, counts, N, 3, &soa, &s);
     if (rc != BPF_OK)
       return rc;
     std::vector<int> keys((size_t)3 * (size_t)N);
@@ -282,6 +302,18 @@ int shard_global_tree(bpf_engine* e, ShardExchange& X, SampleSet& s, int n, long
     return tree_from_keys(e, keys.data(), N, leaf_out, bins_out);
   }
   return tree_merge(e, e->d_x_gather.p, bin_counts_i, W, pad, leaf_out, bins_out);
+}
+
+// The same for the set that is NOT current yet (n samples written into the spare set): the engine's own counts keep
+// describing the current set, and the caller installs leaf / bins / route once the new set is current.
+int shard_spare_tree(bpf_engine* e, ShardExchange& X, int n, long long first, const long long* counts, int* leaf_out,
+                     int* bins_out, int* route_out)
+{
+  const TreeCounts before = e->tree;
+  const int rc = shard_global_tree(e, X, e->sets[e->cur ^ 1], n, first, counts, leaf_out, bins_out);
+  *route_out = e->tree.gt_route;
+  e->tree = before;
+  return rc;
 }
 
 // write this rank's even share into the spare set, find the global tree, and only then make the set current
@@ -305,12 +337,8 @@ int shard_init_all(bpf_engine* e, bool spread, const std::function<int(long long
   rc = write(first, n, G, &rng_after);
   if (rc != BPF_OK)
     return rc;
-  const TreeCounts before = e->tree;
-  int leaf = 0, bins = 0;
-  rc = shard_global_tree(e, X, e->sets[e->cur ^ 1], n, first, counts, &leaf, &bins);
-  const int route = e->tree.gt_route;
-  // (the counts describe the set that is not current yet)
-  e->tree = before;
+  int leaf = 0, bins = 0, route = 0;
+  rc = shard_spare_tree(e, X, n, first, counts, &leaf, &bins, &route);
   if (rc != BPF_OK)
     return rc;
   rc = shard_init_commit(e, n, rng_after, spread);
@@ -360,21 +388,10 @@ int bpf_shard_global_leaf_count(bpf_engine* e, int* leaf_count_out, int* bin_cou
   }
   HIPCHK(e, hipSetDevice(e->device));
   ShardExchange X{ e };
-  const int W = e->shard_world, rank = e->shard_rank;
-  long long counts[kMailboxMaxWorld] = { 0 };
-  const long long mine = e->sample_count;
-  rc = shard_gather_host_words(e, X, &mine, 1, counts);
+  long long counts[kMailboxMaxWorld] = { 0 }, total = 0, first = 0;
+  rc = shard_gather_counts(e, X, "global tree", counts, &first, &total);
   if (rc != BPF_OK)
     return rc;
-  long long total = 0, first = 0;
-  for (int r = 0; r < W; ++r)
-  {
-    if (counts[r] < 0)
-      return e->fail(BPF_ERR_EXCHANGE, "global tree: a negative sample count arrived");
-    if (r < rank)
-      first += counts[r];
-    total += counts[r];
-  }
   if (total <= 0 || total > (long long)e->max_samples)
     return e->fail(BPF_ERR_INVALID_ARGUMENT, "global tree: the global set is empty, or beyond max_samples");
   return shard_global_tree(e, X, e->sets[e->cur], e->sample_count, first, counts, leaf_count_out, bin_count_out);

@@ -199,14 +199,10 @@ int bpf_shard_rebalance(bpf_engine* e, long long* moved_out)
     return rc;
   HIPCHK(e, hipSetDevice(e->device));
   ShardExchange X{ e };
-  long long counts[kMailboxMaxWorld] = { 0 };
-  const long long mine = e->sample_count;
-  rc = shard_gather_host_words(e, X, &mine, 1, counts);
+  long long counts[kMailboxMaxWorld] = { 0 }, first = 0, total = 0;
+  rc = shard_gather_counts(e, X, "rebalance", counts, &first, &total);
   if (rc != BPF_OK)
     return rc;
-  for (int r = 0; r < e->shard_world; ++r)
-    if (counts[r] < 0)
-      return e->fail(BPF_ERR_EXCHANGE, "rebalance: a negative sample count arrived");
   return shard_rebalance_run(e, X, counts, moved_out);
 }
 

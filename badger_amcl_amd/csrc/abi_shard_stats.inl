@@ -27,6 +27,27 @@ int shard_stats_flags(bpf_engine* e)
     return e->fail(BPF_ERR_HIP, "sharded statistics: a bounded table walk ran out (corrupt bin list?)");
   return BPF_OK;
 }
+
+// The gathered bin lists of a merge stage (statistics labels, the global tree, the multinomial stop): every count within
+// [0, pad], a total of 1 .. max_total (0: no bound of its own), and world * pad -- the kernels' flat index -- below
+// 2^30.  *table_out: the size of the merged keys' hash table.
+int bin_lists_check(bpf_engine* e, const int* counts, int world, int pad, long long max_total, const std::string& prefix,
+                    long long* total_out, unsigned* table_out)
+{
+  long long total_bins = 0;
+  for (int r = 0; r < world; ++r)
+  {
+    if (counts[r] < 0 || counts[r] > pad)
+      return e->fail(BPF_ERR_INVALID_ARGUMENT, prefix + ": a bin count outside [0, pad]");
+    total_bins += counts[r];
+  }
+  if (total_bins <= 0 || (long long)world * pad >= (1ll << 30) || (max_total > 0 && total_bins > max_total))
+    return e->fail(BPF_ERR_INVALID_ARGUMENT,
+                   prefix + (max_total > 0 ? ": no bins, or more than max_samples" : ": no bins, or too many"));
+  *total_out = total_bins;
+  *table_out = hash_table_size(total_bins);
+  return BPF_OK;
+}
 }  // namespace
 
 int bpf_shard_samples_dev(bpf_engine* e, void** x_dev, void** y_dev, void** theta_dev, void** w_dev, int* count_out)
@@ -102,9 +123,7 @@ int bpf_shard_stats_local_bins_dev(bpf_engine* e, long long global_first, void**
   if (n > 0)
   {
     SampleSet& s = e->sets[e->cur];
-    unsigned table = 1024;
-    while (table < 2u * (unsigned)n)
-      table <<= 1;
+    const unsigned table = hash_table_size(n);
     const int tiles = blocks_for(n, kStatTile);
     HIPCHK(e, e->d_keys.reserve((size_t)n * 3));
     HIPCHK(e, e->d_kld_hkey.reserve(table));
@@ -160,21 +179,13 @@ int bpf_shard_stats_label_dev(bpf_engine* e, const void* all_bins_dev, const int
   if (!e->have_pf || e->ss_stage < 1 || e->ss_epoch != e->set_epoch)
     return e->fail(BPF_ERR_NOT_CONFIGURED, "bpf_shard_stats_local_bins_dev of the current set first");
   long long total_bins = 0;
-  for (int r = 0; r < world; ++r)
-  {
-    if (counts[r] < 0 || counts[r] > pad)
-      return e->fail(BPF_ERR_INVALID_ARGUMENT, "sharded statistics: a bin count outside [0, pad]");
-    total_bins += counts[r];
-  }
-  const long long flat = (long long)world * pad;
-  if (total_bins <= 0 || flat >= (1ll << 30))
-    return e->fail(BPF_ERR_INVALID_ARGUMENT, "sharded statistics: no bins, or too many");
+  unsigned table = 0;
+  int rc = bin_lists_check(e, counts, world, pad, 0, "sharded statistics", &total_bins, &table);
+  if (rc != BPF_OK)
+    return rc;
   HIPCHK(e, hipSetDevice(e->device));
   e->ss_stage = 1;
-  unsigned table = 1024;
-  while (table < 2ull * (unsigned long long)total_bins)
-    table <<= 1;
-  const int tiles = blocks_for((int)flat, kStatTile);
+  const int flat = world * pad, tiles = blocks_for(flat, kStatTile);
   HIPCHK(e, e->d_ss_gkey.reserve(table));
   HIPCHK(e, e->d_ss_gtmin.reserve(table));
   HIPCHK(e, e->d_ss_parent.reserve(table));
@@ -202,7 +213,7 @@ int bpf_shard_stats_label_dev(bpf_engine* e, const void* all_bins_dev, const int
   G.label = e->d_ss_label.p;
   G.binlabel = e->d_ss_binlabel.p;
   G.flags = e->d_stats_flags.p;
-  const dim3 grid(blocks_for((int)flat, 256)), block(256);
+  const dim3 grid(blocks_for(flat, 256)), block(256);
   hipLaunchKernelGGL(k_gstat_insert, grid, block, 0, e->stream, G);
   hipLaunchKernelGGL(k_gstat_init, dim3(blocks_for((int)table, 256)), block, 0, e->stream, G);
   hipLaunchKernelGGL(k_gstat_union, grid, block, 0, e->stream, G);
@@ -212,7 +223,7 @@ int bpf_shard_stats_label_dev(bpf_engine* e, const void* all_bins_dev, const int
   hipLaunchKernelGGL(k_gstat_labels, dim3(tiles), block, 0, e->stream, G, (const int*)e->d_stats_tiles.p);
   hipLaunchKernelGGL(k_gstat_binlabel, grid, block, 0, e->stream, G);
   HIPCHK(e, hipGetLastError());
-  int rc = shard_stats_flags(e);
+  rc = shard_stats_flags(e);
   if (rc != BPF_OK)
     return rc;
   e->ss_clusters = e->h_stats_flags.p[2];

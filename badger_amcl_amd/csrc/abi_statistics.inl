@@ -87,9 +87,7 @@ int compute_cluster_stats_device(bpf_engine* e, bool* handled)
       return BPF_OK;  // key range / non-finite term: the host evaluation
     // more than 1024 bins or 64 clusters in a small set: the general device path below
   }
-  unsigned table = 1024;
-  while (table < 2u * (unsigned)n)
-    table <<= 1;
+  const unsigned table = hash_table_size(n);
   const int tiles = blocks_for(n, kStatTile);
   HIPCHK(e, e->d_keys.reserve((size_t)n * 3));
   HIPCHK(e, e->d_kld_hkey.reserve(table));

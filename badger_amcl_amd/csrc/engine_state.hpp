@@ -616,7 +616,7 @@ struct bpf_engine
   // ---- transitions: every change of the particle set goes through one of these, and wc, tree, set_epoch and
   // hist_matches_set are written here and in the two structs' own members, nowhere else.  Two
   // exceptions: wc.fused_partials is set by the scoring launch and cleared by the launch that folds the partials, and
-  // TrialScores::score and shard_init_all put back a saved copy of wc / tree around work on a set that is not current
+  // TrialScores::score and shard_spare_tree put back a saved copy of wc / tree around work on a set that is not current
 
   // A scoring pass is about to overwrite the weights of a set that may not be the engine's (the candidate poses of
   // the uniform pose check, the host-buffer seam's scratch set: applyModelToSampleSet on a set of the caller's): the

@@ -21,6 +21,18 @@ constexpr size_t kBounceHalf = (size_t)2 << 20;
 
 int h2d_from_host(bpf_engine* e, void* dst, const void* src, size_t bytes, hipStream_t st);
 
+// The open-addressing table of n keys: the smallest power of two >= 2 n, at least 1024 (at most half full).  Every
+// caller passes an int sample count or a bin total it has held below 2^30, so 2 n < 2^32: the 32-bit product
+// `2u * (unsigned)n` of the sample-count sites and the 64-bit one of the bin-list sites were the same number, and the
+// result, at most 2^31, fits an unsigned.
+unsigned hash_table_size(long long n)
+{
+  unsigned table = 1024;
+  while (table < 2ull * (unsigned long long)n)
+    table <<= 1;
+  return table;
+}
+
 // The way down into PAGEABLE memory (a destination of more than a megabyte is pinned and cached by the runtime just
 // the same): piece by piece into the bounce buffer and from there by this thread.  Everything queued on `st` before
 // the call is done when it returns, and so is the copy.

@@ -634,9 +634,7 @@ int resample_block(bpf_engine* e, int window, bool systematic, const double* tar
 int kld_bins_on_device(bpf_engine* e, int n, bool* handled, int* stop_out, int* leaf_out, int* bins_out,
                        bool whole_stream)
 {
-  unsigned table = 1024;
-  while (table < 2u * (unsigned)n)
-    table <<= 1;
+  const unsigned table = hash_table_size(n);
   constexpr int kResultAt = 4 + 256;  // the pinned result words sit where the pieces form keeps its own
   const int tiles = blocks_for(n, kKldTile);
   HIPCHK(e, e->d_kld_hkey.reserve(table));
@@ -728,9 +726,7 @@ int kld_tree_on_device(bpf_engine* e, int maxs, bool* handled, int* stop_out, in
     return rcl;
   if (kld_bins(e))
     return kld_bins_on_device(e, n, handled, stop_out, leaf_out, bins_out, whole_stream);
-  unsigned table = 1024;
-  while (table < 2u * (unsigned)n)
-    table <<= 1;
+  const unsigned table = hash_table_size(n);
   constexpr int kMaxLevels = 256;
   const int tiles = blocks_for(n, kKldTile);
   HIPCHK(e, e->d_kld_hkey.reserve(table));

@@ -13,11 +13,10 @@ import threading
 import numpy as np
 
 from .pf import BpfError
-from .sharded import REBALANCE_MODES, RESAMPLE_FORMS, ShardedState
+from .sharded import RESAMPLE_FORMS, TREE_ROUTES, ShardedState, check_kld_modes, check_settings, even_counts
 
 EXCHANGE_NONE, EXCHANGE_MAILBOX, EXCHANGE_RCCL, EXCHANGE_LOCAL = 0, 1, 2, 3
 STATS_ROUTES = {1: "gathered", 2: "distributed", 3: "host"}
-TREE_ROUTES = {1: "device", 2: "host", 3: "bins", 4: "keys"}
 _dp = C.POINTER(C.c_double)
 
 
@@ -74,28 +73,19 @@ class LocalShardedFilter:
         self.cdf_miss = False
         self.stats_route = self.tree_route = None
         self.counts = [0] * self.world
-        if resample_form not in RESAMPLE_FORMS:
-            raise ValueError("resample_form: window or in_place")
+        form, mn_form, rebalance_code = check_settings(resample_form, multinomial_form, rebalance)
         self.resample_form, self.max_share, self.form_used = resample_form, float(max_share), "window"
-        for e in self.engines:
-            e.check(self.lib.bpf_shard_set_resample_form(e.h, RESAMPLE_FORMS[resample_form], self.max_share))
-        if multinomial_form not in RESAMPLE_FORMS:
-            raise ValueError("multinomial_form: window or in_place")
         self.multinomial_form = multinomial_form
-        for e in self.engines:
-            e.check(self.lib.bpf_shard_set_multinomial_form(e.h, RESAMPLE_FORMS[multinomial_form]))
-        if rebalance not in REBALANCE_MODES:
-            raise ValueError("rebalance: off or auto")
         self.rebalance_mode, self.trigger_share, self.rebalanced = rebalance, float(trigger_share), 0
         for e in self.engines:
-            e.check(self.lib.bpf_shard_set_rebalance(e.h, REBALANCE_MODES[rebalance], self.trigger_share))
+            e.check(self.lib.bpf_shard_set_resample_form(e.h, form, self.max_share))
+            e.check(self.lib.bpf_shard_set_multinomial_form(e.h, mn_form))
+            e.check(self.lib.bpf_shard_set_rebalance(e.h, rebalance_code, self.trigger_share))
         if kld_count is not None:
             for p in self.pfs:
                 p.setKldCount(int(kld_count))
         modes = [p.getKldCount() for p in self.pfs]
-        if len(set(modes)) != 1:
-            raise ValueError("LocalShardedFilter: the ranks use different KLD count modes %s" % modes)
-        self.kld_count = modes[0]
+        self.kld_count = check_kld_modes("LocalShardedFilter", modes)
         if timeout_ms is not None:
             self.set_timeout_ms(timeout_ms)
         if connect:
@@ -174,8 +164,7 @@ class LocalShardedFilter:
 
     # ---- starting the set
     def _even_share(self, n):
-        W = self.world
-        self.counts = [(n * (q + 1)) // W - (n * q) // W for q in range(W)]
+        self.counts = even_counts(n, self.world)
         self.sample_count = n
 
     def _first(self, r):

@@ -62,6 +62,9 @@ class _DevArray:
                                          "version": 2, "strides": None}
 
 
+_VIEW_DTYPES = {"<i8": torch.int64, "<f8": torch.float64, "<i4": torch.int32}
+
+
 class HipShardBackend:
     """Stage functions of include/badger_pf.h on one GPU.  Runs on torch's current stream so that
     torch copies / RCCL collectives and engine kernels are ordered without host syncs."""
@@ -141,6 +144,19 @@ class HipShardBackend:
         self.e.check(self.e.lib.bpf_shard_mailbox_error_stage(self.e.h, C.byref(a), C.byref(b)))
         return bool(a.value), bool(b.value)
 
+    def _view(self, ptr, shape, typestr="<i8"):
+        """Device tensor over engine memory the library handed out; an empty tensor of that shape when it holds
+        nothing (the pointer need not be valid then)."""
+        if 0 in shape:
+            return torch.empty(shape, dtype=_VIEW_DTYPES[typestr], device=self.device)
+        return torch.as_tensor(_DevArray(ptr, shape, typestr), device=self.device)
+
+    def _bins(self, fn, *args):
+        """(int64 [2, n_bins] device tensor, flag) of one of the bpf_shard_*_bins_dev entry points."""
+        p, n, flag = C.c_void_p(), C.c_int(), C.c_int()
+        self.e.check(fn(self.e.h, *args, C.byref(p), C.byref(n), C.byref(flag)))
+        return self._view(p.value, (2, n.value)), bool(flag.value)
+
     def _mb_view(self, ptr, shape, typestr):
         v = self._mb_views.get(ptr)
         if v is None:
@@ -171,14 +187,12 @@ class HipShardBackend:
             e.check(rc)
             return None
         # beam skipping: the per-beam agreement counts have to be summed over the shards first
-        p, n = C.c_void_p(), C.c_int()
-        e.check(lib.bpf_shard_beam_counts_dev(e.h, C.byref(p), C.byref(n)))
-        return torch.as_tensor(_DevArray(p.value, (n.value,), "<i4"), device=self.device)
+        return self.beam_counts()
 
     def beam_counts(self):
         p, n = C.c_void_p(), C.c_int()
         self.e.check(self.e.lib.bpf_shard_beam_counts_dev(self.e.h, C.byref(p), C.byref(n)))
-        return torch.as_tensor(_DevArray(p.value, (n.value,), "<i4"), device=self.device)
+        return self._view(p.value, (n.value,), "<i4")
 
     def score_finish(self, data, global_n):
         e = self.e
@@ -290,14 +304,14 @@ class HipShardBackend:
         caller)."""
         p, n = C.c_void_p(), C.c_size_t()
         self.e.check(self.e.lib.bpf_shard_inplace_xy_sums_dev(self.e.h, C.byref(p), C.byref(n)))
-        return torch.as_tensor(_DevArray(p.value, (n.value,), "<i8"), device=self.device)
+        return self._view(p.value, (n.value,))
 
     def inplace_converged(self, reduced, global_count):
         """one int64 word: this slice's particles near the mean of the reduced sums (reduced in place by the caller)"""
         p = C.c_void_p()
         self.e.check(self.e.lib.bpf_shard_inplace_converged_dev(self.e.h, C.c_void_p(reduced.data_ptr()),
                                                                 int(global_count), C.byref(p)))
-        return torch.as_tensor(_DevArray(p.value, (1,), "<i8"), device=self.device)
+        return self._view(p.value, (1,))
 
     def inplace_converged_finish(self, reduced_count, global_count):
         self.e.check(self.e.lib.bpf_shard_inplace_converged_finish(self.e.h, C.c_void_p(reduced_count.data_ptr()),
@@ -322,11 +336,7 @@ class HipShardBackend:
 
     def inplace_mn_bins(self):
         """(int64 [2, n_bins] device tensor: packed keys, first draw indices; key-out-of-range flag)."""
-        p, n, oor = C.c_void_p(), C.c_int(), C.c_int()
-        self.e.check(self.e.lib.bpf_shard_inplace_mn_bins_dev(self.e.h, C.byref(p), C.byref(n), C.byref(oor)))
-        if n.value == 0:
-            return torch.empty((2, 0), dtype=torch.int64, device=self.device), bool(oor.value)
-        return torch.as_tensor(_DevArray(p.value, (2, n.value), "<i8"), device=self.device), bool(oor.value)
+        return self._bins(self.e.lib.bpf_shard_inplace_mn_bins_dev)
 
     def inplace_mn_stop(self, all_bins, counts, pad):
         """all_bins: int64 [world, 2, pad] gathered lists.  (M, leaf_count, bin_count, counts of every rank, this rank's
@@ -367,9 +377,7 @@ class HipShardBackend:
         """int64 [4, out[rank]] device view: the bits of x / y / theta / w of this rank's outgoing samples."""
         p, n = C.c_void_p(), C.c_longlong()
         self.e.check(self.e.lib.bpf_shard_rebalance_export_dev(self.e.h, C.byref(p), C.byref(n)))
-        if n.value == 0:
-            return torch.empty((4, 0), dtype=torch.int64, device=self.device)
-        return torch.as_tensor(_DevArray(p.value, (4, n.value), "<i8"), device=self.device)
+        return self._view(p.value, (4, n.value))
 
     def rebalance_import(self, rows, rank_off, row_stride):
         """rows: the gathered int64 rows (None when nothing moves anywhere); rank q's row k at
@@ -423,9 +431,7 @@ class HipShardBackend:
         n = C.c_int()
         self.e.check(self.e.lib.bpf_shard_samples_dev(self.e.h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2]),
                                                       C.byref(p[3]), C.byref(n)))
-        if n.value == 0:
-            return torch.empty((4, 0), dtype=torch.float64, device=self.device)
-        return torch.stack([torch.as_tensor(_DevArray(q.value, (n.value,), "<f8"), device=self.device) for q in p])
+        return torch.stack([self._view(q.value, (n.value,), "<f8") for q in p])
 
     def stats_gathered(self, soa, global_n):
         """Gathered form on the whole set [4, global_n]: 1 installed, 0 declined (too many bins / clusters),
@@ -438,12 +444,7 @@ class HipShardBackend:
 
     def stats_local_bins(self, global_first):
         """(int64 [2, n_bins] device tensor: packed keys, global first indices; host-route flag)."""
-        p, n, hr = C.c_void_p(), C.c_int(), C.c_int()
-        self.e.check(self.e.lib.bpf_shard_stats_local_bins_dev(self.e.h, int(global_first), C.byref(p), C.byref(n),
-                                                               C.byref(hr)))
-        if n.value == 0:
-            return torch.empty((2, 0), dtype=torch.int64, device=self.device), bool(hr.value)
-        return torch.as_tensor(_DevArray(p.value, (2, n.value), "<i8"), device=self.device), bool(hr.value)
+        return self._bins(self.e.lib.bpf_shard_stats_local_bins_dev, int(global_first))
 
     def stats_label(self, all_bins, counts, pad):
         """all_bins: int64 [world, 2, pad] gathered lists; returns the global cluster count."""
@@ -457,7 +458,7 @@ class HipShardBackend:
         """int64 limb words of the slice's per-cluster sums (engine memory; reduced in place by the caller)."""
         p, n = C.c_void_p(), C.c_size_t()
         self.e.check(self.e.lib.bpf_shard_stats_local_sums_dev(self.e.h, C.byref(p), C.byref(n)))
-        return torch.as_tensor(_DevArray(p.value, (n.value,), "<i8"), device=self.device)
+        return self._view(p.value, (n.value,))
 
     def stats_finish(self, reduced):
         self.e.check(self.e.lib.bpf_shard_stats_finish_dev(self.e.h, C.c_void_p(reduced.data_ptr())))
@@ -486,9 +487,7 @@ class HipShardBackend:
         p, n = C.c_void_p(), C.c_int()
         self.e.check(self.e.lib.bpf_shard_pose_rows_dev(self.e.h, int(global_first), int(first), int(stride),
                                                         C.byref(p), C.byref(n)))
-        if n.value == 0:
-            return torch.empty((3, 0), dtype=torch.int64, device=self.device)
-        return torch.as_tensor(_DevArray(p.value, (3, n.value), "<i8"), device=self.device)
+        return self._view(p.value, (3, n.value))
 
     def pose_array_from_rows(self, rows, n):
         """rows: int64 [3, >= n] device tensor of gathered rows in global order; the [n, 7] float64 pose array."""
@@ -545,12 +544,7 @@ class HipShardBackend:
 
     def tree_local_bins(self, global_first):
         """(int64 [2, n_bins] device tensor: packed keys, global first indices; key-out-of-range flag)."""
-        p, n, oor = C.c_void_p(), C.c_int(), C.c_int()
-        self.e.check(self.e.lib.bpf_shard_tree_local_bins_dev(self.e.h, int(global_first), C.byref(p), C.byref(n),
-                                                              C.byref(oor)))
-        if n.value == 0:
-            return torch.empty((2, 0), dtype=torch.int64, device=self.device), bool(oor.value)
-        return torch.as_tensor(_DevArray(p.value, (2, n.value), "<i8"), device=self.device), bool(oor.value)
+        return self._bins(self.e.lib.bpf_shard_tree_local_bins_dev, int(global_first))
 
     def tree_merge(self, all_bins, counts, pad):
         """all_bins: int64 [world, 2, pad] gathered lists; installs and returns (leaf_count, bin_count)."""
@@ -564,10 +558,7 @@ class HipShardBackend:
         """int64 [3, n_local] device tensor: the raw histogram keys of the slice (the keys route only)."""
         p, n = C.c_void_p(), C.c_int()
         self.e.check(self.e.lib.bpf_shard_tree_local_keys_dev(self.e.h, C.byref(p), C.byref(n)))
-        if n.value == 0:
-            return torch.empty((3, 0), dtype=torch.int64, device=self.device)
-        k = torch.as_tensor(_DevArray(p.value, (n.value, 3), "<i4"), device=self.device)
-        return k.to(torch.int64).t().contiguous()
+        return self._view(p.value, (n.value, 3), "<i4").to(torch.int64).t().contiguous()
 
     def tree_from_keys(self, all_keys):
         """all_keys: int [global_n, 3] on the host, in index order; installs and returns (leaf_count, bin_count)."""
@@ -629,6 +620,30 @@ def pose_selection(counts, first, stride):
 RESAMPLE_WINDOW, RESAMPLE_IN_PLACE = 0, 1  # BPF_SHARD_RESAMPLE_*
 RESAMPLE_FORMS = {"window": RESAMPLE_WINDOW, "in_place": RESAMPLE_IN_PLACE}
 REBALANCE_MODES = {"off": 0, "auto": 1}  # BPF_SHARD_REBALANCE_*
+TREE_ROUTES = {1: "device", 2: "host", 3: "bins", 4: "keys"}  # BPF_SHARD_TREE_ROUTE_*
+
+
+def check_settings(resample_form, multinomial_form, rebalance):
+    """The settings ShardedFilter and LocalShardedFilter share; the library's codes of the three."""
+    if resample_form not in RESAMPLE_FORMS:
+        raise ValueError("resample_form: window or in_place")
+    if multinomial_form not in RESAMPLE_FORMS:
+        raise ValueError("multinomial_form: window or in_place")
+    if rebalance not in REBALANCE_MODES:
+        raise ValueError("rebalance: off or auto")
+    return RESAMPLE_FORMS[resample_form], RESAMPLE_FORMS[multinomial_form], REBALANCE_MODES[rebalance]
+
+
+def check_kld_modes(who, modes):
+    """Every rank computes the same stop rule, so every rank must count the same way; the mode."""
+    if len(set(int(m) for m in modes)) != 1:
+        raise ValueError("%s: the ranks use different KLD count modes %s" % (who, modes))
+    return int(modes[0])
+
+
+def even_counts(n, W):
+    """The even split of n samples over W ranks in global order: rank r holds [n r / W, n (r + 1) / W)."""
+    return [(n * (r + 1)) // W - (n * r) // W for r in range(W)]
 
 
 class ShardedState:
@@ -679,29 +694,22 @@ class ShardedFilter:
             backend.set_kld_count(int(kld_count))
         self.kld_count = int(backend.kld_count()) if hasattr(backend, "kld_count") else 0
         modes = self._all_gather(torch.tensor([self.kld_count], dtype=torch.int64, device=self.device)).cpu().tolist()
-        if len(set(int(m) for m in modes)) != 1:
-            raise ValueError("ShardedFilter: the ranks use different KLD count modes %s" % modes)
-        if resample_form not in RESAMPLE_FORMS:
-            raise ValueError("resample_form: window or in_place")
+        check_kld_modes("ShardedFilter", modes)
+        form, mn_form, rebalance_code = check_settings(resample_form, multinomial_form, rebalance)
         self.resample_form, self.max_share = resample_form, float(max_share)
         self.form_used = "window"  # of the last resample
         if resample_form != "window" or hasattr(backend, "set_resample_form"):
-            backend.set_resample_form(RESAMPLE_FORMS[resample_form], self.max_share)
-        if multinomial_form not in RESAMPLE_FORMS:
-            raise ValueError("multinomial_form: window or in_place")
+            backend.set_resample_form(form, self.max_share)
         self.multinomial_form = multinomial_form
         if multinomial_form != "window" or hasattr(backend, "set_multinomial_form"):
-            backend.set_multinomial_form(RESAMPLE_FORMS[multinomial_form])
-        if rebalance not in REBALANCE_MODES:
-            raise ValueError("rebalance: off or auto")
+            backend.set_multinomial_form(mn_form)
         self.rebalance_mode, self.trigger_share = rebalance, float(trigger_share)
         self.rebalanced = 0  # samples the last rebalance moved (0: the last resample needed none)
         if rebalance != "off" or hasattr(backend, "set_rebalance"):
-            backend.set_rebalance(REBALANCE_MODES[rebalance], self.trigger_share)
+            backend.set_rebalance(rebalance_code, self.trigger_share)
         # ranks that took different forms would wait in different exchanges: every rank must pass the same
-        mine = torch.tensor([float(RESAMPLE_FORMS[resample_form]), self.max_share, float(REBALANCE_MODES[rebalance]),
-                             self.trigger_share, float(RESAMPLE_FORMS[multinomial_form])], dtype=torch.float64,
-                            device=self.device)
+        mine = torch.tensor([float(form), self.max_share, float(rebalance_code), self.trigger_share, float(mn_form)],
+                            dtype=torch.float64, device=self.device)
         forms = self._all_gather(mine).reshape(self.world, 5).cpu().tolist()
         if any(f != forms[0] for f in forms):
             raise ValueError("ShardedFilter: the ranks use different resample forms / max_share / rebalance settings %s"
@@ -773,20 +781,25 @@ class ShardedFilter:
         if self.mailbox:
             self.b.mailbox_destroy()
         self.mailbox = False
-        self._windows.clear()
-        self._pose_views.clear()
-        self.totals = None
-        self._fused_totals = False
+        self._drop_exchange_caches()
 
     def try_mailbox(self):
         """(Re-)establish the mailbox between two steps; True when every rank could."""
         if not self.mailbox and hasattr(self.b, "mailbox_create") and self.world <= 16:
-            self._windows.clear()
-            self._pose_views.clear()
-            self.totals = None
-            self._fused_totals = False
+            self._drop_exchange_caches()
             self.mailbox = self._setup_mailbox()
         return self.mailbox
+
+    def _drop_totals(self):
+        """The weights changed (or are about to): the totals of the last update_sensor no longer describe them."""
+        self.totals = None
+        self._fused_totals = False
+
+    def _drop_exchange_caches(self):
+        """What belongs to the exchange in use: the window buffers, the views into them, the totals it delivered."""
+        self._windows.clear()
+        self._pose_views.clear()
+        self._drop_totals()
 
     # ---- a mailbox wait ran out of time (a rank stalled: page-in, debugger, a long host pause)
     def _is_exchange_error(self, err):
@@ -813,16 +826,12 @@ class ShardedFilter:
             raise RuntimeError("sharded filter: the ranks fell out of step around a mailbox time-out: %r" % (steps,))
         b.mailbox_destroy()
         self.mailbox = False
-        self._windows.clear()
-        self._pose_views.clear()
-        if committed:
-            self.totals = None
-        else:
+        self._drop_exchange_caches()
+        if not committed:
             totals = self._all_gather(b.local_total()).clone()
             if totals_failed:
                 b.normalize(totals, self.sample_count)
             self.totals = totals
-        self._fused_totals = False
         self.recoveries += 1
         self._remake_mailbox = True
 
@@ -875,7 +884,7 @@ class ShardedFilter:
         return v
 
     # ---- initWithGaussian / initWithPoseFn over the shards (particle_filter.cpp:105-163): no exchange for the poses
-    TREE_ROUTES = {1: "device", 2: "host", 3: "bins", 4: "keys"}
+    TREE_ROUTES = TREE_ROUTES
 
     def init_with_gaussian(self, mean, rotation, sigma):
         """ParticleFilter::initWithGaussian given PDFGaussian's decomposition (cr_ row-major 3x3, cd_): every rank
@@ -896,38 +905,52 @@ class ShardedFilter:
         self._after_init(*self._global_tree())
 
     def _even_share(self):
-        G, W, r = self.max_global, self.world, self.rank
-        self.counts = [(G * (q + 1)) // W - (G * q) // W for q in range(W)]
+        G = self.max_global
+        self.counts = self._even_counts(G)
         self.sample_count = G
-        return (G * r) // W, self.counts[r]
+        return (G * self.rank) // self.world, self.counts[self.rank]
+
+    def _even_counts(self, n):
+        return even_counts(n, self.world)
 
     def _after_init(self, leaf, bins):
         self._even_share()
         self.leaf_count, self.bin_count = leaf, bins
-        self.totals = None
-        self._fused_totals = False
+        self._drop_totals()
         self._stats_valid = False
         self.window_hint = self._first_window
         self.windows_used = 0
         if hasattr(self.b, "tree_last_route"):
             self.tree_route = self.TREE_ROUTES.get(self.b.tree_last_route())
 
+    def _exchange_bin_lists(self, bins, flag):
+        """The ranks' bin lists of a merge stage (shard_exchange_bin_lists in abi_shard_node.inl): (bin_counts,
+        any_flag, all_bins, pad).  Every rank's (n_bins, flag) pair crosses first; any_flag: some rank raised its
+        flag -- it travelled with the counts, so every rank turns off to its caller's other route here together, and
+        no list crosses (all_bins is None).  Otherwise all_bins = int64 [world, 2, pad], zero-filled."""
+        meta = torch.tensor([bins.shape[1], 1 if flag else 0], dtype=torch.int64, device=self.device)
+        meta = self._all_gather(meta).reshape(self.world, 2).cpu().tolist()
+        bin_counts = [int(m[0]) for m in meta]
+        if any(int(m[1]) for m in meta):
+            return bin_counts, True, None, max(max(bin_counts), 1)
+        all_bins, pad = self._gather_ragged(bins, bin_counts)
+        return bin_counts, False, all_bins.contiguous(), pad
+
+    def _concat_ragged(self, allv, counts):
+        """[world, rows, pad] of _gather_ragged without its padding: [rows, sum(counts)] in rank order."""
+        return torch.cat([allv[r, :, :counts[r]] for r in range(self.world)], dim=1)
+
     def _global_tree(self):
         """Leaf and bin count of the tree of the whole set from the ranks' bin lists (self.counts describes the
         slices); installed in the backend."""
-        b, W = self.b, self.world
-        bins, out_of_range = b.tree_local_bins(sum(self.counts[:self.rank]))
-        meta = torch.tensor([bins.shape[1], 1 if out_of_range else 0], dtype=torch.int64, device=self.device)
-        meta = self._all_gather(meta).reshape(W, 2).cpu().tolist()
-        bin_counts = [int(m[0]) for m in meta]
-        if any(int(m[1]) for m in meta):
-            # the keys route (the flag travelled with the counts: every rank turns off here together)
+        b = self.b
+        bin_counts, out_of_range, all_bins, pad = self._exchange_bin_lists(
+            *b.tree_local_bins(sum(self.counts[:self.rank])))
+        if out_of_range:
+            # the keys route: every raw key of the global set, in index order, through the host tree
             allk, _ = self._gather_ragged(b.tree_local_keys(), self.counts)
-            allk = allk.cpu()
-            keys = torch.cat([allk[r, :, :self.counts[r]] for r in range(W)], dim=1).t().contiguous().numpy()
-            return b.tree_from_keys(keys)
-        all_bins, pad = self._gather_ragged(bins, bin_counts)
-        return b.tree_merge(all_bins.contiguous(), bin_counts, pad)
+            return b.tree_from_keys(self._concat_ragged(allk.cpu(), self.counts).t().contiguous().numpy())
+        return b.tree_merge(all_bins, bin_counts, pad)
 
     # ---- motion update (Odom::updateAction): no exchange
     def update_action(self, odom, data):
@@ -943,9 +966,7 @@ class ShardedFilter:
             if self.b.mailbox_update_sensor(data, self.sample_count):
                 if self.b.max_beams() < 2:
                     # PlanarScanner::updateSensor is a no-op then (planar_scanner.cpp:128-129): nothing was posted
-                    self.totals = None
-                    self._fused_totals = False
-                    return
+                    return self._drop_totals()
                 self.totals = self.b.mailbox_totals()
                 self._fused_totals = True
                 return
@@ -1013,7 +1034,7 @@ class ShardedFilter:
             b.adopt(pose[0][lo:hi], pose[1][lo:hi], pose[2][lo:hi], hi - lo, M, leaf, bins)
             b.converged(pose[0][:M], pose[1][:M], M)
         b.set_rng_state(b.end_resample(M))
-        self.counts = [(M * (r + 1)) // W - (M * r) // W for r in range(W)]
+        self.counts = self._even_counts(M)
         self.sample_count = M
         self.leaf_count, self.bin_count = leaf, bins
         self.windows_used = 1
@@ -1027,9 +1048,14 @@ class ShardedFilter:
         counts, _, form = b.inplace_select(rng, count, sums, sums_are_totals, self.rank, self.world, self.flags)
         if form != RESAMPLE_IN_PLACE:
             return False
-        M = count
+        self.counts, self.sample_count = counts, count
+        return self._finish_in_place(count, counts, *self._global_tree())
+
+    def _finish_in_place(self, M, counts, leaf, bins):
+        """The tail of both in-place forms: the new slices (`counts` of every rank, M in all) are current in the
+        backends.  The limb words of the x / y sums and the count of updateConverged cross, then the books; True."""
+        b = self.b
         self.counts, self.sample_count = counts, M
-        leaf, bins = self._global_tree()
         words = b.inplace_xy_sums()
         self._all_reduce_sum(words)  # limb form: the lane-wise int64 sum is exact
         near = b.inplace_converged(words, M)
@@ -1044,7 +1070,7 @@ class ShardedFilter:
             self.tree_route = self.TREE_ROUTES.get(b.tree_last_route())
         self.rebalanced = 0
         if self.rebalance_mode == "auto" and max(counts) > self.trigger_share * ((M + self.world - 1) // self.world):
-            self.rebalance()  # every rank decides alike from the select's counts
+            self.rebalance()  # every rank decides alike from the same counts
         return True
 
     def _resample_in_place_mn(self, rng, sums, sums_are_totals):
@@ -1054,33 +1080,13 @@ class ShardedFilter:
         updateConverged."""
         b, W = self.b, self.world
         b.inplace_mn_select(rng, sums, sums_are_totals, self.rank, W, self.flags)
-        bins, out_of_range = b.inplace_mn_bins()
-        meta = torch.tensor([bins.shape[1], 1 if out_of_range else 0], dtype=torch.int64, device=self.device)
-        meta = self._all_gather(meta).reshape(W, 2).cpu().tolist()
-        if any(int(m[1]) for m in meta):
-            return False  # (the flag travelled with the counts: every rank turns off here together)
-        bin_counts = [int(m[0]) for m in meta]
-        all_bins, pad = self._gather_ragged(bins, bin_counts)
-        M, leaf, nbins, counts, _, form = b.inplace_mn_stop(all_bins.contiguous(), bin_counts, pad)
+        bin_counts, out_of_range, all_bins, pad = self._exchange_bin_lists(*b.inplace_mn_bins())
+        if out_of_range:
+            return False
+        M, leaf, nbins, counts, _, form = b.inplace_mn_stop(all_bins, bin_counts, pad)
         if form != RESAMPLE_IN_PLACE:
             return False
-        self.counts, self.sample_count = counts, M
-        words = b.inplace_xy_sums()
-        self._all_reduce_sum(words)  # limb form: the lane-wise int64 sum is exact
-        near = b.inplace_converged(words, M)
-        self._all_reduce_sum(near)
-        b.inplace_converged_finish(near, M)
-        b.set_rng_state(b.end_resample(M))
-        self.leaf_count, self.bin_count = leaf, nbins
-        self.windows_used = 0
-        self.totals = None
-        self.form_used = "in_place"
-        if hasattr(b, "tree_last_route"):
-            self.tree_route = self.TREE_ROUTES.get(b.tree_last_route())
-        self.rebalanced = 0
-        if self.rebalance_mode == "auto" and max(counts) > self.trigger_share * ((M + W - 1) // W):
-            self.rebalance()  # every rank decides alike from the owners' counts
-        return True
+        return self._finish_in_place(M, counts, leaf, nbins)
 
     # ---- the slices back to the even split, in global order (include/badger_pf.h, bpf_shard_rebalance_*)
     def rebalance(self):
@@ -1095,13 +1101,11 @@ class ShardedFilter:
         if moved:
             allr, pad = self._gather_ragged(b.rebalance_export(), out)
             b.rebalance_import(allr.contiguous(), [r * 4 * pad for r in range(W)], pad)
-            self.totals = None
-            self._fused_totals = False
+            self._drop_totals()
             self._stats_valid = False
         else:
             b.rebalance_import(None, None, 0)
-        G = sum(self.counts)
-        self.counts = [(G * (r + 1)) // W - (G * r) // W for r in range(W)]
+        self.counts = self._even_counts(sum(self.counts))
         self.rebalanced = moved
         return moved
 
@@ -1145,8 +1149,8 @@ class ShardedFilter:
 
     def _after_one_call_resample(self, M, leaf, bins, wins, hint):
         """The books after the engine's one-call resample made its new set current."""
-        b, W = self.b, self.world
-        self.counts = [(M * (r + 1)) // W - (M * r) // W for r in range(W)]
+        b = self.b
+        self.counts = self._even_counts(M)
         self.form_used = "window"
         if self._in_place_wanted() and b.slice()[2] == RESAMPLE_IN_PLACE:
             # the slices are uneven: every rank's count (the engines hold them; one small gather tells the host)
@@ -1156,8 +1160,7 @@ class ShardedFilter:
             self.rebalanced = b.rebalance_last() if self.rebalance_mode == "auto" else 0
         self.sample_count, self.leaf_count, self.bin_count = M, leaf, bins
         self.windows_used, self.window_hint = wins, hint
-        self.totals = None
-        self._fused_totals = False
+        self._drop_totals()
 
     def _in_place_wanted(self):
         """The in-place form is set for the resampler in use."""
@@ -1239,7 +1242,7 @@ class ShardedFilter:
             b.adopt(self.out[0, lo:hi], self.out[1, lo:hi], self.out[2, lo:hi], hi - lo, M, leaf, bins)
             b.converged(self.out[0, :M], self.out[1, :M], M)
         b.set_rng_state(b.end_resample(M))
-        self.counts = [(M * (r + 1)) // W - (M * r) // W for r in range(W)]
+        self.counts = self._even_counts(M)
         self.sample_count = M
         self.leaf_count, self.bin_count = leaf, bins
         self.window_hint = max(1024, ((M + M // 4) + 1023) // 1024 * 1024)
@@ -1249,8 +1252,7 @@ class ShardedFilter:
         """Bench helper: the shards were put back by pf.restore(); reset the bookkeeping."""
         self.counts = list(counts)
         self.sample_count = sum(counts)
-        self.totals = None
-        self._fused_totals = False
+        self._drop_totals()
         self._stats_valid = False
         self.leaf_count = leaf_count
 
@@ -1269,26 +1271,23 @@ class ShardedFilter:
         make the query (the exchanges are collective)."""
         if self._stats_valid:
             return
-        b, W, n = self.b, self.world, self.sample_count
+        b, n = self.b, self.sample_count
         route = None
         if n <= self.STATS_GATHER_MAX:
             # the tracking regime: the whole set on every rank, evaluated redundantly
             allv, _ = self._gather_ragged(b.stats_local_soa(), self.counts)
-            soa = torch.cat([allv[r, :, :self.counts[r]] for r in range(W)], dim=1).contiguous()
+            soa = self._concat_ragged(allv, self.counts).contiguous()
             handled = b.stats_gathered(soa, n)
             if handled > 0:
                 route = "gathered"
             elif handled < 0:
                 route = "host"
         if route is None:
-            bins, host_route = b.stats_local_bins(sum(self.counts[:self.rank]))
-            meta = torch.tensor([bins.shape[1], 1 if host_route else 0], dtype=torch.int64, device=self.device)
-            meta = self._all_gather(meta).reshape(W, 2).cpu().tolist()
-            bin_counts = [int(m[0]) for m in meta]
-            if any(int(m[1]) for m in meta):
-                route = "host"  # the flag travelled with the first exchange: every rank turns off here together
+            bin_counts, host_route, all_bins, pad = self._exchange_bin_lists(
+                *b.stats_local_bins(sum(self.counts[:self.rank])))
+            if host_route:
+                route = "host"
             else:
-                all_bins, pad = self._gather_ragged(bins, bin_counts)
                 b.stats_label(all_bins, bin_counts, pad)
                 sums = b.stats_local_sums()
                 self._all_reduce_sum(sums)  # limb form: the lane-wise int64 sum is exact
@@ -1297,8 +1296,7 @@ class ShardedFilter:
         if route == "host":
             local = torch.from_numpy(np.ascontiguousarray(b.stats_local_samples_host()[:, :4].T))
             allv, _ = self._gather_ragged(local.to(self.device), self.counts)
-            allv = allv.cpu()
-            b.stats_host(torch.cat([allv[r, :, :self.counts[r]] for r in range(W)], dim=1).T.contiguous().numpy())
+            b.stats_host(self._concat_ragged(allv.cpu(), self.counts).T.contiguous().numpy())
         self.stats_route = route
         self._stats_valid = True
 
@@ -1338,7 +1336,7 @@ class ShardedFilter:
         allr, _ = self._gather_ragged(mine, sel_counts)
         if not receives:
             return None
-        rows = torch.cat([allr[r, :, :sel_counts[r]] for r in range(self.world)], dim=1).contiguous()
+        rows = self._concat_ragged(allr, sel_counts).contiguous()
         return self.b.pose_array_from_rows(rows, count)
 
     def set_random_pose_generator(self, mode):

@@ -6,61 +6,13 @@
 // the concatenation of the ranks' slices.  tests/test_gpu_cpp_local_world.py compares.
 //
 // usage: local_world dir        (dir holds cfg.txt and the binary inputs, as for shard_node, and takes the dumps)
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <map>
-#include <sstream>
-#include <string>
-#include <vector>
-
-#include "badger_amcl_amd/adapter.hpp"
-#include "badger_pf.h"
-
-namespace amd = badger_amcl_amd;
-
-template <typename T>
-static std::vector<T> slurp(const std::string& path)
-{
-  FILE* f = std::fopen(path.c_str(), "rb");
-  if (!f) { std::perror(path.c_str()); std::exit(2); }
-  std::fseek(f, 0, SEEK_END);
-  const long n = std::ftell(f);
-  std::fseek(f, 0, SEEK_SET);
-  std::vector<T> v(n / sizeof(T));
-  if (!v.empty() && std::fread(v.data(), sizeof(T), v.size(), f) != v.size()) std::exit(2);
-  std::fclose(f);
-  return v;
-}
-
-struct Inputs
-{
-  std::string dir;
-  std::map<std::string, std::vector<double>> cfg;
-  std::vector<int32_t> cells;
-  std::vector<float> lut;
-  std::vector<double> samples, ranges, angles;
-  double v(const std::string& k, int i = 0) const { return cfg.at(k).at((size_t)i); }
-  int i(const std::string& k, int j = 0) const { return (int)v(k, j); }
-};
+#include "shard_harness.hpp"
 
 // map, scanner, model, odometry and the filter (GLOBAL bounds) of one engine
 static std::shared_ptr<amd::ParticleFilter> make_filter(std::shared_ptr<amd::Engine> eng, const Inputs& in)
 {
-  bpf_engine* e = eng->get();
-  eng->check(bpf_map2d_set(e, in.cells.data(), in.lut.data(), in.i("size"), in.i("size"), (float)in.v("origin", 0),
-                           (float)in.v("origin", 1), in.v("res"), in.v("max_dist")));
-  eng->check(bpf_planar_init(e, in.i("max_beams")));
-  eng->check(bpf_planar_set_model_likelihood_field(e, in.v("model_p", 0), in.v("model_p", 1), in.v("model_p", 2),
-                                                   in.v("max_dist")));
-  eng->check(bpf_planar_set_map_factors(e, in.v("map_factors", 0), in.v("map_factors", 1), in.v("map_factors", 2)));
-  const double pose[3] = { in.v("scanner_pose", 0), in.v("scanner_pose", 1), in.v("scanner_pose", 2) };
-  eng->check(bpf_planar_set_scanner_pose(e, pose));
-  eng->check(bpf_odom_set_model(e, BPF_ODOM_MODEL_DIFF_CORRECTED, 0.05, 0.04, 0.03, 0.02, 0.0));
-  auto pf = std::make_shared<amd::ParticleFilter>(eng, in.i("min_samples"), in.i("max_samples"), 0.0, 0.0, 85.0);
-  pf->setResampleModel(in.i("resampler") ? amd::PF_RESAMPLE_SYSTEMATIC : amd::PF_RESAMPLE_MULTINOMIAL);
-  pf->srand48(in.i("seed"));
+  auto pf = make_filter(eng, in, in.i("resampler") ? amd::PF_RESAMPLE_SYSTEMATIC : amd::PF_RESAMPLE_MULTINOMIAL);
+  eng->check(bpf_odom_set_model(eng->get(), BPF_ODOM_MODEL_DIFF_CORRECTED, 0.05, 0.04, 0.03, 0.02, 0.0));
   return pf;
 }
 
@@ -73,10 +25,8 @@ static std::vector<amd::PFSample> slice(const Inputs& in, int lo, int hi)
 
 static void dump(const Inputs& in, const std::string& name, const std::vector<amd::PFSample>& s)
 {
-  FILE* f = std::fopen((in.dir + "/" + name).c_str(), "wb");
-  if (!f) std::exit(3);
-  std::fwrite(s.data(), sizeof(amd::PFSample), s.size(), f);
-  std::fclose(f);
+  if (dump(in.dir + "/" + name, s.data(), s.size() * sizeof(amd::PFSample)) != 0)
+    std::exit(3);
 }
 
 static std::string pose_line(double w, const std::array<double, 3>& p, bool have, double cw, const std::array<double, 3>& cm)
@@ -92,24 +42,8 @@ int main(int argc, char** argv)
   if (argc != 2)
     return 2;
   Inputs in;
-  in.dir = argv[1];
-  {
-    std::ifstream f(in.dir + "/cfg.txt");
-    std::string line, key;
-    while (std::getline(f, line))
-    {
-      std::istringstream ss(line);
-      ss >> key;
-      double x;
-      while (ss >> x)
-        in.cfg[key].push_back(x);
-    }
-  }
-  in.cells = slurp<int32_t>(in.dir + "/cells.bin");
-  in.lut = slurp<float>(in.dir + "/lut.bin");
-  in.samples = slurp<double>(in.dir + "/samples.bin");
-  in.ranges = slurp<double>(in.dir + "/ranges.bin");
-  in.angles = slurp<double>(in.dir + "/angles.bin");
+  if (!in.read(argv[1]))
+    return 2;
   const int W = in.i("world"), n = (int)in.samples.size() / 4, cycles = in.i("cycles");
   try
   {
@@ -134,15 +68,8 @@ int main(int argc, char** argv)
     bpf_shard_exchange_mode(pfs[W - 1]->engine().get(), &mode);
     std::printf("local mode %d world %d\n", mode, local.world());
 
-    auto data = std::make_shared<amd::PlanarData>();
-    data->range_count_ = (int)in.ranges.size();
-    data->range_max_ = in.v("range_max");
-    data->ranges_ = in.ranges;
-    data->angles_ = in.angles;
-    auto odo = std::make_shared<amd::OdomData>();
-    odo->pose = { 1.0, 2.0, 0.3 };
-    odo->delta = { 0.03, -0.01, 0.02 };
-    odo->absolute_motion = { 0.03, 0.01, 0.02 };
+    const auto data = scan(in);
+    const auto odo = odom_data();
 
     // the ranks' slices dumped and concatenated; the global pose of the world next to one engine holding them
     auto compare = [&](int cycle, const char* step) {

@@ -6,46 +6,9 @@
 //
 // usage: shard_init dir world port flags kind n resampler size      (kind 0: Gaussian, 1: random free-space poses)
 // dir holds cells.bin lut.bin ranges.bin angles.bin mean.bin (3 doubles) and takes the dumps
-#include <sys/wait.h>
-#include <unistd.h>
+#include "shard_harness.hpp"
 
-#include <cstdio>
-#include <cstdlib>
-#include <functional>
-#include <string>
-#include <vector>
-
-#include "badger_amcl_amd/adapter.hpp"
-#include "badger_pf.h"
-
-namespace amd = badger_amcl_amd;
-
-template <typename T>
-static std::vector<T> slurp(const std::string& path)
-{
-  FILE* f = std::fopen(path.c_str(), "rb");
-  if (!f) { std::perror(path.c_str()); std::exit(2); }
-  std::fseek(f, 0, SEEK_END);
-  const long n = std::ftell(f);
-  std::fseek(f, 0, SEEK_SET);
-  std::vector<T> v(n / sizeof(T));
-  if (!v.empty() && std::fread(v.data(), sizeof(T), v.size(), f) != v.size()) std::exit(2);
-  std::fclose(f);
-  return v;
-}
-
-#define CHECK(e, call)                                                                                          \
-  do                                                                                                            \
-  {                                                                                                             \
-    const int _rc = (call);                                                                                     \
-    if (_rc != BPF_OK)                                                                                          \
-    {                                                                                                           \
-      std::fprintf(stderr, "rank %d: %s -> %d (%s)\n", rank, #call, _rc, (e) ? bpf_last_error_message(e) : ""); \
-      return 10 + _rc;                                                                                          \
-    }                                                                                                           \
-  } while (0)
-
-struct Inputs
+struct InitInputs
 {
   std::string dir;
   std::vector<int32_t> cells;
@@ -57,7 +20,7 @@ struct Inputs
 static const std::array<double, 9> kRot = { 0.8, -0.6, 0.0, 0.6, 0.8, 0.0, 0.0, 0.0, 1.0 };
 static const std::array<double, 3> kSigma = { 0.15, 0.1, 0.05 };
 
-static int setup(bpf_engine* e, const Inputs& in, int rank)
+static int setup(bpf_engine* e, const InitInputs& in, int rank)
 {
   const float origin = (float)((in.size / 2) * 0.05);
   CHECK(e, bpf_map2d_set(e, in.cells.data(), in.lut.data(), in.size, in.size, origin, origin, 0.05, 2.0));
@@ -69,7 +32,7 @@ static int setup(bpf_engine* e, const Inputs& in, int rank)
   return 0;
 }
 
-static std::shared_ptr<amd::ParticleFilter> make_filter(std::shared_ptr<amd::Engine> eng, const Inputs& in)
+static std::shared_ptr<amd::ParticleFilter> make_filter(std::shared_ptr<amd::Engine> eng, const InitInputs& in)
 {
   auto pf = std::make_shared<amd::ParticleFilter>(eng, 100, in.n, 0.0, 0.0, 85.0);  // the GLOBAL bounds on every rank
   pf->srand48(42);
@@ -78,28 +41,9 @@ static std::shared_ptr<amd::ParticleFilter> make_filter(std::shared_ptr<amd::Eng
   return pf;
 }
 
-static std::shared_ptr<amd::OdomData> odom_data()
+static int dump_set(bpf_engine* e, const InitInputs& in, int rank, const std::string& name)
 {
-  auto d = std::make_shared<amd::OdomData>();
-  d->pose = { 1.0, 2.0, 0.3 };
-  d->delta = { 0.03, -0.01, 0.02 };
-  d->absolute_motion = { 0.03, 0.01, 0.02 };
-  return d;
-}
-
-static int dump_set(bpf_engine* e, const Inputs& in, int rank, const std::string& name)
-{
-  std::vector<double> local((size_t)in.n * 4 + 4);
-  int got = 0;
-  bpf_pf_state st;
-  CHECK(e, bpf_pf_get_state(e, &st));
-  if (st.sample_count > 0)
-    CHECK(e, bpf_pf_get_samples(e, local.data(), in.n, &got));
-  FILE* f = std::fopen((in.dir + "/" + name).c_str(), "wb");
-  if (!f) return 3;
-  std::fwrite(local.data(), sizeof(double), (size_t)got * 4, f);
-  std::fclose(f);
-  return 0;
+  return dump_set(e, in.dir, in.n, rank, name);
 }
 
 static int print_state(bpf_engine* e, int rank, const char* tag, long long first, int global, int leaf, int bins)
@@ -115,7 +59,7 @@ static int print_state(bpf_engine* e, int rank, const char* tag, long long first
   return 0;
 }
 
-static int run_rank_body(const Inputs& in, int rank, int world, int port, int flags)
+static int run_rank_body(const InitInputs& in, int rank, int world, int port, int flags)
 {
   auto eng = std::make_shared<amd::Engine>(0);
   bpf_engine* e = eng->get();
@@ -170,7 +114,7 @@ static int run_rank_body(const Inputs& in, int rank, int world, int port, int fl
 }
 
 // the same filter on one engine through the ordinary entry points
-static int run_unsharded_body(const Inputs& in)
+static int run_unsharded_body(const InitInputs& in)
 {
   const int rank = -1;
   auto eng = std::make_shared<amd::Engine>(0);
@@ -206,19 +150,6 @@ static int run_unsharded_body(const Inputs& in)
   return 0;
 }
 
-static int guarded(int rank, const std::function<int()>& body)
-{
-  try
-  {
-    return body();
-  }
-  catch (const std::exception& ex)
-  {
-    std::fprintf(stderr, "rank %d: %s\n", rank, ex.what());
-    return 9;
-  }
-}
-
 int main(int argc, char** argv)
 {
   if (argc < 9)
@@ -226,7 +157,7 @@ int main(int argc, char** argv)
     std::fprintf(stderr, "usage: dir world port flags kind n resampler size\n");
     return 2;
   }
-  Inputs in;
+  InitInputs in;
   in.dir = argv[1];
   const int world = std::atoi(argv[2]), port = std::atoi(argv[3]), flags = std::atoi(argv[4]);
   in.kind = std::atoi(argv[5]);
@@ -240,30 +171,6 @@ int main(int argc, char** argv)
   in.mean = slurp<double>(in.dir + "/mean.bin");
   if (in.mean.size() != 3)
     return 2;
-  // fork BEFORE anything touches the GPU: every child initialises HIP for itself
-  std::vector<pid_t> kids;
-  for (int r = -1; r < world; ++r)
-  {
-    const pid_t pid = fork();
-    if (pid == 0)
-    {
-      const std::string out = in.dir + "/" + (r < 0 ? std::string("single") : "rank" + std::to_string(r)) + ".txt";
-      if (!std::freopen(out.c_str(), "w", stdout))
-        _exit(3);
-      const int rc = guarded(r, [&]() { return r < 0 ? run_unsharded_body(in) : run_rank_body(in, r, world, port, flags); });
-      std::fflush(stdout);
-      _exit(rc);
-    }
-    kids.push_back(pid);
-  }
-  int worst = 0;
-  for (pid_t pid : kids)
-  {
-    int status = 0;
-    waitpid(pid, &status, 0);
-    const int code = WIFEXITED(status) ? WEXITSTATUS(status) : 99;
-    if (code != 0)
-      worst = code;
-  }
-  return worst;
+  return fork_ranks(in.dir, world,
+                    [&](int r) { return r < 0 ? run_unsharded_body(in) : run_rank_body(in, r, world, port, flags); });
 }

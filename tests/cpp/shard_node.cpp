@@ -8,65 +8,20 @@
 //
 // usage: shard_node dir world port flags api        (dir holds cfg.txt and the binary inputs, and takes the dumps)
 // cfg.txt: "key value ..." lines; kind 0 planar scanner, 1 cloud scanner, 2 none (statistics and their timing only)
-#include <sys/wait.h>
-#include <unistd.h>
-
 #include <algorithm>
 #include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <map>
-#include <sstream>
-#include <string>
-#include <vector>
 
-#include "badger_amcl_amd/adapter.hpp"
-#include "badger_pf.h"
+#include "shard_harness.hpp"
 
-namespace amd = badger_amcl_amd;
-
-template <typename T>
-static std::vector<T> slurp(const std::string& path)
+struct NodeInputs : Inputs
 {
-  FILE* f = std::fopen(path.c_str(), "rb");
-  if (!f) { std::perror(path.c_str()); std::exit(2); }
-  std::fseek(f, 0, SEEK_END);
-  const long n = std::ftell(f);
-  std::fseek(f, 0, SEEK_SET);
-  std::vector<T> v(n / sizeof(T));
-  if (!v.empty() && std::fread(v.data(), sizeof(T), v.size(), f) != v.size()) std::exit(2);
-  std::fclose(f);
-  return v;
-}
-
-#define CHECK(e, call)                                                                                          \
-  do                                                                                                            \
-  {                                                                                                             \
-    const int _rc = (call);                                                                                     \
-    if (_rc != BPF_OK)                                                                                          \
-    {                                                                                                           \
-      std::fprintf(stderr, "rank %d: %s -> %d (%s)\n", rank, #call, _rc, (e) ? bpf_last_error_message(e) : ""); \
-      return 10 + _rc;                                                                                          \
-    }                                                                                                           \
-  } while (0)
-
-struct Inputs
-{
-  std::string dir;
-  std::map<std::string, std::vector<double>> cfg;
-  std::vector<int32_t> cells;
-  std::vector<float> lut, points;
+  std::vector<float> points;
   std::vector<uint32_t> pose_indices;
   std::vector<uint8_t> ratios;
-  std::vector<double> samples, ranges, angles;
-  double v(const std::string& k, int i = 0) const { return cfg.at(k).at((size_t)i); }
-  int i(const std::string& k, int j = 0) const { return (int)v(k, j); }
   bool cloud() const { return i("kind") == 1; }
 };
 
-static int setup(bpf_engine* e, const Inputs& in, int rank)
+static int setup(bpf_engine* e, const NodeInputs& in, int rank)
 {
   if (in.i("kind") == 2)
     ;  // no scanner: the statistics of the loaded set only
@@ -104,19 +59,9 @@ static int setup(bpf_engine* e, const Inputs& in, int rank)
   return 0;
 }
 
-static int dump_set(bpf_engine* e, const Inputs& in, int rank, const std::string& name)
+static int dump_set(bpf_engine* e, const NodeInputs& in, int rank, const std::string& name)
 {
-  std::vector<double> local((size_t)in.i("max_samples") * 4 + 4);
-  int got = 0;
-  bpf_pf_state st;
-  CHECK(e, bpf_pf_get_state(e, &st));
-  if (st.sample_count > 0)  // (a shard without samples: an empty file)
-    CHECK(e, bpf_pf_get_samples(e, local.data(), in.i("max_samples"), &got));
-  FILE* f = std::fopen((in.dir + "/" + name).c_str(), "wb");
-  if (!f) return 3;
-  std::fwrite(local.data(), sizeof(double), (size_t)got * 4, f);
-  std::fclose(f);
-  return 0;
+  return dump_set(e, in.dir, in.i("max_samples"), rank, name);
 }
 
 // the sharded filter of one rank behind either binding
@@ -129,21 +74,14 @@ struct Node
   std::unique_ptr<amd::ShardedParticleFilter> sf;
   int global = 0, leaf = 1, bins = 0, windows = 0, hint = 4096, miss = 0;
 
-  int update_sensor(const Inputs& in)
+  int update_sensor(const NodeInputs& in)
   {
     if (api == 1)
     {
       if (in.cloud())
         sf->updateSensorCloud(in.points.data(), (int)in.points.size() / 3);
       else
-      {
-        auto d = std::make_shared<amd::PlanarData>();
-        d->range_count_ = (int)in.ranges.size();
-        d->range_max_ = in.v("range_max");
-        d->ranges_ = in.ranges;
-        d->angles_ = in.angles;
-        sf->updateSensor(d);
-      }
+        sf->updateSensor(scan(in));
       return 0;
     }
     if (in.cloud())
@@ -232,7 +170,7 @@ static int print_stats(Node& nd, const char* tag, int cycle)
   return 0;
 }
 
-static int run_rank_body(const Inputs& in, Node& nd, int world, int port, int flags)
+static int run_rank_body(const NodeInputs& in, Node& nd, int world, int port, int flags)
 {
   const int rank = nd.rank;
   const int n_global = (int)in.samples.size() / 4;
@@ -252,12 +190,7 @@ static int run_rank_body(const Inputs& in, Node& nd, int world, int port, int fl
   else
     CHECK(e, bpf_pf_create(e, in.i("min_samples"), in.i("max_samples"), 0.0, 0.0, 85.0));
   CHECK(e, bpf_pf_srand48(e, in.i("seed")));
-  int lo = (int)((long long)n_global * rank / world), hi = (int)((long long)n_global * (rank + 1) / world);
-  if (in.cfg.count("cuts"))
-  {
-    lo = in.i("cuts", rank);
-    hi = in.i("cuts", rank + 1);
-  }
+  const int lo = in.cut(rank, world), hi = in.cut(rank + 1, world);
   if (hi > lo)
     CHECK(e, bpf_pf_set_samples(e, in.samples.data() + 4 * (size_t)lo, hi - lo, 1));
   else
@@ -355,24 +288,16 @@ static int run_rank_body(const Inputs& in, Node& nd, int world, int port, int fl
   return 0;
 }
 
-static int run_rank(const Inputs& in, int rank, int world, int port, int flags, int api)
+static int run_rank(const NodeInputs& in, int rank, int world, int port, int flags, int api)
 {
   Node nd;
   nd.api = api;
   nd.rank = rank;
-  try
-  {
-    return run_rank_body(in, nd, world, port, flags);
-  }
-  catch (const std::exception& ex)
-  {
-    std::fprintf(stderr, "rank %d: %s\n", rank, ex.what());
-    return 9;
-  }
+  return run_rank_body(in, nd, world, port, flags);
 }
 
 // the same filter on one engine through the ordinary entry points
-static int run_unsharded(const Inputs& in)
+static int run_unsharded(const NodeInputs& in)
 {
   const int rank = -1;
   const int n = (int)in.samples.size() / 4;
@@ -416,22 +341,9 @@ int main(int argc, char** argv)
     std::fprintf(stderr, "usage: dir world port flags api\n");
     return 2;
   }
-  Inputs in;
-  in.dir = argv[1];
-  std::ifstream cfg(in.dir + "/cfg.txt");
-  for (std::string line; std::getline(cfg, line);)
-  {
-    std::istringstream ss(line);
-    std::string key;
-    ss >> key;
-    for (double x; ss >> x;)
-      in.cfg[key].push_back(x);
-  }
-  if (!in.cfg.count("kind"))
-  {
-    std::fprintf(stderr, "no cfg.txt in %s\n", in.dir.c_str());
+  NodeInputs in;
+  if (!in.read_cfg(argv[1], "kind"))
     return 2;
-  }
   in.samples = slurp<double>(in.dir + "/samples.bin");
   if (in.i("kind") == 2)
     ;
@@ -442,38 +354,8 @@ int main(int argc, char** argv)
     in.points = slurp<float>(in.dir + "/points.bin");
   }
   else
-  {
-    in.cells = slurp<int32_t>(in.dir + "/cells.bin");
-    in.lut = slurp<float>(in.dir + "/lut.bin");
-    in.ranges = slurp<double>(in.dir + "/ranges.bin");
-    in.angles = slurp<double>(in.dir + "/angles.bin");
-  }
+    in.read_planar();
   const int world = std::atoi(argv[2]), port = std::atoi(argv[3]), flags = std::atoi(argv[4]), api = std::atoi(argv[5]);
-  // fork BEFORE anything touches the GPU: every child initialises HIP for itself
-  std::vector<pid_t> kids;
-  for (int r = -1; r < world; ++r)
-  {
-    const pid_t pid = fork();
-    if (pid == 0)
-    {
-      // every process prints into a file of its own (a line of a few thousand clusters is no atomic pipe write)
-      const std::string out = in.dir + "/" + (r < 0 ? std::string("single") : "rank" + std::to_string(r)) + ".txt";
-      if (!std::freopen(out.c_str(), "w", stdout))
-        _exit(3);
-      const int rc = r < 0 ? run_unsharded(in) : run_rank(in, r, world, port, flags, api);
-      std::fflush(stdout);
-      _exit(rc);
-    }
-    kids.push_back(pid);
-  }
-  int worst = 0;
-  for (pid_t pid : kids)
-  {
-    int status = 0;
-    waitpid(pid, &status, 0);
-    const int code = WIFEXITED(status) ? WEXITSTATUS(status) : 99;
-    if (code != 0)
-      worst = code;
-  }
-  return worst;
+  return fork_ranks(in.dir, world,
+                    [&](int r) { return r < 0 ? run_unsharded(in) : run_rank(in, r, world, port, flags, api); });
 }

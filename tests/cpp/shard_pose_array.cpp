@@ -7,51 +7,11 @@
 // <dir>/rank<r>.txt; tests/test_gpu_cpp_shard_pose_array.py compares.
 //
 // usage: shard_pose_array dir world port flags [cut_0 .. cut_world]     (dir holds samples.bin: n x 4 doubles)
-#include <sys/wait.h>
-#include <unistd.h>
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "badger_amcl_amd/adapter.hpp"
-#include "badger_pf.h"
-
-namespace amd = badger_amcl_amd;
-
-#define CHECK(e, call)                                                                                          \
-  do                                                                                                            \
-  {                                                                                                             \
-    const int _rc = (call);                                                                                     \
-    if (_rc != BPF_OK)                                                                                          \
-    {                                                                                                           \
-      std::fprintf(stderr, "rank %d: %s -> %d (%s)\n", rank, #call, _rc, (e) ? bpf_last_error_message(e) : ""); \
-      return 10 + _rc;                                                                                          \
-    }                                                                                                           \
-  } while (0)
-
-static std::vector<double> slurp(const std::string& path)
-{
-  FILE* f = std::fopen(path.c_str(), "rb");
-  if (!f) { std::perror(path.c_str()); std::exit(2); }
-  std::fseek(f, 0, SEEK_END);
-  const long n = std::ftell(f);
-  std::fseek(f, 0, SEEK_SET);
-  std::vector<double> v(n / sizeof(double));
-  if (!v.empty() && std::fread(v.data(), sizeof(double), v.size(), f) != v.size()) std::exit(2);
-  std::fclose(f);
-  return v;
-}
+#include "shard_harness.hpp"
 
 static int dump(const std::string& path, const double* p, size_t n_doubles)
 {
-  FILE* f = std::fopen(path.c_str(), "wb");
-  if (!f) return 3;
-  std::fwrite(p, sizeof(double), n_doubles, f);
-  std::fclose(f);
-  return 0;
+  return dump(path, static_cast<const void*>(p), n_doubles * sizeof(double));
 }
 
 struct Query
@@ -70,7 +30,7 @@ static long long exchanges(bpf_engine* e)
   return x;
 }
 
-static int run_rank_body(const std::string& dir, const std::vector<double>& samples, const std::vector<int>& cuts, int rank,
+static int run_rank(const std::string& dir, const std::vector<double>& samples, const std::vector<int>& cuts, int rank,
                          int world, int port, int flags)
 {
   const int n_global = (int)samples.size() / 4;
@@ -151,20 +111,6 @@ static int run_rank_body(const std::string& dir, const std::vector<double>& samp
   return 0;
 }
 
-static int run_rank(const std::string& dir, const std::vector<double>& samples, const std::vector<int>& cuts, int rank,
-                    int world, int port, int flags)
-{
-  try
-  {
-    return run_rank_body(dir, samples, cuts, rank, world, port, flags);
-  }
-  catch (const std::exception& ex)
-  {
-    std::fprintf(stderr, "rank %d: %s\n", rank, ex.what());
-    return 9;
-  }
-}
-
 // the whole set on one engine through the ordinary entry point
 static int run_unsharded(const std::string& dir, const std::vector<double>& samples)
 {
@@ -196,37 +142,14 @@ int main(int argc, char** argv)
   }
   const std::string dir = argv[1];
   const int world = std::atoi(argv[2]), port = std::atoi(argv[3]), flags = std::atoi(argv[4]);
-  const std::vector<double> samples = slurp(dir + "/samples.bin");
+  const std::vector<double> samples = slurp<double>(dir + "/samples.bin");
   const int n = (int)samples.size() / 4;
   std::vector<int> cuts;
   for (int r = 0; r <= world; ++r)
     cuts.push_back(argc >= 6 + world ? std::atoi(argv[5 + r]) : (int)((long long)n * r / world));
   if (cuts.front() != 0 || cuts.back() != n)
     return 2;
-  // fork BEFORE anything touches the GPU: every child initialises HIP for itself
-  std::vector<pid_t> kids;
-  for (int r = -1; r < world; ++r)
-  {
-    const pid_t pid = fork();
-    if (pid == 0)
-    {
-      const std::string out = dir + "/" + (r < 0 ? std::string("single") : "rank" + std::to_string(r)) + ".txt";
-      if (!std::freopen(out.c_str(), "w", stdout))
-        _exit(3);
-      const int rc = r < 0 ? run_unsharded(dir, samples) : run_rank(dir, samples, cuts, r, world, port, flags);
-      std::fflush(stdout);
-      _exit(rc);
-    }
-    kids.push_back(pid);
-  }
-  int worst = 0;
-  for (pid_t pid : kids)
-  {
-    int status = 0;
-    waitpid(pid, &status, 0);
-    const int code = WIFEXITED(status) ? WEXITSTATUS(status) : 99;
-    if (code != 0)
-      worst = code;
-  }
-  return worst;
+  return fork_ranks(dir, world, [&](int r) {
+    return r < 0 ? run_unsharded(dir, samples) : run_rank(dir, samples, cuts, r, world, port, flags);
+  });
 }

@@ -5,42 +5,9 @@
 // bpf_shard_update_resample.  Every process writes what it ends up with; the Python test compares.
 //
 // usage: shard_two_procs cells lut samples ranges angles size world port flags out_prefix
-#include <sys/wait.h>
-#include <unistd.h>
+#include "shard_harness.hpp"  // slurp and CHECK; the calls are the C ABI's
 
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
-
-#include "badger_pf.h"
-
-template <typename T>
-static std::vector<T> slurp(const char* path)
-{
-  FILE* f = std::fopen(path, "rb");
-  if (!f) { std::perror(path); std::exit(2); }
-  std::fseek(f, 0, SEEK_END);
-  const long n = std::ftell(f);
-  std::fseek(f, 0, SEEK_SET);
-  std::vector<T> v(n / sizeof(T));
-  if (std::fread(v.data(), sizeof(T), v.size(), f) != v.size()) std::exit(2);
-  std::fclose(f);
-  return v;
-}
-
-#define CHECK(e, call)                                                                                          \
-  do                                                                                                            \
-  {                                                                                                             \
-    const int _rc = (call);                                                                                     \
-    if (_rc != BPF_OK)                                                                                          \
-    {                                                                                                           \
-      std::fprintf(stderr, "rank %d: %s -> %d (%s)\n", rank, #call, _rc, (e) ? bpf_last_error_message(e) : ""); \
-      return 10 + _rc;                                                                                          \
-    }                                                                                                           \
-  } while (0)
-
-struct Inputs
+struct FileInputs
 {
   std::vector<int32_t> cells;
   std::vector<float> lut;
@@ -48,7 +15,7 @@ struct Inputs
   int size;
 };
 
-static int setup(bpf_engine* e, const Inputs& in, int rank, int n_global)
+static int setup(bpf_engine* e, const FileInputs& in, int rank, int n_global)
 {
   const float origin = (float)((in.size / 2) * 0.05);
   CHECK(e, bpf_map2d_set(e, in.cells.data(), in.lut.data(), in.size, in.size, origin, origin, 0.05, 2.0));
@@ -69,7 +36,7 @@ static void dump(const std::string& path, const std::vector<double>& v, int coun
   std::fclose(f);
 }
 
-static int run_rank(const Inputs& in, int rank, int world, int port, int flags, const std::string& prefix)
+static int run_rank(const FileInputs& in, int rank, int world, int port, int flags, const std::string& prefix)
 {
   const int n_global = (int)in.samples.size() / 4;
   bpf_engine* e = nullptr;
@@ -102,7 +69,7 @@ static int run_rank(const Inputs& in, int rank, int world, int port, int flags, 
 }
 
 // the same filter on one engine through the ordinary entry points
-static int run_unsharded(const Inputs& in, const std::string& prefix)
+static int run_unsharded(const FileInputs& in, const std::string& prefix)
 {
   const int rank = -1;
   const int n = (int)in.samples.size() / 4;
@@ -138,7 +105,7 @@ int main(int argc, char** argv)
     std::fprintf(stderr, "usage: cells lut samples ranges angles size world port flags out_prefix\n");
     return 2;
   }
-  Inputs in;
+  FileInputs in;
   in.cells = slurp<int32_t>(argv[1]);
   in.lut = slurp<float>(argv[2]);
   in.samples = slurp<double>(argv[3]);

@@ -2,11 +2,11 @@
 filter unsharded, in ONE program (tests/cpp/local_world.cpp): three cycles of motion, sensor, resample with the
 comparisons of tests/test_gpu_cpp_shard_node.py::_check_cycles, and the global pose, cluster 0 and the particle cloud
 bit for bit those of one engine holding the concatenation of the ranks' slices."""
-import subprocess
+import os
 
-import numpy as np
 import pytest
 
+import cpp_driver
 from test_local_world_cpu import compile_local_world
 
 W, CYCLES = 8, 3
@@ -22,13 +22,8 @@ def test_local_sharded_particle_filter_beside_an_unsharded_filter(tmp_path, orc)
                                min_samples=[100])
     exe = compile_local_world(tmp_path)
     d = tmp_path / "case"
-    d.mkdir()
-    with open(d / "cfg.txt", "w") as f:
-        for k, v in cfg.items():
-            f.write(k + " " + " ".join(repr(float(x)) for x in v) + "\n")
-    for name, arr in arrays.items():
-        np.ascontiguousarray(arr).tofile(str(d / (name + ".bin")))
-    res = subprocess.run([str(exe), str(d)], capture_output=True, text=True, timeout=120)
+    cpp_driver.write_case(d, cfg, arrays)
+    res = cpp_driver.run_driver(exe, [d], timeout=120, env=dict(os.environ))  # (one process: no IPC environment)
     assert res.returncode == 0, res.stdout + res.stderr
     lines = res.stdout.splitlines()
     assert lines[0] == "before mode 0" and lines[1] == "local mode 3 world %d" % W and lines[-1] == "after mode 0"

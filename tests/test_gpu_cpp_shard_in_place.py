@@ -6,16 +6,14 @@ resample whatever M is: the (count, flag) words and the bin lists of the new tre
 the count of updateConverged."""
 import os
 import pathlib
-import socket
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import cpp_driver  # noqa: E402
 import shard_in_place_ref as ipr  # noqa: E402
 
 EXCHANGES = 4  # recorded: per in-place resample, on the mailbox, RCCL and the local exchange alike
@@ -24,12 +22,7 @@ FORCE_COLLECTIVE = 1
 
 
 def compile_driver(tmp_path):
-    exe = pathlib.Path(tmp_path) / "shard_in_place"
-    libdir = os.path.join(ROOT, "badger_amcl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "shard_in_place.cpp"), "-o", str(exe),
-                           "-L", libdir, "-lbadger_pf_hip", "-Wl,-rpath," + libdir])
-    return exe
+    return cpp_driver.compile_driver(tmp_path, "shard_in_place")
 
 
 def test_driver_compiles_and_links(tmp_path):
@@ -44,43 +37,25 @@ def _fields(line):
 
 
 def _run(tmp_path, orc, sc, mode, world, flags=0, cuts=None):
-    from badger_amcl_amd import synth
     n = sc.samples.shape[0]
     tree = orc.KDTree()
     for p in sc.samples[:, :3]:
         tree.insert_pose(p, 1.0)
-    cfg = dict(size=[sc.size], origin=[float(np.float32(sc.origin[0])), float(np.float32(sc.origin[1]))], res=[sc.res],
-               max_dist=[sc.max_dist], max_beams=[sc.ranges.shape[0]],
-               model_p=[synth.LF_DEFAULTS[k] for k in ("z_hit", "z_rand", "sigma_hit")],
-               map_factors=list(sc.map_factors), scanner_pose=list(sc.scanner_pose), range_max=[sc.range_max],
-               min_samples=[100], max_samples=[n], seed=[21], kld=[0], leaf=[tree.leaf_count()],
-               max_share=[float(world)])
+    cfg, arrays = cpp_driver.planar_case(sc, min_samples=[100], max_samples=[n], seed=[21], kld=[0],
+                                         leaf=[tree.leaf_count()], max_share=[float(world)])
     if cuts is not None:
         cfg["cuts"] = cuts
     d = pathlib.Path(tmp_path) / ("case_%d_%d_%d" % (mode, world, len(list(pathlib.Path(tmp_path).glob("case_*")))))
-    d.mkdir()
-    with open(d / "cfg.txt", "w") as f:
-        for k, v in cfg.items():
-            f.write(k + " " + " ".join(repr(float(x)) for x in v) + "\n")
-    arrays = dict(cells=sc.cells.astype(np.int32), lut=np.asarray(sc.lut, dtype=np.float32), samples=sc.samples,
-                  ranges=sc.ranges, angles=sc.angles)
-    for name, arr in arrays.items():
-        np.ascontiguousarray(arr).tofile(str(d / (name + ".bin")))
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    res = subprocess.run([str(compile_driver(tmp_path)), str(d), str(mode), str(world), str(port), str(flags)],
-                         capture_output=True, text=True, env=env, timeout=120)  # world + 1 <= 4 processes on the GPU
+    cpp_driver.write_case(d, cfg, arrays)
+    res = cpp_driver.run_driver(compile_driver(tmp_path), [d, mode, world, cpp_driver.free_port(), flags],
+                                timeout=120)  # world + 1 <= 4 processes on the GPU
     assert res.returncode == 0, res.stdout + res.stderr
     if mode == 0:
         lines = res.stdout.splitlines()
         modes = [l for l in lines if l.startswith("mode ")]
         assert "next step ok form 1" in lines
     else:
-        lines = []
-        for name in ["rank%d" % r for r in range(world)] + ["single"]:
-            lines += open(d / (name + ".txt")).read().splitlines()
+        lines = cpp_driver.output_lines(d, world)
         modes = [l for l in lines if l.startswith("mode ")]
     ranks = [_fields(l) for l in lines if l.startswith("rank ")]
     single = _fields([l for l in lines if l.startswith("single ")][0])

@@ -5,16 +5,14 @@ unsharded set sorted stably by the rank that holds each sample's source particle
 distinct, so a pose names its source), bit for bit; windows_out is 0; the exchange count rises by EXCHANGES."""
 import os
 import pathlib
-import socket
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import cpp_driver  # noqa: E402
 import shard_in_place_mn_ref as mnr  # noqa: E402
 
 EXCHANGES = 4  # the (count, flag) words, the bin lists, the limb words of the x / y sums, the count of updateConverged
@@ -22,12 +20,7 @@ MODE_MAILBOX, MODE_LOCAL = 1, 3
 
 
 def compile_driver(tmp_path):
-    exe = pathlib.Path(tmp_path) / "shard_in_place_mn"
-    libdir = os.path.join(ROOT, "badger_amcl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "shard_in_place_mn.cpp"), "-o", str(exe),
-                           "-L", libdir, "-lbadger_pf_hip", "-Wl,-rpath," + libdir])
-    return exe
+    return cpp_driver.compile_driver(tmp_path, "shard_in_place_mn")
 
 
 def test_driver_compiles_and_links(tmp_path):
@@ -42,36 +35,19 @@ def _fields(line):
 
 
 def _run(tmp_path, sc, mode, world):
-    from badger_amcl_amd import synth
     n = sc.samples.shape[0]
-    cfg = dict(size=[sc.size], origin=[float(np.float32(sc.origin[0])), float(np.float32(sc.origin[1]))], res=[sc.res],
-               max_dist=[sc.max_dist], max_beams=[sc.ranges.shape[0]],
-               model_p=[synth.LF_DEFAULTS[k] for k in ("z_hit", "z_rand", "sigma_hit")],
-               map_factors=list(sc.map_factors), scanner_pose=list(sc.scanner_pose), range_max=[sc.range_max],
-               min_samples=[100], max_samples=[n], seed=[21], kld=[0], leaf=[0], max_share=[float(world)])
+    cfg, arrays = cpp_driver.planar_case(sc, min_samples=[100], max_samples=[n], seed=[21], kld=[0], leaf=[0],
+                                         max_share=[float(world)])
     d = pathlib.Path(tmp_path) / ("case_%d_%d" % (mode, world))
-    d.mkdir()
-    with open(d / "cfg.txt", "w") as f:
-        for k, v in cfg.items():
-            f.write(k + " " + " ".join(repr(float(x)) for x in v) + "\n")
-    arrays = dict(cells=sc.cells.astype(np.int32), lut=np.asarray(sc.lut, dtype=np.float32), samples=sc.samples,
-                  ranges=sc.ranges, angles=sc.angles)
-    for name, arr in arrays.items():
-        np.ascontiguousarray(arr).tofile(str(d / (name + ".bin")))
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    res = subprocess.run([str(compile_driver(tmp_path)), str(d), str(mode), str(world), str(port), "0"],
-                         capture_output=True, text=True, env=env, timeout=120)  # world + 1 <= 3 processes on the GPU
+    cpp_driver.write_case(d, cfg, arrays)
+    res = cpp_driver.run_driver(compile_driver(tmp_path), [d, mode, world, cpp_driver.free_port(), 0],
+                                timeout=120)  # world + 1 <= 3 processes on the GPU
     assert res.returncode == 0, res.stdout + res.stderr
     if mode == 0:
         lines = res.stdout.splitlines()
         assert "next step ok form 1" in lines
     else:
-        lines = []
-        for name in ["rank%d" % r for r in range(world)] + ["single"]:
-            lines += open(d / (name + ".txt")).read().splitlines()
+        lines = cpp_driver.output_lines(d, world)
     modes = [l for l in lines if l.startswith("mode ")]
     ranks = [_fields(l) for l in lines if l.startswith("rank ")]
     single = _fields([l for l in lines if l.startswith("single ")][0])

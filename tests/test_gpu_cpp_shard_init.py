@@ -3,27 +3,20 @@ badger_amcl_amd::ShardedParticleFilter::initWithGaussian / initWithRandomPoses (
 exchange of the bin lists over the engine's own exchange, the global set's tree), updateAction, updateSensor,
 updateResample and getMaxWeightPose -- against an unsharded ParticleFilter in the same program.  Worlds 2 and 3 over the
 mailbox, world 1 over RCCL."""
-import os
 import re
-import socket
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_driver
 from scenario import Scenario
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 6000
 
 
 def _compile(tmp_path):
-    exe = tmp_path / "shard_init"
-    libdir = os.path.join(ROOT, "badger_amcl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "shard_init.cpp"), "-o", str(exe),
-                           "-L", libdir, "-lbadger_pf_hip", "-Wl,-rpath," + libdir])
-    return exe
+    return cpp_driver.compile_driver(tmp_path, "shard_init", "-Wall", "-Werror")
 
 
 def test_shard_init_driver_compiles():
@@ -62,15 +55,11 @@ def test_cpp_ranks_init_and_run_a_cycle(tmp_path, orc, world, flags, kind, resam
     world size 1).  kind 0: Gaussian around the scenario's pose (a handful of bins); kind 1: random free-space poses."""
     exe = _compile(tmp_path)
     sc = Scenario(orc, size=400, n=256, beams=91)
-    for name, arr in (("cells", sc.cells.astype(np.int32)), ("lut", sc.lut.astype(np.float32)),
-                      ("ranges", sc.ranges), ("angles", sc.angles), ("mean", np.asarray(sc.pose, dtype=np.float64))):
-        np.ascontiguousarray(arr).tofile(str(tmp_path / (name + ".bin")))
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    res = subprocess.run([str(exe), str(tmp_path), str(world), str(port), str(flags), str(kind), str(N), str(resampler),
-                          "400"], capture_output=True, text=True, env=env, timeout=240)
+    cpp_driver.write_case(tmp_path, None, dict(cells=sc.cells.astype(np.int32), lut=sc.lut.astype(np.float32),
+                                               ranges=sc.ranges, angles=sc.angles,
+                                               mean=np.asarray(sc.pose, dtype=np.float64)))
+    res = cpp_driver.run_driver(exe, [tmp_path, world, cpp_driver.free_port(), flags, kind, N, resampler, "400"],
+                                timeout=240)
     assert res.returncode == 0, res.stdout + res.stderr
     one = _parse(str(tmp_path / "single.txt"))
     ranks = [_parse(str(tmp_path / ("rank%d.txt" % r))) for r in range(world)]

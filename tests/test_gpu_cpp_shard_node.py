@@ -8,13 +8,13 @@ A shard WITHOUT samples cannot take a sensor update (bpf_shard_score_planar refu
 the split with an empty shard is queried as loaded; every other set is queried as loaded, after each sensor update
 and after each resample."""
 import os
-import socket
 import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cpp_driver
+
 NEW_ABI = ("bpf_shard_update_sensor_cloud", "bpf_shard_compute_cluster_stats", "bpf_shard_get_max_weight_pose",
            "bpf_shard_exchange_count")
 WORLDS = [(2, 2), (3, 2), (1, 1)]  # (world, bootstrap flags): see test_gpu_cpp_shards.py for why these three
@@ -22,12 +22,7 @@ KEYS = ["n", "set_mean", "set_cov", "weight", "mean", "count", "cov", "best_w", 
 
 
 def _compile(tmp_path):
-    exe = tmp_path / "shard_node"
-    libdir = os.path.join(ROOT, "badger_amcl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "shard_node.cpp"), "-o", str(exe),
-                           "-L", libdir, "-lbadger_pf_hip", "-Wl,-rpath," + libdir])
-    return exe
+    return cpp_driver.compile_driver(tmp_path, "shard_node")
 
 
 def test_shard_node_compiles_and_the_new_entry_points_are_exported():
@@ -48,35 +43,18 @@ def test_shard_node_compiles_and_the_new_entry_points_are_exported():
 
 # ------------------------------------------------------------------------------------------------ running the program
 def _planar_case(sc, model="lf", beamskip=None, **kw):
-    from badger_amcl_amd import synth
-    cfg = dict(kind=[0], size=[sc.size], origin=[float(np.float32(sc.origin[0])), float(np.float32(sc.origin[1]))],
-               res=[sc.res], max_dist=[sc.max_dist], max_beams=[sc.ranges.shape[0]], model=[1 if model == "prob" else 0],
-               model_p=[synth.LF_DEFAULTS[k] for k in ("z_hit", "z_rand", "sigma_hit")],
-               beamskip=beamskip or [0, 0.5, 0.3, 0.9], map_factors=list(sc.map_factors),
-               scanner_pose=list(sc.scanner_pose), range_max=[sc.range_max])
-    cfg.update(kw)
-    arrays = dict(cells=sc.cells.astype(np.int32), lut=np.asarray(sc.lut, dtype=np.float32), samples=sc.samples,
-                  ranges=sc.ranges, angles=sc.angles)
-    return cfg, arrays
+    return cpp_driver.planar_case(sc, kind=[0], model=[1 if model == "prob" else 0],
+                                  beamskip=beamskip or [0, 0.5, 0.3, 0.9], **kw)
 
 
 def _run(tmp_path, cfg, arrays, world, flags, api):
     """Runs the program; returns (per-rank lines, the unsharded process's lines, directory of the dumps)."""
     exe = _compile(tmp_path)
     d = tmp_path / "case"
-    d.mkdir()
     cfg = dict(dict(min_samples=[100], seed=[42], cycles=[2], stats=[0], stats_host=[0]), **cfg)
-    with open(d / "cfg.txt", "w") as f:
-        for k, v in cfg.items():
-            f.write(k + " " + " ".join(repr(float(x)) for x in v) + "\n")
-    for name, arr in arrays.items():
-        np.ascontiguousarray(arr).tofile(str(d / (name + ".bin")))
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    res = subprocess.run([str(exe), str(d), str(world), str(port), str(flags), str(api)], capture_output=True, text=True,
-                         env=env, timeout=240)  # world + 1 <= 4 processes on the GPU
+    cpp_driver.write_case(d, cfg, arrays)
+    res = cpp_driver.run_driver(exe, [d, world, cpp_driver.free_port(), flags, api],
+                                timeout=240)  # world + 1 <= 4 processes on the GPU
     assert res.returncode == 0, res.stdout + res.stderr
     # (only the program's own lines: RCCL prints a banner of its own into the same stream)
     ranks = [[l for l in open(d / ("rank%d.txt" % r)).read().splitlines() if l.startswith("rank %d " % r)]

@@ -2,14 +2,13 @@
 bpf_shard_get_pose_array -- through the C call and through badger_amcl_amd::ShardedParticleFilter::getPoseArray -- with
 every exchange on the engine's own transport.  The ranks share the one GPU of the box; one more process holds the whole
 set on one engine and calls bpf_pf_get_pose_array.  Every received array is that one, bit for bit."""
-import os
-import socket
 import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cpp_driver
+
 NEW_ABI = ("bpf_pf_get_pose_array", "bpf_shard_pose_rows_dev", "bpf_pose_array_from_rows_dev",
            "bpf_shard_get_pose_array")
 WORLDS = [(2, 2), (3, 2), (1, 1)]  # (world, bootstrap flags): see test_gpu_cpp_shards.py for why these three
@@ -18,12 +17,7 @@ QUERIES = {"root0": (0, 0, 1), "all": (-1, 3, 7)}  # kQueries of the driver: (ro
 
 
 def _compile(tmp_path):
-    exe = tmp_path / "shard_pose_array"
-    libdir = os.path.join(ROOT, "badger_amcl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "shard_pose_array.cpp"), "-o", str(exe),
-                           "-L", libdir, "-lbadger_pf_hip", "-Wl,-rpath," + libdir])
-    return exe
+    return cpp_driver.compile_driver(tmp_path, "shard_pose_array")
 
 
 def test_driver_compiles_and_the_new_entry_points_are_exported():
@@ -64,15 +58,10 @@ def _fields(line, names):
 def test_pose_array_from_cpp(tmp_path, world, flags, cuts):
     exe = _compile(tmp_path)
     d = tmp_path / "case"
-    d.mkdir()
     s = _samples()
-    s.tofile(str(d / "samples.bin"))
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    args = [str(exe), str(d), str(world), str(port), str(flags)] + [str(c) for c in (cuts or ())]
-    res = subprocess.run(args, capture_output=True, text=True, env=env, timeout=120)  # world + 1 <= 4 processes
+    cpp_driver.write_case(d, None, dict(samples=s))
+    res = cpp_driver.run_driver(exe, [d, world, cpp_driver.free_port(), flags] + list(cuts or ()),
+                                timeout=120)  # world + 1 <= 4 processes
     assert res.returncode == 0, res.stdout + res.stderr
     ranks = [[l for l in open(d / ("rank%d.txt" % r)).read().splitlines() if l.startswith("rank %d " % r)]
              for r in range(world)]

@@ -4,24 +4,17 @@ bpf_shard_update_resample -- no Python, torch.distributed or launcher anywhere i
 one GPU of the box; a third process runs the same filter unsharded."""
 import os
 import re
-import socket
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_driver
 from scenario import Scenario
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _compile(tmp_path):
-    exe = tmp_path / "shard_two_procs"
-    libdir = os.path.join(ROOT, "badger_amcl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "shard_two_procs.cpp"), "-o", str(exe),
-                           "-L", libdir, "-lbadger_pf_hip", "-Wl,-rpath," + libdir])
-    return exe
+    return cpp_driver.compile_driver(tmp_path, "shard_two_procs")
 
 
 def test_shard_driver_compiles_and_the_rccl_object_links():
@@ -52,19 +45,11 @@ def test_cpp_ranks_bootstrap_over_tcp_and_agree(tmp_path, orc, world, flags):
     path a node takes when its ranks cannot map each other's memory, as far as one GPU can exercise it."""
     exe = _compile(tmp_path)
     sc = Scenario(orc, size=400, n=6000, beams=91, cloud="converged")
-    paths = {}
-    for name, arr in (("cells", sc.cells.astype(np.int32)), ("lut", sc.lut.astype(np.float32)),
-                      ("samples", sc.samples), ("ranges", sc.ranges), ("angles", sc.angles)):
-        paths[name] = str(tmp_path / (name + ".bin"))
-        np.ascontiguousarray(arr).tofile(paths[name])
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
+    paths = cpp_driver.write_case(tmp_path, None, dict(cells=sc.cells.astype(np.int32), lut=sc.lut.astype(np.float32),
+                                                       samples=sc.samples, ranges=sc.ranges, angles=sc.angles))
     prefix = str(tmp_path / "out")
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    res = subprocess.run([str(exe), paths["cells"], paths["lut"], paths["samples"], paths["ranges"], paths["angles"],
-                          "400", str(world), str(port), str(flags), prefix],
-                         capture_output=True, text=True, env=env, timeout=240)
+    res = cpp_driver.run_driver(exe, [paths["cells"], paths["lut"], paths["samples"], paths["ranges"], paths["angles"],
+                                      "400", world, cpp_driver.free_port(), flags, prefix], timeout=240)
     assert res.returncode == 0, res.stdout + res.stderr
     rows = {}
     single = {}

@@ -6,17 +6,14 @@ import pathlib
 import subprocess
 import tempfile
 
+import cpp_driver
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LOCAL_ABI = ("bpf_shard_connect_local", "bpf_shard_exchange_mode", "bpf_shard_local_selftest")
 
 
 def compile_local_world(tmp_path):
-    exe = pathlib.Path(tmp_path) / "local_world"
-    libdir = os.path.join(ROOT, "badger_amcl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "local_world.cpp"), "-o", str(exe),
-                           "-L", libdir, "-lbadger_pf_hip", "-Wl,-rpath," + libdir])
-    return exe
+    return cpp_driver.compile_driver(tmp_path, "local_world")
 
 
 def test_the_three_entry_points_are_exported_and_bound():
