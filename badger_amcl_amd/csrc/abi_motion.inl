@@ -184,15 +184,11 @@ int build_set_tree(bpf_engine* e, int n)
   HIPCHK(e, e->d_keys.reserve((size_t)n * 3));
   hipLaunchKernelGGL(k_set_keys, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, s.dev(), n, e->d_keys.p);
   HIPCHK(e, hipGetLastError());
-  bool handled = false;
-  int stop = -1, leaf = 0, bins = 0;
+  KldOutcome dev;
   if (n >= 8192)
-  {
-    int rc = kld_tree_on_device(e, n, &handled, &stop, &leaf, &bins, true);
-    if (rc != BPF_OK)
-      return rc;
-  }
-  if (!handled)
+    H2D_OR_RETURN(kld_tree_on_device(e, n, &dev, true));
+  int leaf = dev.leaf, bins = dev.bins;
+  if (!dev.handled)
   {
     std::vector<int> keys((size_t)n * 3);
     H2D_OR_RETURN(d2h_to_host(e, keys.data(), e->d_keys.p, keys.size() * sizeof(int), e->stream));

@@ -116,15 +116,7 @@ namespace
 // caller can fall back to a stream synchronisation
 bool seam_wait_word(const unsigned long long* word, unsigned long long value)
 {
-  const auto t0 = std::chrono::steady_clock::now();
-  for (unsigned spins = 0;; ++spins)
-  {
-    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == value)
-      return true;
-    if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50))
-      return false;
-    __builtin_ia32_pause();
-  }
+  return spin_until([&] { return __atomic_load_n(word, __ATOMIC_ACQUIRE) == value; }, 50);
 }
 
 // Seam A on a REGISTERED host buffer, one scoring launch and no copy in either direction (HOST_MODE 2 of

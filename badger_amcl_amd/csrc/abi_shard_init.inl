@@ -211,18 +211,16 @@ int tree_merge(bpf_engine* e, const long long* all, const int* counts, int world
   int leaf = n_distinct, route = BPF_SHARD_TREE_ROUTE_BIN_COUNT;
   if (!kld_bins(e))
   {
-    bool handled = false;
-    int stop = -1, bins = 0;
+    KldOutcome dev;
     if (n_distinct >= 8192)
     {
-      rc = kld_tree_on_device(e, n_distinct, &handled, &stop, &leaf, &bins, true);
-      if (rc != BPF_OK)
-        return rc;
-      if (handled && bins != n_distinct)
+      H2D_OR_RETURN(kld_tree_on_device(e, n_distinct, &dev, true));
+      if (dev.handled && dev.bins != n_distinct)
         return e->fail(BPF_ERR_HIP, "global tree: the device tree saw repeated keys (internal error)");
+      leaf = dev.leaf;
       route = BPF_SHARD_TREE_ROUTE_DEVICE;
     }
-    if (!handled)
+    if (!dev.handled)
     {
       std::vector<int> keys((size_t)n_distinct * 3);
       H2D_OR_RETURN(d2h_to_host(e, keys.data(), e->d_keys.p, keys.size() * sizeof(int), e->stream));

@@ -187,11 +187,10 @@ int mn_merge_stop(bpf_engine* e, const long long* all, const int* counts, int wo
     bool handled = bins_mode;
     if (!bins_mode)
     {
-      int stop = -1, leaf = 0, bins = 0;
-      rc = kld_tree_on_device(e, B, &handled, &stop, &leaf, &bins, true);
-      if (rc != BPF_OK)
-        return rc;
-      if (handled && bins != B)
+      KldOutcome dev;
+      H2D_OR_RETURN(kld_tree_on_device(e, B, &dev, true));
+      handled = dev.handled;
+      if (handled && dev.bins != B)
         return e->fail(BPF_ERR_HIP, "in-place resample: the device tree saw repeated keys (internal error)");
     }
     else

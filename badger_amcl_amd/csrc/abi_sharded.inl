@@ -425,29 +425,15 @@ int shard_stop_block(bpf_engine* e, const long long* window, int stride, int cou
   *status = BPF_FUSED_TOO_MANY_BINS;
   if (count <= 0 || count > kFusedWindow || stride < count)
     return BPF_OK;
-  if (!systematic)
-  {
-    int rc = ensure_limit_table(e, count);
-    if (rc != BPF_OK)
-      return rc;
-  }
-  HIPCHK(e, e->h_fused.reserve(32));
   const bool bins = kld_bins(e);  // BPF_KLD_COUNT_BINS: the stop rule on the distinct-key count
-  bool& stop_attr_set = bins ? e->shard_stop_bins_attr_set : e->shard_stop_attr_set;
-  if (!stop_attr_set)
-  {
-    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(bins ? k_shard_stop_block_bins : k_shard_stop_block),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds));
-    stop_attr_set = true;
-  }
   SampleSet& b = e->sets[e->cur ^ 1];
   ShardStopArgs A{};
+  H2D_OR_RETURN(fused_block_arm(e, bins ? k_shard_stop_block_bins : k_shard_stop_block, count, systematic, &A));
   A.window = window;
   A.stride = stride;
   A.count = count;
   A.systematic = systematic ? 1 : 0;
   A.max_samples = e->max_samples;
-  A.limit = e->d_kld_limit.p;
   A.rank = e->shard_rank;
   A.world = std::max(1, e->shard_world);
   A.dst = b.dev();
@@ -457,28 +443,16 @@ int shard_stop_block(bpf_engine* e, const long long* window, int stride, int cou
   A.mb = shard_window_wait(e, window, 1);
   A.wait_parity = (int)(e->mb.win_gen & 1);
   A.wait_gen = e->mb.win_gen;
-  A.result_host = e->h_fused.p;
-  e->fused_generation = (e->fused_generation % 0x3fffffff) + 1;
-  A.generation = e->fused_generation;
-  A.debug = getenv("BPF_DEBUG") != nullptr;
-  A.lds_tree = e->fused_lds_tree ? 1 : 0;
   if (draw != nullptr)
   {
     // mailbox mode: the draws of the window and their consumer in one launch (k_shard_resample_block)
-    bool& resample_attr_set = bins ? e->shard_resample_bins_attr_set : e->shard_resample_attr_set;
-    if (!resample_attr_set)
-    {
-      HIPCHK(e, hipFuncSetAttribute(
-                    reinterpret_cast<const void*>(bins ? k_shard_resample_block_bins : k_shard_resample_block),
-                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds));
-      resample_attr_set = true;
-    }
+    const auto kernel = bins ? k_shard_resample_block_bins : k_shard_resample_block;
+    H2D_OR_RETURN(ensure_dynamic_lds(e, kernel, kFusedLds));
     ShardResampleArgs R{};
     R.W = *draw;
     R.S = A;
     ProfScope ps(e, BPF_K_DRAW);
-    hipLaunchKernelGGL(bins ? k_shard_resample_block_bins : k_shard_resample_block,
-                       dim3(blocks_for(count, kFusedDrawsPerBlock)), dim3(1024), kFusedLds, e->stream, R);
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(count, kFusedDrawsPerBlock)), dim3(1024), kFusedLds, e->stream, R);
   }
   else
   {
@@ -488,12 +462,7 @@ int shard_stop_block(bpf_engine* e, const long long* window, int stride, int cou
   }
   HIPCHK(e, hipGetLastError());
   int r5[5] = { 0, 0, 0, 0, 0 };
-  bool seen = false;
-  int rcw = fused_result_wait(e, A.generation, 50, r5, &seen);
-  if (rcw != BPF_OK)
-    return rcw;
-  if (!seen)
-    return e->fail(BPF_ERR_HIP, "k_shard_stop_block did not publish its result");
+  H2D_OR_RETURN(fused_result_wait(e, A.generation, "k_shard_stop_block", r5));
   if (int rcx = mailbox_check(e))
     return rcx;
   const int* res = e->h_fused.p;  // (the debug stamps, [8 ..])
@@ -566,28 +535,37 @@ int bpf_kld_feed(bpf_engine* e, const void* keys, int keys_are_int64, int stride
   *stop_count_out = -1;
   const long long* k64 = static_cast<const long long*>(keys);
   const int* k32 = static_cast<const int*>(keys);
-  int cached_leaf = -1, cached_limit = 0;
-  for (int q = 0; q < n_keys; ++q)
+  KldReplay replay;
+  for (int q = 0; q < n_keys && *stop_count_out < 0; ++q)
   {
     int k[3];
     for (int d = 0; d < 3; ++d)
       k[d] = keys_are_int64 ? (int)k64[(size_t)d * stride + q] : k32[(size_t)d * stride + q];
-    kld_host_insert(e, k[0], k[1], k[2]);
-    const int lc = kld_host_k(e);
-    if (lc != cached_leaf)
-    {
-      cached_leaf = lc;
-      cached_limit = resample_limit(lc, e->min_samples, e->max_samples, e->pop_err, e->pop_z);
-    }
-    const int count = first_draw_index + q + 1;
-    if (count > cached_limit)
-    {
-      *stop_count_out = count;
-      break;
-    }
+    if (replay.feed(e, k[0], k[1], k[2], first_draw_index + q + 1))
+      *stop_count_out = first_draw_index + q + 1;
   }
   return BPF_OK;
 }
+
+namespace
+{
+// the keys of an exchanged window's n columns in e->h_keys as three rows of n (k_publish_window_keys, which also
+// waits for the window's mailbox words), polled for like a resampler's zero-copy keys
+int publish_window_keys(bpf_engine* e, const void* window, int stride, int n)
+{
+  HIPCHK(e, e->h_keys.reserve((size_t)n * 3));
+  const unsigned generation = ++e->done_generation;
+  const MailboxDev wait = shard_window_wait(e, window, blocks_for(n, 256));
+  hipLaunchKernelGGL(k_publish_window_keys, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream,
+                     static_cast<const long long*>(window), stride, n, e->h_keys.p,
+                     reinterpret_cast<unsigned*>(e->d_flags.p + 4), reinterpret_cast<volatile unsigned*>(e->h_done.p),
+                     generation, wait, (int)(e->mb.win_gen & 1), e->mb.win_gen);
+  HIPCHK(e, hipGetLastError());
+  if (!wait_generation(e, generation))
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+  return mailbox_check(e);
+}
+}  // namespace
 
 int bpf_kld_feed_dev(bpf_engine* e, const void* window_dev, int stride, int n_keys, int first_draw_index,
                      int* stop_count_out)
@@ -597,18 +575,7 @@ int bpf_kld_feed_dev(bpf_engine* e, const void* window_dev, int stride, int n_ke
   if (!e->have_pf)
     return e->fail(BPF_ERR_NOT_CONFIGURED, "bpf_pf_create first");
   HIPCHK(e, hipSetDevice(e->device));
-  HIPCHK(e, e->h_keys.reserve((size_t)n_keys * 3));
-  const unsigned generation = ++e->done_generation;
-  const MailboxDev wait = shard_window_wait(e, window_dev, blocks_for(n_keys, 256));
-  hipLaunchKernelGGL(k_publish_window_keys, dim3(blocks_for(n_keys, 256)), dim3(256), 0, e->stream,
-                     static_cast<const long long*>(window_dev), stride, n_keys, e->h_keys.p,
-                     reinterpret_cast<unsigned*>(e->d_flags.p + 4), reinterpret_cast<volatile unsigned*>(e->h_done.p),
-                     generation, wait, (int)(e->mb.win_gen & 1), e->mb.win_gen);
-  HIPCHK(e, hipGetLastError());
-  if (!wait_generation(e, generation))
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-  if (int rcx = mailbox_check(e))
-    return rcx;
+  H2D_OR_RETURN(publish_window_keys(e, window_dev, stride, n_keys));
   return bpf_kld_feed(e, e->h_keys.p, 0, n_keys, n_keys, first_draw_index, stop_count_out);
 }
 
@@ -842,18 +809,7 @@ int bpf_kld_insert_dev(bpf_engine* e, const void* window_dev, int stride, int n_
   if (!e->have_pf)
     return e->fail(BPF_ERR_NOT_CONFIGURED, "bpf_pf_create first");
   HIPCHK(e, hipSetDevice(e->device));
-  HIPCHK(e, e->h_keys.reserve((size_t)n_keys * 3));
-  const unsigned generation = ++e->done_generation;
-  const MailboxDev wait = shard_window_wait(e, window_dev, blocks_for(n_keys, 256));
-  hipLaunchKernelGGL(k_publish_window_keys, dim3(blocks_for(n_keys, 256)), dim3(256), 0, e->stream,
-                     static_cast<const long long*>(window_dev), stride, n_keys, e->h_keys.p,
-                     reinterpret_cast<unsigned*>(e->d_flags.p + 4), reinterpret_cast<volatile unsigned*>(e->h_done.p),
-                     generation, wait, (int)(e->mb.win_gen & 1), e->mb.win_gen);
-  HIPCHK(e, hipGetLastError());
-  if (!wait_generation(e, generation))
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-  if (int rcx = mailbox_check(e))
-    return rcx;
+  H2D_OR_RETURN(publish_window_keys(e, window_dev, stride, n_keys));
   return bpf_kld_insert(e, e->h_keys.p, 0, n_keys, n_keys);
 }
 
@@ -872,11 +828,12 @@ int bpf_kld_stop_dev(bpf_engine* e, const void* window_dev, int stride, int n_ke
                      static_cast<const long long*>(window_dev), stride, n_keys, e->d_keys.p, wait,
                      (int)(e->mb.win_gen & 1), e->mb.win_gen);
   HIPCHK(e, hipGetLastError());
-  bool handled = false;
-  *stop_count_out = -1;
-  *leaf_count_out = *bin_count_out = 0;
-  int rc = kld_tree_on_device(e, n_keys, &handled, stop_count_out, leaf_count_out, bin_count_out);
-  *handled_out = handled ? 1 : 0;
+  KldOutcome dev;
+  int rc = kld_tree_on_device(e, n_keys, &dev);
+  *handled_out = dev.handled ? 1 : 0;
+  *stop_count_out = dev.stop;
+  *leaf_count_out = dev.leaf;
+  *bin_count_out = dev.bins;
   if (rc == BPF_OK)
     rc = mailbox_check(e);
   return rc;

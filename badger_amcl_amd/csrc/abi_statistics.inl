@@ -9,37 +9,18 @@ int stats_block_evaluate(bpf_engine* e, ParticlesDev p, int n, int* status)
 {
   HIPCHK(e, e->d_stats_clusters.reserve((size_t)std::max(n, kStatBlockClusters)));
   HIPCHK(e, e->h_stats_block.reserve(64));
-  if (!e->stats_lds_attr_set)
-  {
-    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(k_stats_block),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStatBlockLds));
-    e->stats_lds_attr_set = true;
-  }
+  H2D_OR_RETURN(ensure_dynamic_lds(e, k_stats_block, kStatBlockLds));
   StatsBlockArgs B{};
   B.p = p;
   B.n = n;
   B.clusters = reinterpret_cast<ClusterDev*>(e->d_stats_clusters.p);
   B.result_host = e->h_stats_block.p;
-  e->stats_generation = (e->stats_generation % 0x3fffffff) + 1;
+  e->stats_generation = next_generation(e->stats_generation);
   B.generation = e->stats_generation;
   hipLaunchKernelGGL(k_stats_block, dim3(1), dim3(1024), kStatBlockLds, e->stream, B);
   HIPCHK(e, hipGetLastError());
-  const auto t0 = std::chrono::steady_clock::now();
-  bool seen = false;
-  for (unsigned spins = 0; !seen; ++spins)
-  {
-    seen = __atomic_load_n(e->h_stats_block.p, __ATOMIC_ACQUIRE) == B.generation;
-    if (!seen && (spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50))
-      break;
-    if (!seen)
-      __builtin_ia32_pause();
-  }
-  if (!seen)
-  {
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (__atomic_load_n(e->h_stats_block.p, __ATOMIC_ACQUIRE) != B.generation)
-      return e->fail(BPF_ERR_HIP, "k_stats_block did not publish its result");
-  }
+  H2D_OR_RETURN(await_published(
+      e, [&] { return __atomic_load_n(e->h_stats_block.p, __ATOMIC_ACQUIRE) == B.generation; }, 50, "k_stats_block"));
   if (e->h_stats_block.p[1] == 0)
   {
     StatsResult r;

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <condition_variable>
 #include <mutex>
+#include <optional>
 #include <functional>
 #include <queue>
 #include <cmath>
@@ -20,6 +21,7 @@
 #include "../../include/badger_pf.h"
 #include "device_types.hpp"
 #include "kdhist.hpp"
+#include "host_poll.hpp"
 #include "kernels_cloud.hpp"
 #include "kernels_lut3d.hpp"
 #include "kernels_motion.hpp"

@@ -249,8 +249,7 @@ struct bpf_engine
   DevBuf<double4> d_prep;
   DevBuf<double> d_prep_stats, d_chunk_partials;
   DevBuf<WindowPlan> d_plan;
-  bool window_lds_attr_set = false;
-  bool beam_lds_attr_set = false;
+  std::vector<const void*> dynamic_lds_set;  // kernels whose dynamic LDS limit has been raised (ensure_dynamic_lds)
   bool graded_shares = true;    // BPF_OPT_GRADED_SHARES
   DevBuf<int> d_beam_counter;   // work counter of k_score_beam
   bool window_enabled = false;  // measured: no gain on wide clouds; opt-in via BPF_OPT_WINDOW_PATH
@@ -309,9 +308,6 @@ struct bpf_engine
   bool fused_resample = true; // BPF_OPT_FUSED_RESAMPLE
   bool fused_lds_tree = false; // BPF_OPT_FUSED_LDS_TREE: the LDS form of the <= 64-key tree (tests)
   bool lut_exact_edt = false; // BPF_OPT_LUT_EXACT_EDT: implicit LUT builds take the device EDT instead of the reference's brushfire
-  bool fused_lds_attr_set = false;
-  bool shard_stop_attr_set = false;
-  bool shard_resample_attr_set = false;
   bool kld_persistent = false;         // BPF_OPT_KLD_PERSISTENT: the device tree in one launch when its grid is resident
   int kld_generation = 0;
   int kld_persist_blocks_per_cu = -1;  // occupancy of k_kld_tree_persistent (-1: not asked yet)
@@ -443,7 +439,6 @@ struct bpf_engine
   int kld_leaf = 0, kld_bins = 0;
   int kld_count_mode = BPF_KLD_COUNT_LEAVES;  // bpf_pf_set_kld_count: what the stop rule's k counts
   int kld_host_bins = 0;  // BINS mode: distinct keys the host replay has seen (e->seen first occurrences)
-  bool resample_bins_attr_set = false, shard_stop_bins_attr_set = false, shard_resample_bins_attr_set = false;
   DevBuf<unsigned long long> d_kld_hkey;
   DevBuf<int> d_kld_htmin, d_kld_slot, d_kld_cur, d_kld_first, d_kld_child, d_kld_flags, d_kld_limit;
   DevBuf<int2> d_kld_delta, d_kld_tiles, d_kld_counts;
@@ -452,7 +447,6 @@ struct bpf_engine
   DevBuf<Kld2Top> d_kld2_top;
   DevBuf<unsigned long long> d_kld2_slots;  // look-back slots of k_kld2_scan
   bool kld_local = true;        // BPF_OPT_KLD_LOCAL
-  bool kld2_attr_set = false;
   // the histogram tree's hash tables were left in their start state behind the last build (pieces form): table size,
   // buffers and capacities they were cleared at (0: not clean)
   unsigned kld_clean_table = 0;
@@ -489,7 +483,6 @@ struct bpf_engine
   PinnedBuf<int> h_stats_flags;
   PinnedBuf<int> h_stats_block;     // k_stats_block: [0] generation, [1] status, [4 ..] StatsResult
   int stats_generation = 0;
-  bool stats_lds_attr_set = false;
 
   // ---- cluster statistics of a sharded set (kernels_shard_stats.hpp, abi_shard_stats.inl)
   int ss_stage = 0;                 // 0 none, 1 local bins listed, 2 bins merged and labelled, 3 local sums exported

@@ -180,6 +180,39 @@ constexpr unsigned kTimedLaunchStride = 8;
       hipLaunchKernelGGL(kernel, grid, block, lds, _e->stream, __VA_ARGS__);                                          \
   } while (0)
 
+// ------------------------------------------------------------------ results published in pinned memory
+// Waits for what `kernel_name` publishes in pinned host memory (host_poll.hpp): spins up to `ms`, then lets the stream
+// drain (a mailbox wait may be running up to its bound) and looks once more.
+template <class Ready>
+int await_published(bpf_engine* e, Ready&& ready, int ms, const char* kernel_name)
+{
+  if (spin_until(ready, ms))
+    return BPF_OK;
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (ready())
+    return BPF_OK;
+  return e->fail(BPF_ERR_HIP, std::string(kernel_name) + " did not publish its result");
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize for a kernel that asks for more than the default 64 KB, once per engine
+template <class Kernel>
+int ensure_dynamic_lds(bpf_engine* e, Kernel* kernel, size_t bytes)
+{
+  const void* f = reinterpret_cast<const void*>(kernel);
+  if (std::find(e->dynamic_lds_set.begin(), e->dynamic_lds_set.end(), f) != e->dynamic_lds_set.end())
+    return BPF_OK;
+  HIPCHK(e, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  e->dynamic_lds_set.push_back(f);
+  return BPF_OK;
+}
+
+// BPF_DEBUG: the drivers' debug lines on stderr and the one-block kernels' phase clocks
+bool debug_on()
+{
+  static const bool on = getenv("BPF_DEBUG") != nullptr;
+  return on;
+}
+
 void lcg_tables(LcgJump& J)
 {
   const uint64_t mask = (1ull << 48) - 1;

@@ -53,8 +53,6 @@ int fetch_scalars(bpf_engine* e)
   return BPF_OK;
 }
 
-// zero_word2 / sum_out (optional): a second miss flag to clear and where to leave c[n], both written by the scan
-// itself instead of by a memset and a copy behind it
 // k_resample_block stages every (1 << shift)-th CDF value in LDS: the smallest shift that fits kFusedCoarse brackets
 int fused_coarse_shift(int n)
 {
@@ -106,7 +104,7 @@ int launch_normalize_cdf(bpf_engine* e, double* w, int n)
   // k_resample_block searches through the subsample; the guide table is for the general path's draw kernel, worth its
   // writes only when a long draw stream is expected (the previous resample ran to the end: a spread cloud)
   const bool want_guide = e->window_hint >= e->max_samples;
-  if (getenv("BPF_DEBUG"))
+  if (debug_on())
     fprintf(stderr, "[normalize_cdf] n %d window_hint %d max %d guide %d\n", n, e->window_hint, e->max_samples, (int)want_guide);
   A.guide = want_guide ? e->d_cdf_guide.p : nullptr;
   A.zero_word = e->d_flags.p;
@@ -117,6 +115,8 @@ int launch_normalize_cdf(bpf_engine* e, double* w, int n)
   return BPF_OK;
 }
 
+// zero_word2 / sum_out (optional): a second miss flag to clear and where to leave c[n], both written by the scan
+// itself instead of by a memset and a copy behind it
 int build_cdf(bpf_engine* e, const double* w, int n, int* zero_word2 = nullptr, double* sum_out = nullptr)
 {
   if (e->wc.cdf_ready_n == n && w == e->sets[e->cur].w.p && !e->cdf_serial && zero_word2 == nullptr &&
@@ -475,9 +475,6 @@ int ensure_limit_table(bpf_engine* e, int upto)
   return BPF_OK;
 }
 
-// The whole resample for a candidate stream of at most kFusedWindow draws as one single-block launch
-// (k_resample_block): draws, histogram tree and KLD stop, weights 1/M, updateConverged.  *handled = false when the
-// stop lies beyond the window, a key does not fit the packing or the tree is too deep: the caller runs the general path.
 // draw m takes stream element 2 m + 2: the composed LCG step for that distance, per draw of a window kernel
 int ensure_fused_jump(bpf_engine* e)
 {
@@ -506,69 +503,52 @@ int ensure_fused_jump(bpf_engine* e)
   return BPF_OK;
 }
 
-// Waits for a window kernel's three result words (fused_publish in kernels_fused.hpp) of `generation` in e->h_fused;
-// res[0..4] = M, leaf count, bin count, status, levels.  BPF_OK with *seen = false when they do not show up.
-int fused_result_wait(bpf_engine* e, int generation, int spin_ms, int res[5], bool* seen)
+// What the window kernels (k_resample_block, k_shard_stop_block and their kin) need ahead of the launch, in `A`: the
+// limit table, the pinned result block, the kernel's LDS limit, a new generation and the debug flag
+template <class Args, class Kernel>
+int fused_block_arm(bpf_engine* e, Kernel* kernel, int window, bool systematic, Args* A)
 {
-  const unsigned long long* w = reinterpret_cast<const unsigned long long*>(e->h_fused.p);
-  const auto t0 = std::chrono::steady_clock::now();
-  auto there = [&]() {
-    for (int k = 0; k < 3; ++k)
-      if ((unsigned)(__atomic_load_n(&w[k], __ATOMIC_ACQUIRE) >> 32) != (unsigned)generation)
-        return false;
-    return true;
-  };
-  *seen = false;
-  for (unsigned spins = 0; !*seen; ++spins)
-  {
-    *seen = there();
-    if (!*seen && (spins & 1023) == 1023 &&
-        std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(spin_ms))
-      break;
-    if (!*seen)
-      __builtin_ia32_pause();
-  }
-  if (!*seen)
-  {
-    HIPCHK(e, hipStreamSynchronize(e->stream));  // (a mailbox wait may be running up to its bound)
-    *seen = there();
-  }
-  if (*seen)
-  {
-    const unsigned long long w0 = w[0], w1 = w[1], w2 = w[2];
-    res[0] = (int)(unsigned)w0;
-    res[1] = (int)((w1 >> 16) & 0xFFFF);
-    res[2] = (int)(w1 & 0xFFFF);
-    res[3] = (int)((w2 >> 8) & 0xFF);
-    res[4] = (int)(w2 & 0xFF);
-  }
+  if (!systematic)
+    H2D_OR_RETURN(ensure_limit_table(e, window));
+  HIPCHK(e, e->h_fused.reserve(32));
+  H2D_OR_RETURN(ensure_dynamic_lds(e, kernel, kFusedLds));
+  A->limit = e->d_kld_limit.p;
+  A->result_host = e->h_fused.p;
+  e->fused_generation = next_generation(e->fused_generation);
+  A->generation = e->fused_generation;
+  A->debug = debug_on();
+  A->lds_tree = e->fused_lds_tree ? 1 : 0;
   return BPF_OK;
 }
 
+// Waits for a window kernel's three result words (fused_publish in kernels_fused.hpp) of `generation` in e->h_fused
+// (a ~25 us kernel); res[0..4] = M, leaf count, bin count, status, levels
+int fused_result_wait(bpf_engine* e, int generation, const char* kernel_name, int res[5])
+{
+  const unsigned long long* w = reinterpret_cast<const unsigned long long*>(e->h_fused.p);
+  int low[3] = { 0, 0, 0 };
+  H2D_OR_RETURN(await_published(
+      e, [&] { return tagged_words(w, 0, 3, (unsigned)generation, low); }, 50, kernel_name));
+  res[0] = low[0];
+  res[1] = (low[1] >> 16) & 0xFFFF;
+  res[2] = low[1] & 0xFFFF;
+  res[3] = (low[2] >> 8) & 0xFF;
+  res[4] = low[2] & 0xFF;
+  return BPF_OK;
+}
+
+// The whole resample for a candidate stream of at most kFusedWindow draws as one single-block launch
+// (k_resample_block): draws, histogram tree and KLD stop, weights 1/M, updateConverged.  *handled = false when the
+// stop lies beyond the window, a key does not fit the packing or the tree is too deep: the caller runs the general path.
 int resample_block(bpf_engine* e, int window, bool systematic, const double* targets, bool* handled)
 {
   *handled = false;
   SampleSet& a = e->sets[e->cur];
   SampleSet& b = e->sets[e->cur ^ 1];
-  if (!systematic)
-  {
-    int rc = ensure_limit_table(e, window);
-    if (rc != BPF_OK)
-      return rc;
-  }
-  HIPCHK(e, e->h_fused.reserve(32));
-  const bool bins = kld_bins(e);
-  bool& attr_set = bins ? e->resample_bins_attr_set : e->fused_lds_attr_set;
-  if (!attr_set)
-  {
-    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(bins ? k_resample_block_bins : k_resample_block),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLds));
-    attr_set = true;
-  }
-  int rcj = ensure_fused_jump(e);
-  if (rcj != BPF_OK)
-    return rcj;
+  const auto kernel = kld_bins(e) ? k_resample_block_bins : k_resample_block;
   ResampleBlockArgs A{};
+  H2D_OR_RETURN(fused_block_arm(e, kernel, window, systematic, &A));
+  H2D_OR_RETURN(ensure_fused_jump(e));
   A.src = a.dev();
   A.n_src = e->sample_count;
   A.cdf = e->d_cdf.p;
@@ -583,32 +563,19 @@ int resample_block(bpf_engine* e, int window, bool systematic, const double* tar
   A.jump = e->d_fused_jump.p;
   A.keys = e->d_fused_keys.p;
   A.counter = e->d_fused_counter.p;
-  A.limit = e->d_kld_limit.p;
   A.miss_flag = e->d_flags.p;
   A.thr = e->dist_threshold;
   A.sc = e->d_scalars.p;
   A.conv_count = e->d_flags.p + 1;
-  A.result_host = e->h_fused.p;
-  e->fused_generation = (e->fused_generation % 0x3fffffff) + 1;
-  A.generation = e->fused_generation;
-  A.debug = getenv("BPF_DEBUG") != nullptr;
-  A.lds_tree = e->fused_lds_tree ? 1 : 0;
   {
     ProfScope ps(e, BPF_K_DRAW);
-    hipLaunchKernelGGL(bins ? k_resample_block_bins : k_resample_block, dim3(blocks_for(window, kFusedDrawsPerBlock)),
-                       dim3(1024), kFusedLds, e->stream, A);
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(window, kFusedDrawsPerBlock)), dim3(1024), kFusedLds, e->stream, A);
   }
   HIPCHK(e, hipGetLastError());
-  // the block publishes its result words in pinned memory (a ~25 us kernel)
   int r5[5] = { 0, 0, 0, 0, 0 };
-  bool seen = false;
-  int rcw = fused_result_wait(e, A.generation, 50, r5, &seen);
-  if (rcw != BPF_OK)
-    return rcw;
-  if (!seen)
-    return e->fail(BPF_ERR_HIP, "k_resample_block did not publish its result");
+  H2D_OR_RETURN(fused_result_wait(e, A.generation, "k_resample_block", r5));
   const int* res = e->h_fused.p;  // (the debug stamps, [6] and [8 ..])
-  if (getenv("BPF_DEBUG"))
+  if (debug_on())
   {
     fprintf(stderr, "[resample block] window %d M %d leaf %d bins %d status %d levels %d; last block (10 ns ticks): load %d "
             "dedup %d tree %d scan %d tail %d = %d shader clocks\n", window, r5[0], r5[1], r5[2], r5[3], r5[4],
@@ -628,39 +595,104 @@ int resample_block(bpf_engine* e, int window, bool systematic, const double* tar
   return BPF_OK;
 }
 
-// BINS mode: the stop rule over the whole stream [0, n) with k = distinct keys so far (kernels_kld_bins.hpp): the key
-// hash, then one look-back prefix count of the first occurrences with the stop test, and the result in pinned memory.
-// Same outputs as kld_tree_on_device below, with *leaf_out = *bins_out.
-int kld_bins_on_device(bpf_engine* e, int n, bool* handled, int* stop_out, int* leaf_out, int* bins_out,
-                       bool whole_stream)
+// ---- the KLD stop rule for a whole candidate stream [0, n) on the device, keys in e->d_keys (AoS).
+// stop = the stop count (-1: no stop), leaf / bins at the final count; handled = false when the device declined (a key
+// that does not fit the 64-bit packing, a tree deeper than the level budget): the caller replays on the host.
+struct KldOutcome
 {
-  const unsigned table = hash_table_size(n);
-  constexpr int kResultAt = 4 + 256;  // the pinned result words sit where the pieces form keeps its own
-  const int tiles = blocks_for(n, kKldTile);
+  bool handled = false;
+  int stop = -1, leaf = 0, bins = 0;
+
+  void set(int stop_, int leaf_, int bins_)
+  {
+    handled = true;
+    stop = stop_;
+    leaf = leaf_;
+    bins = bins_;
+  }
+};
+
+// what one form of the device tree made of the stream
+enum KldForm
+{
+  KLD_HANDLED,    // the outcome is filled in
+  KLD_DECLINED,   // to the host replay
+  KLD_NEXT_FORM,  // nothing decided: the driver goes on down its chain
+};
+
+constexpr int kKldMaxLevels = 256;  // the level budget; e->d_kld_flags and the pinned e->h_kld hold 4 + kKldMaxLevels flag words
+// behind them in e->h_kld: the eight 64-bit result words of the pieces form, or the bins form's (never both in a call)
+constexpr int kKldResultAt = 4 + kKldMaxLevels;
+static_assert(kKldResultAt % 2 == 0, "the result words are 8-byte aligned");
+
+// the buffers of a build over n keys and the arguments every kernel of it takes (`tree`: with the node arrays, which
+// the bins form does without)
+int kld_prepare(bpf_engine* e, int n, unsigned table, bool tree, KldArgs* K)
+{
   HIPCHK(e, e->d_kld_hkey.reserve(table));
   HIPCHK(e, e->d_kld_htmin.reserve(table));
   HIPCHK(e, e->d_kld_slot.reserve((size_t)n));
   HIPCHK(e, e->d_kld_counts.reserve((size_t)n));
-  HIPCHK(e, e->d_kld_flags.reserve(4));
-  HIPCHK(e, e->h_kld.reserve(kResultAt + 16));
+  HIPCHK(e, e->d_kld_flags.reserve(tree ? 4 + kKldMaxLevels : 4));
+  HIPCHK(e, e->h_kld.reserve(kKldResultAt + 16));
+  *K = KldArgs{};
+  if (tree)
+  {
+    HIPCHK(e, e->d_kld_cur.reserve((size_t)n));
+    HIPCHK(e, e->d_kld_first.reserve((size_t)n));
+    HIPCHK(e, e->d_kld_child.reserve((size_t)2 * n));
+    HIPCHK(e, e->d_kld_delta.reserve((size_t)n));
+    HIPCHK(e, e->d_kld_tiles.reserve((size_t)blocks_for(n, kKldTile)));
+    K->cur = e->d_kld_cur.p;
+    K->first = e->d_kld_first.p;
+    K->child = e->d_kld_child.p;
+    K->delta = e->d_kld_delta.p;
+  }
+  K->keys = e->d_keys.p;
+  K->n = n;
+  K->h_key = e->d_kld_hkey.p;
+  K->h_tmin = e->d_kld_htmin.p;
+  K->h_mask = table - 1;
+  K->slot = e->d_kld_slot.p;
+  K->flags = e->d_kld_flags.p;
+  K->limit = e->d_kld_limit.p;
+  return BPF_OK;
+}
+
+// the look-back slots of the one-launch prefix scans (k_kld2_scan, k_kld_bins_scan), tagged with the generation:
+// reserved and zeroed once
+int kld_scan_slots(bpf_engine* e, int tiles)
+{
   if (e->d_kld2_slots.cap < (size_t)tiles)
   {
     HIPCHK(e, e->d_kld2_slots.reserve((size_t)std::max(tiles, 1024)));
     HIPCHK(e, hipMemsetAsync(e->d_kld2_slots.p, 0, e->d_kld2_slots.cap * sizeof(unsigned long long), e->stream));
   }
+  return BPF_OK;
+}
+
+// the tagged result words at e->h_kld + kKldResultAt: res[k] = word k for k = 1 .. count
+int kld_result_wait(bpf_engine* e, int generation, int count, int* res, const char* kernel_name)
+{
+  const unsigned long long* words = reinterpret_cast<const unsigned long long*>(e->h_kld.p + kKldResultAt);
+  return await_published(
+      e, [&] { return tagged_words(words, 1, count, (unsigned)generation, res + 1); }, 100, kernel_name);
+}
+
+// BINS mode: the stop rule over the whole stream [0, n) with k = distinct keys so far (kernels_kld_bins.hpp): the key
+// hash, then one look-back prefix count of the first occurrences with the stop test, and the result in pinned memory.
+// leaf = bins in the outcome.
+int kld_bins_on_device(bpf_engine* e, int n, bool whole_stream, KldOutcome* out)
+{
+  const unsigned table = hash_table_size(n);
+  const int tiles = blocks_for(n, kKldTile);
   KldArgs K{};
-  K.keys = e->d_keys.p;
-  K.n = n;
-  K.h_key = e->d_kld_hkey.p;
-  K.h_tmin = e->d_kld_htmin.p;
-  K.h_mask = table - 1;
-  K.slot = e->d_kld_slot.p;
-  K.flags = e->d_kld_flags.p;
-  K.limit = e->d_kld_limit.p;
+  H2D_OR_RETURN(kld_prepare(e, n, table, false, &K));
+  H2D_OR_RETURN(kld_scan_slots(e, tiles));
   int* counts = reinterpret_cast<int*>(e->d_kld_counts.p);
   e->kld_clean_table = 0;  // (the pieces form's start state is gone)
   e->kld_last_form = 4;
-  e->kld_generation = (e->kld_generation % 0x3fffffff) + 1;
+  e->kld_generation = next_generation(e->kld_generation);
   const int generation = e->kld_generation;
   ProfScope ps(e, BPF_K_DRAW);
   hipLaunchKernelGGL(k_kld_clear, dim3(std::min(1024, blocks_for((int)table, 256))), dim3(256), 0, e->stream, K, table,
@@ -669,296 +701,187 @@ int kld_bins_on_device(bpf_engine* e, int n, bool* handled, int* stop_out, int* 
   hipLaunchKernelGGL(k_kld_bins_scan, dim3(tiles), dim3(256), 0, e->stream, K, e->d_kld2_slots.p, (unsigned)generation,
                      counts, K.flags + 3);
   hipLaunchKernelGGL(k_kld_bins_result, dim3(1), dim3(64), 0, e->stream, K, (const int*)counts,
-                     (const int*)(K.flags + 3), whole_stream ? 1 : 0, e->h_kld.p + kResultAt, generation);
+                     (const int*)(K.flags + 3), whole_stream ? 1 : 0, e->h_kld.p + kKldResultAt, generation);
   HIPCHK(e, hipGetLastError());
-  volatile unsigned long long* words = reinterpret_cast<volatile unsigned long long*>(e->h_kld.p + kResultAt);
   int res[5] = { 0, 0, 0, 0, 0 };
-  auto all_there = [&]() {
-    for (int k = 1; k < 5; ++k)
-    {
-      const unsigned long long w = __atomic_load_n(const_cast<unsigned long long*>(words + k), __ATOMIC_ACQUIRE);
-      if ((unsigned)(w >> 32) != (unsigned)generation)
-        return false;
-      res[k] = (int)(unsigned)w;
-    }
-    return true;
-  };
-  const auto t0 = std::chrono::steady_clock::now();
-  bool seen = false;
-  for (unsigned spins = 0; !seen; ++spins)
-  {
-    seen = all_there();
-    if (!seen && (spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100))
-      break;
-    if (!seen)
-      __builtin_ia32_pause();
-  }
-  if (!seen)
-  {
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (!all_there())
-      return e->fail(BPF_ERR_HIP, "k_kld_bins_result did not publish its result");
-  }
-  if (getenv("BPF_DEBUG"))
+  H2D_OR_RETURN(kld_result_wait(e, generation, 4, res, "k_kld_bins_result"));
+  if (debug_on())
     fprintf(stderr, "[kld bins] n %d key range %d stop %d bins %d status %d\n", n, res[1], res[2], res[3], res[4]);
   if (res[1] != 0 || res[4] != 0)
     return BPF_OK;  // a key outside the packing range, or a look-back that timed out: not handled (host replay)
-  *stop_out = res[2];
-  *leaf_out = *bins_out = res[3];
-  *handled = true;
+  out->set(res[2], res[3], res[3]);
   return BPF_OK;
 }
 
-// The KLD stop rule for the whole candidate stream [0, maxs) on the device (kernels_kld.hpp), keys in
-// e->d_keys (AoS): grows the histogram tree level by level and scans the leaf count.
-// Returns BPF_OK with *stop_out = stop count (or -1: no stop), *leaf_out / *bins_out at the final count;
-// *handled = false when a key does not fit the 64-bit packing or the tree is deeper than the level budget
-// (the caller then replays on the host as before).
-int kld_tree_on_device(bpf_engine* e, int maxs, bool* handled, int* stop_out, int* leaf_out, int* bins_out,
-                       bool whole_stream = false, bool allow_local = true)
+// One start of the tree forms' chain: the hash tables in their start state (the pieces form clears them behind its
+// result while the host is turning around: `clean` then, and nothing to launch) and every key hashed
+int kld_tree_begin(bpf_engine* e, const KldArgs& K, unsigned table, bool local)
 {
-  *handled = false;
-  const int n = maxs;
-  if (n >= (1 << 30))
-    return BPF_OK;  // element indices 2v + side are folded as 32-bit tags
-  int rcl = ensure_limit_table(e, n);
-  if (rcl != BPF_OK)
-    return rcl;
-  if (kld_bins(e))
-    return kld_bins_on_device(e, n, handled, stop_out, leaf_out, bins_out, whole_stream);
-  const unsigned table = hash_table_size(n);
-  constexpr int kMaxLevels = 256;
-  const int tiles = blocks_for(n, kKldTile);
-  HIPCHK(e, e->d_kld_hkey.reserve(table));
-  HIPCHK(e, e->d_kld_htmin.reserve(table));
-  HIPCHK(e, e->d_kld_slot.reserve((size_t)n));
-  HIPCHK(e, e->d_kld_cur.reserve((size_t)n));
-  HIPCHK(e, e->d_kld_first.reserve((size_t)n));
-  HIPCHK(e, e->d_kld_child.reserve((size_t)2 * n));
-  HIPCHK(e, e->d_kld_delta.reserve((size_t)n));
-  HIPCHK(e, e->d_kld_counts.reserve((size_t)n));
-  HIPCHK(e, e->d_kld_tiles.reserve((size_t)tiles));
-  HIPCHK(e, e->d_kld_flags.reserve(4 + kMaxLevels));
-  HIPCHK(e, e->h_kld.reserve(4 + kMaxLevels + 16));  // (+ the pieces form's eight result words)
-  ProfScope ps(e, BPF_K_DRAW);
-  KldArgs K{};
-  K.keys = e->d_keys.p;
-  K.n = n;
-  K.h_key = e->d_kld_hkey.p;
-  K.h_tmin = e->d_kld_htmin.p;
-  K.h_mask = table - 1;
-  K.slot = e->d_kld_slot.p;
-  K.cur = e->d_kld_cur.p;
-  K.first = e->d_kld_first.p;
-  K.child = e->d_kld_child.p;
-  K.delta = e->d_kld_delta.p;
-  K.flags = e->d_kld_flags.p;
-  K.limit = e->d_kld_limit.p;
-  const dim3 grid(blocks_for(n, 256)), block(256);
-  const bool local = e->kld_local && allow_local && !e->kld_persistent;
-  // (pieces form: the previous build cleared the tables behind its result, while the host was turning around)
   const bool clean = local && e->kld_clean_table == table && e->kld_clean_key == e->d_kld_hkey.p &&
                      e->kld_clean_tmin == e->d_kld_htmin.p && e->kld_clean_cap == e->d_kld_hkey.cap;
   e->kld_clean_table = 0;
-  const dim3 clear_grid(std::min(1024, blocks_for((int)std::max<unsigned>(table, 2u * (unsigned)n), 256)));
+  const dim3 clear_grid(std::min(1024, blocks_for((int)std::max<unsigned>(table, 2u * (unsigned)K.n), 256)));
   if (!clean)
-    hipLaunchKernelGGL(k_kld_clear, clear_grid, block, 0, e->stream, K, table, 4 + kMaxLevels, local ? 0 : 1);
-  hipLaunchKernelGGL(k_kld_hash, grid, block, 0, e->stream, K);
-  if (e->kld_persistent)
+    hipLaunchKernelGGL(k_kld_clear, clear_grid, dim3(256), 0, e->stream, K, table, 4 + kKldMaxLevels, local ? 0 : 1);
+  hipLaunchKernelGGL(k_kld_hash, dim3(blocks_for(K.n, 256)), dim3(256), 0, e->stream, K);
+  return BPF_OK;
+}
+
+// The whole stream in one resident round of 1024-thread blocks: the level loop, the prefix sums and the stop test run
+// in ONE launch with grid barriers between the levels (k_kld_tree_persistent).  KLD_NEXT_FORM: the grid does not fit
+// the device, or (e->kld_persistent cleared for the rest of the engine's life, and the stream drained) it did not
+// become resident as a whole because the GPU is shared with another process.
+int kld_tree_persistent(bpf_engine* e, const KldArgs& K, bool whole_stream, KldOutcome* out, KldForm* form)
+{
+  *form = KLD_NEXT_FORM;
+  e->kld_last_form = 3;
+  const int n = K.n, pgrid = blocks_for(n, kKldBlock);
+  if (e->kld_persist_blocks_per_cu < 0)
   {
-    e->kld_last_form = 3;
-    // the whole stream in one resident round of 1024-thread blocks: the level loop, the prefix sums and the stop test
-    // run in ONE launch with grid barriers between the levels (k_kld_tree_persistent)
-    const int pgrid = blocks_for(n, kKldBlock);
-    if (e->kld_persist_blocks_per_cu < 0)
-    {
-      int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k_kld_tree_persistent),
-                                                       kKldBlock, 0) != hipSuccess)
-        nb = 0;
-      e->kld_persist_blocks_per_cu = nb;
-    }
-    if (pgrid <= e->kld_persist_blocks_per_cu * e->n_cu)
-    {
-      HIPCHK(e, e->d_kld_bar.reserve(4));
-      HIPCHK(e, e->d_kld_tiles.reserve((size_t)std::max(pgrid, tiles)));
-      HIPCHK(e, hipMemsetAsync(e->d_kld_bar.p, 0, 4 * sizeof(unsigned), e->stream));
-      KldPersistArgs P{};
-      P.K = K;
-      P.bar = e->d_kld_bar.p;
-      P.level_waiting = e->d_kld_flags.p + 4;
-      P.tile_sums = e->d_kld_tiles.p;
-      P.max_levels = kMaxLevels;
-      P.whole_stream = whole_stream ? 1 : 0;
-      P.timeout_ticks = 2000000ll;  // 20 ms per barrier: a resident grid passes one in microseconds
-      P.result_host = e->h_kld.p;
-      e->kld_generation = (e->kld_generation % 0x3fffffff) + 1;
-      P.generation = e->kld_generation;
-      e->h_kld.p[0] = 0;  // (the level-per-launch form copies its flag words here)
-      hipLaunchKernelGGL(k_kld_tree_persistent, dim3(pgrid), dim3(kKldBlock), 0, e->stream, P);
-      HIPCHK(e, hipGetLastError());
-      const auto t0 = std::chrono::steady_clock::now();
-      bool seen = false;
-      for (unsigned spins = 0; !seen; ++spins)
-      {
-        seen = __atomic_load_n(e->h_kld.p, __ATOMIC_ACQUIRE) == P.generation;
-        if (!seen && (spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200))
-          break;
-        if (!seen)
-          __builtin_ia32_pause();
-      }
-      if (!seen)
-      {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (__atomic_load_n(e->h_kld.p, __ATOMIC_ACQUIRE) != P.generation)
-          return e->fail(BPF_ERR_HIP, "k_kld_tree_persistent did not publish its result");
-      }
-      const int* res = e->h_kld.p;
-      if (getenv("BPF_DEBUG"))
-        fprintf(stderr, "[kld persistent] n %d blocks %d stop %d leaf %d bins %d status %d levels %d\n", n, pgrid, res[1],
-                res[2], res[3], res[4], res[5]);
-      if (res[4] == BPF_KLD_PERSIST_OK)
-      {
-        *stop_out = res[1];
-        *leaf_out = res[2];
-        *bins_out = res[3];
-        *handled = true;
-        return BPF_OK;
-      }
-      if (res[4] != BPF_KLD_PERSIST_TIMEOUT)
-        return BPF_OK;  // a key outside the packing, or deeper than the level budget: not handled (host replay)
-      // the grid was not resident as a whole (the GPU is shared with another process): let the launch drain, leave
-      // this form alone from now on and build the tree again with one launch pair per level
-      HIPCHK(e, hipStreamSynchronize(e->stream));
-      e->kld_persistent = false;
-      return kld_tree_on_device(e, maxs, handled, stop_out, leaf_out, bins_out, whole_stream);
-    }
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k_kld_tree_persistent),
+                                                     kKldBlock, 0) != hipSuccess)
+      nb = 0;
+    e->kld_persist_blocks_per_cu = nb;
   }
-  e->kld_last_form = local ? 2 : 1;
-  if (local)
+  if (pgrid > e->kld_persist_blocks_per_cu * e->n_cu)
+    return BPF_OK;
+  HIPCHK(e, e->d_kld_bar.reserve(4));
+  HIPCHK(e, e->d_kld_tiles.reserve((size_t)std::max(pgrid, blocks_for(n, kKldTile))));
+  HIPCHK(e, hipMemsetAsync(e->d_kld_bar.p, 0, 4 * sizeof(unsigned), e->stream));
+  KldPersistArgs P{};
+  P.K = K;
+  P.bar = e->d_kld_bar.p;
+  P.level_waiting = e->d_kld_flags.p + 4;
+  P.tile_sums = e->d_kld_tiles.p;
+  P.max_levels = kKldMaxLevels;
+  P.whole_stream = whole_stream ? 1 : 0;
+  P.timeout_ticks = 2000000ll;  // 20 ms per barrier: a resident grid passes one in microseconds
+  P.result_host = e->h_kld.p;
+  e->kld_generation = next_generation(e->kld_generation);
+  P.generation = e->kld_generation;
+  e->h_kld.p[0] = 0;  // (the level-per-launch form copies its flag words here)
+  hipLaunchKernelGGL(k_kld_tree_persistent, dim3(pgrid), dim3(kKldBlock), 0, e->stream, P);
+  HIPCHK(e, hipGetLastError());
+  H2D_OR_RETURN(await_published(
+      e, [&] { return __atomic_load_n(e->h_kld.p, __ATOMIC_ACQUIRE) == P.generation; }, 200, "k_kld_tree_persistent"));
+  const int* res = e->h_kld.p;
+  if (debug_on())
+    fprintf(stderr, "[kld persistent] n %d blocks %d stop %d leaf %d bins %d status %d levels %d\n", n, pgrid, res[1],
+            res[2], res[3], res[4], res[5]);
+  if (res[4] == BPF_KLD_PERSIST_OK)
   {
-    // the tree in LDS-sized pieces (kernels_kld2.hpp): no level loop, no host round trip until the result
-    const size_t nn = (size_t)n;
-    const int n_tiles = blocks_for(n, 256);
-    HIPCHK(e, e->d_kld2_int.reserve(5 * nn + 3 * (size_t)kKld2Nodes + 8 + (size_t)n_tiles));
-    HIPCHK(e, e->d_kld2_top.reserve((size_t)kKld2Nodes));
-    if (!e->kld2_attr_set)
-    {
-      HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kld2_top),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kKld2LdsBytes));
-      HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kld2_subtrees),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kKld2LdsBytes));
-      e->kld2_attr_set = true;
-    }
-    Kld2Args L{};
-    L.K = K;
-    L.pk = reinterpret_cast<unsigned long long*>(e->d_kld2_int.p);  // first: 8-byte aligned
-    int* base = e->d_kld2_int.p + 2 * nn;
-    L.tkeys = base;
-    L.bucket = base + nn;
-    L.bk = base + 2 * nn;
-    L.cnt = base + 3 * nn;
-    L.off = L.cnt + kKld2Nodes;
-    L.fill = L.off + kKld2Nodes + 1;
-    L.n_tkeys = L.fill + kKld2Nodes;
-    L.n_top = L.n_tkeys + 1;
-    L.status = L.n_top + 1;
-    int* tile_first = L.status + 4;
-    L.tile_first = tile_first;
-    L.n_tiles = n_tiles;
-    L.top = e->d_kld2_top.p;
-    L.counts = e->d_kld_counts.p;
-    L.whole_stream = whole_stream ? 1 : 0;
-    e->kld_generation = (e->kld_generation % 0x3fffffff) + 1;
-    L.generation = e->kld_generation;
-    // (eight 64-bit words behind the level loop's flag words in the pinned block)
-    static_assert((4 + kMaxLevels) % 2 == 0, "the result words are 8-byte aligned");
-    volatile unsigned long long* words = reinterpret_cast<volatile unsigned long long*>(e->h_kld.p + 4 + kMaxLevels);
-    L.result_host = e->h_kld.p + 4 + kMaxLevels;
-    int res[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    hipLaunchKernelGGL(k_kld2_init, dim3(n_tiles), dim3(256), 0, e->stream, K, tile_first);
-    hipLaunchKernelGGL(k_kld2_compact, dim3(n_tiles), dim3(256), 0, e->stream, L);
-    hipLaunchKernelGGL(k_kld2_top, dim3(1), dim3(kKld2Block), kKld2LdsBytes, e->stream, L);
-    hipLaunchKernelGGL(k_kld2_route, dim3(blocks_for(n, kKld2Block)), dim3(kKld2Block), 0, e->stream, L);
-    hipLaunchKernelGGL(k_kld2_offsets, dim3(1), dim3(1024), 0, e->stream, L);
-    hipLaunchKernelGGL(k_kld2_scatter, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, L);
-    hipLaunchKernelGGL(k_kld2_subtrees, dim3(blocks_for(n, kKld2Span) + 1), dim3(kKld2Block), kKld2LdsBytes, e->stream,
-                       L);
-    // prefix sums + stop test in one launch (look-back slots tagged with the generation: reserved and zeroed once)
-    if (e->d_kld2_slots.cap < (size_t)tiles)
-    {
-      HIPCHK(e, e->d_kld2_slots.reserve((size_t)std::max(tiles, 1024)));
-      HIPCHK(e, hipMemsetAsync(e->d_kld2_slots.p, 0, e->d_kld2_slots.cap * sizeof(unsigned long long), e->stream));
-    }
-    hipLaunchKernelGGL(k_kld2_scan, dim3(tiles), dim3(256), 0, e->stream, K, e->d_kld2_slots.p,
-                       (unsigned)L.generation, e->d_kld_counts.p, L.status);
-    hipLaunchKernelGGL(k_kld2_result, dim3(1), dim3(64), 0, e->stream, L);
-    // the next build's start state now, behind the result: the GPU does it while this thread turns around
-    hipLaunchKernelGGL(k_kld_clear, dim3(std::min(1024, blocks_for((int)table, 256))), block, 0, e->stream, K, table,
-                       4 + kMaxLevels, 0);
-    HIPCHK(e, hipGetLastError());
-    // the result block in pinned memory, every word tagged with the generation: one poll instead of three copies
-    // with a stream synchronisation each
-    {
-      auto all_there = [&]() {
-        for (int k = 1; k < 8; ++k)
-        {
-          const unsigned long long w = __atomic_load_n(const_cast<unsigned long long*>(words + k), __ATOMIC_ACQUIRE);
-          if ((unsigned)(w >> 32) != (unsigned)L.generation)
-            return false;
-          res[k] = (int)(unsigned)w;
-        }
-        return true;
-      };
-      const auto t0 = std::chrono::steady_clock::now();
-      bool seen = false;
-      for (unsigned spins = 0; !seen; ++spins)
-      {
-        seen = all_there();
-        if (!seen && (spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100))
-          break;
-        if (!seen)
-          __builtin_ia32_pause();
-      }
-      if (!seen)
-      {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (!all_there())
-          return e->fail(BPF_ERR_HIP, "k_kld2_result did not publish its result");
-      }
-    }
-    if (getenv("BPF_DEBUG"))
-      fprintf(stderr, "[kld pieces] n %d tree keys %d status %d largest bucket %d stop %d leaf %d bins %d\n", n, res[6],
-              res[5], res[7], res[2], res[3], res[4]);
-    e->kld_clean_table = table;
-    e->kld_clean_key = e->d_kld_hkey.p;
-    e->kld_clean_tmin = e->d_kld_htmin.p;
-    e->kld_clean_cap = e->d_kld_hkey.cap;
-    if (res[1] != 0)
-      return BPF_OK;  // a key outside the packing range: not handled
-    if (res[5] != BPF_KLD2_OK)  // a bucket that does not fit a block, or a piece deeper than its budget
-      return kld_tree_on_device(e, maxs, handled, stop_out, leaf_out, bins_out, whole_stream, false);
-    *stop_out = res[2];
-    *leaf_out = res[3];
-    *bins_out = res[4];
-    *handled = true;
+    out->set(res[1], res[2], res[3]);
+    *form = KLD_HANDLED;
+  }
+  else if (res[4] != BPF_KLD_PERSIST_TIMEOUT)
+    *form = KLD_DECLINED;  // a key outside the packing, or deeper than the level budget
+  else
+  {
+    // let the launch drain and leave this form alone from now on
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->kld_persistent = false;
+  }
+  return BPF_OK;
+}
+
+// The tree in LDS-sized pieces (kernels_kld2.hpp): no level loop, no host round trip until the result.
+// KLD_NEXT_FORM: a bucket that does not fit a block, or a piece deeper than its budget.
+int kld_tree_pieces(bpf_engine* e, const KldArgs& K, unsigned table, bool whole_stream, KldOutcome* out, KldForm* form)
+{
+  *form = KLD_DECLINED;
+  e->kld_last_form = 2;
+  const int n = K.n;
+  const size_t nn = (size_t)n;
+  const int n_tiles = blocks_for(n, 256), tiles = blocks_for(n, kKldTile);
+  HIPCHK(e, e->d_kld2_int.reserve(5 * nn + 3 * (size_t)kKld2Nodes + 8 + (size_t)n_tiles));
+  HIPCHK(e, e->d_kld2_top.reserve((size_t)kKld2Nodes));
+  H2D_OR_RETURN(ensure_dynamic_lds(e, &k_kld2_top, kKld2LdsBytes));
+  H2D_OR_RETURN(ensure_dynamic_lds(e, &k_kld2_subtrees, kKld2LdsBytes));
+  Kld2Args L{};
+  L.K = K;
+  L.pk = reinterpret_cast<unsigned long long*>(e->d_kld2_int.p);  // first: 8-byte aligned
+  int* base = e->d_kld2_int.p + 2 * nn;
+  L.tkeys = base;
+  L.bucket = base + nn;
+  L.bk = base + 2 * nn;
+  L.cnt = base + 3 * nn;
+  L.off = L.cnt + kKld2Nodes;
+  L.fill = L.off + kKld2Nodes + 1;
+  L.n_tkeys = L.fill + kKld2Nodes;
+  L.n_top = L.n_tkeys + 1;
+  L.status = L.n_top + 1;
+  int* tile_first = L.status + 4;
+  L.tile_first = tile_first;
+  L.n_tiles = n_tiles;
+  L.top = e->d_kld2_top.p;
+  L.counts = e->d_kld_counts.p;
+  L.whole_stream = whole_stream ? 1 : 0;
+  e->kld_generation = next_generation(e->kld_generation);
+  L.generation = e->kld_generation;
+  L.result_host = e->h_kld.p + kKldResultAt;
+  hipLaunchKernelGGL(k_kld2_init, dim3(n_tiles), dim3(256), 0, e->stream, K, tile_first);
+  hipLaunchKernelGGL(k_kld2_compact, dim3(n_tiles), dim3(256), 0, e->stream, L);
+  hipLaunchKernelGGL(k_kld2_top, dim3(1), dim3(kKld2Block), kKld2LdsBytes, e->stream, L);
+  hipLaunchKernelGGL(k_kld2_route, dim3(blocks_for(n, kKld2Block)), dim3(kKld2Block), 0, e->stream, L);
+  hipLaunchKernelGGL(k_kld2_offsets, dim3(1), dim3(1024), 0, e->stream, L);
+  hipLaunchKernelGGL(k_kld2_scatter, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, L);
+  hipLaunchKernelGGL(k_kld2_subtrees, dim3(blocks_for(n, kKld2Span) + 1), dim3(kKld2Block), kKld2LdsBytes, e->stream,
+                     L);
+  // prefix sums + stop test in one launch
+  H2D_OR_RETURN(kld_scan_slots(e, tiles));
+  hipLaunchKernelGGL(k_kld2_scan, dim3(tiles), dim3(256), 0, e->stream, K, e->d_kld2_slots.p,
+                     (unsigned)L.generation, e->d_kld_counts.p, L.status);
+  hipLaunchKernelGGL(k_kld2_result, dim3(1), dim3(64), 0, e->stream, L);
+  // the next build's start state now, behind the result: the GPU does it while this thread turns around
+  hipLaunchKernelGGL(k_kld_clear, dim3(std::min(1024, blocks_for((int)table, 256))), dim3(256), 0, e->stream, K, table,
+                     4 + kKldMaxLevels, 0);
+  HIPCHK(e, hipGetLastError());
+  // the result block in pinned memory, every word tagged with the generation: one poll instead of three copies
+  // with a stream synchronisation each
+  int res[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+  H2D_OR_RETURN(kld_result_wait(e, L.generation, 7, res, "k_kld2_result"));
+  if (debug_on())
+    fprintf(stderr, "[kld pieces] n %d tree keys %d status %d largest bucket %d stop %d leaf %d bins %d\n", n, res[6],
+            res[5], res[7], res[2], res[3], res[4]);
+  e->kld_clean_table = table;
+  e->kld_clean_key = e->d_kld_hkey.p;
+  e->kld_clean_tmin = e->d_kld_htmin.p;
+  e->kld_clean_cap = e->d_kld_hkey.cap;
+  if (res[1] != 0)
+    return BPF_OK;  // a key outside the packing range
+  if (res[5] != BPF_KLD2_OK)
+  {
+    *form = KLD_NEXT_FORM;
     return BPF_OK;
   }
-  hipLaunchKernelGGL(k_kld_init, grid, block, 0, e->stream, K);
+  out->set(res[2], res[3], res[4]);
+  *form = KLD_HANDLED;
+  return BPF_OK;
+}
+
+// The tree grown level by level, a launch pair per level and a look at the flag words per batch of levels, then the
+// scan of the leaf count.  The last form of the chain: the outcome stays unhandled when a key does not fit the packing
+// or the tree is deeper than the level budget.
+int kld_tree_levels(bpf_engine* e, const KldArgs& K, bool whole_stream, KldOutcome* out)
+{
+  e->kld_last_form = 1;
+  const int n = K.n, tiles = blocks_for(n, kKldTile);
+  hipLaunchKernelGGL(k_kld_init, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, K);
   hipLaunchKernelGGL(k_kld_root_first, dim3(1), dim3(1024), 0, e->stream, K);
   int level = 0;
   bool done = false;
   int batch = std::min(24, (int)std::ceil(1.3 * std::log2((double)n + 1.0)) + 1);  // (see below)
-  while (!done && level < kMaxLevels)
+  while (!done && level < kKldMaxLevels)
   {
-    for (int q = 0; q < batch && level < kMaxLevels; ++q, ++level)
+    for (int q = 0; q < batch && level < kKldMaxLevels; ++q, ++level)
     {
       hipLaunchKernelGGL(k_kld_children, dim3(blocks_for(n, kKldBlock)), dim3(kKldBlock), 0, e->stream, K);
       hipLaunchKernelGGL(k_kld_descend, dim3(blocks_for(n, kKldBlock)), dim3(kKldBlock), 0, e->stream, K,
                          e->d_kld_flags.p + 4 + level);
     }
     HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(e->h_kld.p, e->d_kld_flags.p, (4 + kMaxLevels) * sizeof(int), hipMemcpyDeviceToHost,
+    HIPCHK(e, hipMemcpyAsync(e->h_kld.p, e->d_kld_flags.p, (4 + kKldMaxLevels) * sizeof(int), hipMemcpyDeviceToHost,
                              e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (e->h_kld.p[0] != 0)
@@ -973,7 +896,7 @@ int kld_tree_on_device(bpf_engine* e, int maxs, bool* handled, int* stop_out, in
     // in one block against 14 us as a launch pair, and the switch costs what it saves.)
     batch = std::min(24, (int)std::ceil(1.3 * std::log2((double)waiting + 1.0)) + 1);
   }
-  if (getenv("BPF_DEBUG"))
+  if (debug_on())
   {
     fprintf(stderr, "[kld device] n %d levels %d done %d; keys waiting after each level:", n, level, (int)done);
     for (int l = 0; l < level; ++l)
@@ -995,15 +918,56 @@ int kld_tree_on_device(bpf_engine* e, int maxs, bool* handled, int* stop_out, in
   int2 c;
   HIPCHK(e, hipMemcpyAsync(&c, e->d_kld_counts.p + (M - 1), sizeof(int2), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
-  *stop_out = (stop >= 1 && stop <= n) ? stop : -1;
-  *leaf_out = c.x;
-  *bins_out = c.y;
-  *handled = true;
+  out->set((stop >= 1 && stop <= n) ? stop : -1, c.x, c.y);
   return BPF_OK;
 }
 
+// The driver.  BINS mode has one form.  Otherwise the chain is: the persistent form (BPF_OPT_KLD_PERSISTENT), the
+// pieces (BPF_OPT_KLD_LOCAL), the level loop; a form that hands on leaves the tables used, so the chain starts again
+// with them (kld_tree_begin), in a ProfScope of its own inside the one before it.
+int kld_tree_on_device(bpf_engine* e, int n, KldOutcome* out, bool whole_stream = false)
+{
+  *out = KldOutcome{};
+  if (n >= (1 << 30))
+    return BPF_OK;  // element indices 2v + side are folded as 32-bit tags
+  H2D_OR_RETURN(ensure_limit_table(e, n));
+  if (kld_bins(e))
+    return kld_bins_on_device(e, n, whole_stream, out);
+  const unsigned table = hash_table_size(n);
+  KldArgs K{};
+  H2D_OR_RETURN(kld_prepare(e, n, table, true, &K));
+  KldForm form = KLD_NEXT_FORM;
+  bool local = e->kld_local && !e->kld_persistent;
+  ProfScope ps(e, BPF_K_DRAW);
+  std::optional<ProfScope> ps_again, ps_levels;
+  H2D_OR_RETURN(kld_tree_begin(e, K, table, local));
+  if (e->kld_persistent)
+  {
+    H2D_OR_RETURN(kld_tree_persistent(e, K, whole_stream, out, &form));
+    if (form != KLD_NEXT_FORM)
+      return BPF_OK;
+    if (!e->kld_persistent)
+    {
+      // it timed out and is out of the way for good: from the top without it.  (A grid that merely does not fit goes
+      // on to the level loop: the option is still set, and it keeps the pieces out.)
+      local = e->kld_local;
+      ps_again.emplace(e, BPF_K_DRAW);
+      H2D_OR_RETURN(kld_tree_begin(e, K, table, local));
+    }
+  }
+  if (local)
+  {
+    H2D_OR_RETURN(kld_tree_pieces(e, K, table, whole_stream, out, &form));
+    if (form != KLD_NEXT_FORM)
+      return BPF_OK;
+    ps_levels.emplace(e, BPF_K_DRAW);
+    H2D_OR_RETURN(kld_tree_begin(e, K, table, false));
+  }
+  return kld_tree_levels(e, K, whole_stream, out);
+}
+
 // the whole candidate stream [0, maxs) again with the keys on the device only, then the tree
-int kld_on_device(bpf_engine* e, DrawArgs A, int maxs, bool* handled, int* stop_out, int* leaf_out, int* bins_out)
+int kld_on_device(bpf_engine* e, DrawArgs A, int maxs, KldOutcome* out)
 {
   A.m0 = 0;
   A.m1 = maxs;
@@ -1012,22 +976,90 @@ int kld_on_device(bpf_engine* e, DrawArgs A, int maxs, bool* handled, int* stop_
     ProfScope ps(e, BPF_K_DRAW);
     hipLaunchKernelGGL(k_draw_select, dim3(blocks_for(maxs, 256)), dim3(256), 0, e->stream, A);
   }
-  return kld_tree_on_device(e, maxs, handled, stop_out, leaf_out, bins_out);
+  return kld_tree_on_device(e, maxs, out);
 }
 
 // Spin on the generation word a kernel publishes in pinned host memory (kernels of ~10 us); false if it
-// takes implausibly long, and the caller falls back to a copy + stream synchronisation.
+// takes implausibly long, and the caller falls back to a copy or a stream synchronisation.
 bool wait_generation(bpf_engine* e, unsigned generation)
 {
-  const auto t0 = std::chrono::steady_clock::now();
-  for (unsigned spins = 0;; ++spins)
+  return spin_until([&] { return __atomic_load_n(e->h_done.p, __ATOMIC_ACQUIRE) == generation; }, 20);
+}
+
+// ---- the resamplers' keys on their way to the ordered host replay
+// Zero-copy hand-off (DrawArgs, SystematicArgs): the kernel writes the keys of its n draws straight into pinned host
+// memory as three rows and its last block publishes a generation number there (wait_generation), so that the host
+// polls a word instead of paying for a copy plus a stream synchronisation.
+template <class Args>
+void arm_key_handoff(bpf_engine* e, int n, Args* A)
+{
+  A->host_keys = e->h_keys.p;
+  A->host_stride = n;
+  A->done_counter = reinterpret_cast<unsigned*>(e->d_flags.p + 4);
+  A->host_done = reinterpret_cast<volatile unsigned*>(e->h_done.p);
+  A->generation = ++e->done_generation;
+}
+
+// the keys of n draws in e->h_keys: three rows of `stride` (the zero-copy hand-off), or AoS triples (stride 0)
+struct KeyView
+{
+  const int* keys;
+  int stride;
+
+  int key(int o, int d) const
   {
-    if (__atomic_load_n(e->h_done.p, __ATOMIC_ACQUIRE) == generation)
-      return true;
-    if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20))
-      return false;
-    __builtin_ia32_pause();
+    return stride ? keys[(size_t)d * stride + o] : keys[3 * (size_t)o + d];
   }
+};
+
+// the AoS triples the kernel left in e->d_keys, copied
+int copy_key_triples(bpf_engine* e, int n, KeyView* view)
+{
+  HIPCHK(e, hipMemcpyAsync(e->h_keys.p, e->d_keys.p, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  *view = KeyView{ e->h_keys.p, 0 };
+  return BPF_OK;
+}
+
+// The ordered replay's stop test (particle_filter.cpp:409-417): the bound follows the stop rule's k, recomputed when k
+// changes
+struct KldReplay
+{
+  int leaf = -1, limit = 0;
+
+  // the key of draw number `count` (1-based); true when the set is complete with it
+  bool feed(bpf_engine* e, int x, int y, int t, int count)
+  {
+    if (kld_host_insert(e, x, y, t) || leaf < 0)
+    {
+      const int lc = kld_host_k(e);
+      if (lc != leaf)
+      {
+        leaf = lc;
+        limit = resample_limit(lc, e->min_samples, e->max_samples, e->pop_err, e->pop_z);
+      }
+    }
+    return count > limit;  // particle_filter.cpp:416
+  }
+};
+
+// tracking regime: the previous cycle's stop (+ 25 %) fits one block's window and no recovery draws are due
+int resample_multinomial_block(bpf_engine* e, double w_diff, bool* handled)
+{
+  *handled = false;
+  const int maxs = e->max_samples;
+  const int w0 = std::min(std::max(1024, std::min(e->window_hint, maxs)), maxs);
+  const bool long_stream0 = e->window_hint >= maxs && maxs >= e->kld_device_min;
+  if (!e->fused_resample || w_diff != 0.0 || w0 > kFusedWindow || long_stream0)
+    return BPF_OK;
+  H2D_OR_RETURN(resample_block(e, w0, false, nullptr, handled));
+  if (*handled)
+  {
+    const int M = e->sample_count;
+    e->rng = lcg_skip_host(e->rng, 2ull * (uint64_t)M, e->jump);
+    e->window_hint = resample_window_for(M);
+  }
+  return BPF_OK;
 }
 
 int resample_multinomial(bpf_engine* e, double w_diff)
@@ -1052,25 +1084,10 @@ int resample_multinomial(bpf_engine* e, double w_diff)
     chain = e->d_chain.p;
   }
   e->fused_used = 0;
-  {
-    // tracking regime: the previous cycle's stop (+ 25 %) fits one block's window and no recovery draws are due
-    const int w0 = std::min(std::max(1024, std::min(e->window_hint, maxs)), maxs);
-    const bool long_stream0 = e->window_hint >= maxs && maxs >= e->kld_device_min;
-    if (e->fused_resample && w_diff == 0.0 && w0 <= kFusedWindow && !long_stream0)
-    {
-      bool handled = false;
-      int rcb = resample_block(e, w0, false, nullptr, &handled);
-      if (rcb != BPF_OK)
-        return rcb;
-      if (handled)
-      {
-        const int M = e->sample_count;
-        e->rng = lcg_skip_host(e->rng, 2ull * (uint64_t)M, e->jump);
-        e->window_hint = resample_window_for(M);
-        return BPF_OK;
-      }
-    }
-  }
+  bool tracked = false;
+  H2D_OR_RETURN(resample_multinomial_block(e, w_diff, &tracked));
+  if (tracked)
+    return BPF_OK;
   HIPCHK(e, e->d_keys.reserve((size_t)maxs * 3));
   HIPCHK(e, e->d_src_index.reserve((size_t)maxs));
   HIPCHK(e, e->h_keys.reserve((size_t)maxs * 3));
@@ -1078,7 +1095,7 @@ int resample_multinomial(bpf_engine* e, double w_diff)
   int m0 = 0, stop = -1;
   int window = std::max(1024, std::min(e->window_hint, maxs));
   e->resample_windows = 0;
-  int cached_leaf = -1, cached_limit = 0;
+  KldReplay replay;
   e->kld_device_used = false;
   bool device_declined = false;
   // keep the host's first window short when the device tree can take over after it
@@ -1105,79 +1122,46 @@ int resample_multinomial(bpf_engine* e, double w_diff)
     A.guide = e->wc.cdf_guide_valid ? e->d_cdf_guide.p : nullptr;
     // long stream ahead: the previous cycle ran to the end, or the windows so far found no stop and the bound for
     // the leaves seen so far (a lower estimate of where the stop will be) is still far away
-    const bool long_stream = (m0 > 0 ? cached_limit - m0 >= e->kld_device_min : e->window_hint >= maxs) &&
+    const bool long_stream = (m0 > 0 ? replay.limit - m0 >= e->kld_device_min : e->window_hint >= maxs) &&
                              maxs - m0 >= e->kld_device_min;
     if (long_stream && !device_declined)
     {
       // no stop inside the first window and a long stream ahead (a spread cloud): the ordered replay moves
       // to the device for the whole stream
-      bool handled = false;
-      int dstop = -1, dleaf = 0, dbins = 0;
-      int rc = kld_on_device(e, A, maxs, &handled, &dstop, &dleaf, &dbins);
+      KldOutcome dev;
+      int rc = kld_on_device(e, A, maxs, &dev);
       if (rc != BPF_OK)
         return rc;
-      if (handled)
+      if (dev.handled)
       {
         e->resample_windows++;
-        stop = dstop;
+        stop = dev.stop;
         e->kld_device_used = true;
-        e->kld_leaf = dleaf;
-        e->kld_bins = dbins;
+        e->kld_leaf = dev.leaf;
+        e->kld_bins = dev.bins;
         break;
       }
       device_declined = true;  // key range or depth outside what the device tree takes: host replay as before
     }
     const int wn = m1 - m0;
-    // Keys go straight into pinned host memory and the last block publishes a generation number
-    // there: the host polls that word instead of paying for a copy plus a stream synchronisation.
     const bool zero_copy = e->zero_copy_keys && wn <= (1 << 20);
     if (zero_copy)
-    {
-      A.host_keys = e->h_keys.p;
-      A.host_stride = wn;
-      A.done_counter = reinterpret_cast<unsigned*>(e->d_flags.p + 4);
-      A.host_done = reinterpret_cast<volatile unsigned*>(e->h_done.p);
-      A.generation = ++e->done_generation;
-    }
+      arm_key_handoff(e, wn, &A);
     {
       ProfScope ps(e, BPF_K_DRAW);
       hipLaunchKernelGGL(k_draw_select, dim3(blocks_for(wn, 256)), dim3(256), 0, e->stream, A);
     }
     HIPCHK(e, hipGetLastError());
-    const bool have_keys = zero_copy && wait_generation(e, A.generation);
-    int k_stride = wn;
-    if (!have_keys)
-    {
-      HIPCHK(e, hipMemcpyAsync(e->h_keys.p, e->d_keys.p, (size_t)wn * 3 * sizeof(int), hipMemcpyDeviceToHost,
-                               e->stream));
-      HIPCHK(e, hipStreamSynchronize(e->stream));
-      k_stride = 0;  // AoS triples from the device buffer
-    }
+    KeyView keys{ e->h_keys.p, wn };
+    if (!(zero_copy && wait_generation(e, A.generation)))
+      H2D_OR_RETURN(copy_key_triples(e, wn, &keys));  // (the kernel writes e->d_keys either way)
     e->resample_windows++;
-    const int* keys = e->h_keys.p;
-    for (int m = m0; m < m1; ++m)
-    {
-      const int o = m - m0;
-      const int k[3] = { k_stride ? keys[o] : keys[3 * o], k_stride ? keys[k_stride + o] : keys[3 * o + 1],
-                         k_stride ? keys[2 * k_stride + o] : keys[3 * o + 2] };
-      if (kld_host_insert(e, k[0], k[1], k[2]))
-      {
-        const int lc = kld_host_k(e);
-        if (lc != cached_leaf)
-        {
-          cached_leaf = lc;
-          cached_limit = resample_limit(lc, e->min_samples, e->max_samples, e->pop_err, e->pop_z);
-        }
-      }
-      if (m + 1 > cached_limit)  // particle_filter.cpp:416
-      {
+    for (int m = m0; m < m1 && stop < 0; ++m)
+      if (replay.feed(e, keys.key(m - m0, 0), keys.key(m - m0, 1), keys.key(m - m0, 2), m + 1))
         stop = m + 1;
-        break;
-      }
-    }
     m0 = m1;
     // next window: up to a quarter past the bound for the leaves seen so far
-    const int need = cached_limit - m0;
+    const int need = replay.limit - m0;
     window = resample_window_for(need);
   }
   const int M = (stop > 0) ? stop : maxs;
@@ -1193,6 +1177,25 @@ int resample_multinomial(bpf_engine* e, double w_diff)
     e->rng = lcg_skip_host(e->rng, 2ull * (uint64_t)M, e->jump);
   e->window_hint = resample_window_for(M);
   e->sample_count = M;
+  return BPF_OK;
+}
+
+// the systematic targets in e->h_targets: a serial floating-point chain (particle_filter.cpp:337-341), target +=
+// delta, and target -= 1 once it passes 1.  A CPU core runs that dependency chain several times faster than a GPU
+// lane, with the same IEEE arithmetic, so the host forms the targets and the kernel reads them from pinned memory.
+int systematic_targets(bpf_engine* e, double start, int num_systematic)
+{
+  HIPCHK(e, e->h_targets.reserve((size_t)e->max_samples));
+  const double delta = 1.0 / num_systematic;
+  double t = start;
+  double* out = e->h_targets.p;
+  for (int i = 0; i < num_systematic; ++i)
+  {
+    out[i] = t;
+    t += delta;
+    if (t > 1.0)
+      t -= 1.0;
+  }
   return BPF_OK;
 }
 
@@ -1236,8 +1239,6 @@ int resample_systematic(bpf_engine* e, double w_diff)
   const int num_systematic = count - num_random;
   const uint64_t rng_before = e->rng;
   e->rng = lcg_skip_host(e->rng, 1, e->jump);
-  const double start = std::ldexp((double)e->rng, -48);
-  const double delta = 1.0 / num_systematic;
   HIPCHK(e, e->d_keys.reserve((size_t)e->max_samples * 3));
   HIPCHK(e, e->d_src_index.reserve((size_t)e->max_samples));
   HIPCHK(e, e->h_keys.reserve((size_t)e->max_samples * 3));
@@ -1254,21 +1255,7 @@ int resample_systematic(bpf_engine* e, double w_diff)
   A.keys = e->d_keys.p;
   A.src_index = e->d_src_index.p;
   A.miss_flag = e->d_flags.p;
-  // The targets are a serial floating-point chain (particle_filter.cpp:337-341): target += delta, and
-  // target -= 1 once it passes 1.  A CPU core runs that dependency chain several times faster than a
-  // GPU lane, with the same IEEE arithmetic, so the host forms the targets and uploads them.
-  HIPCHK(e, e->h_targets.reserve((size_t)e->max_samples));
-  {
-    double t = start;
-    double* out = e->h_targets.p;
-    for (int i = 0; i < num_systematic; ++i)
-    {
-      out[i] = t;
-      t += delta;
-      if (t > 1.0)
-        t -= 1.0;
-    }
-  }
+  H2D_OR_RETURN(systematic_targets(e, std::ldexp((double)e->rng, -48), num_systematic));
   if (e->fused_resample && num_random == 0 && count <= kFusedWindow)
   {
     // the whole resample as one launch (k_resample_block): selection, the new set's histogram tree, weights,
@@ -1287,55 +1274,30 @@ int resample_systematic(bpf_engine* e, double w_diff)
   const bool device_count = kld_bins(e) && count >= 8192;
   const bool zero_copy = e->zero_copy_keys && count <= (1 << 20) && !device_count;
   if (zero_copy)
-  {
-    A.host_keys = e->h_keys.p;
-    A.host_stride = count;
-    A.done_counter = reinterpret_cast<unsigned*>(e->d_flags.p + 4);
-    A.host_done = reinterpret_cast<volatile unsigned*>(e->h_done.p);
-    A.generation = ++e->done_generation;
-  }
+    arm_key_handoff(e, count, &A);
   {
     ProfScope ps(e, BPF_K_DRAW);
     hipLaunchKernelGGL(k_systematic_select, dim3(blocks_for(count, 256)), dim3(256), 0, e->stream, A);
   }
   HIPCHK(e, hipGetLastError());
+  KldOutcome dev;
   if (device_count)
+    H2D_OR_RETURN(kld_tree_on_device(e, count, &dev, true));
+  if (dev.handled)
   {
-    bool handled = false;
-    int stop = -1, leaf = 0, bins = 0;
-    int rc = kld_tree_on_device(e, count, &handled, &stop, &leaf, &bins, true);
-    if (rc != BPF_OK)
-      return rc;
-    if (handled)
-    {
-      e->kld_device_used = true;
-      e->kld_leaf = e->kld_bins = bins;
-      e->rng = lcg_skip_host(e->rng, random_consumed, e->jump);
-      e->resample_windows = 1;
-      e->sample_count = count;
-      return BPF_OK;
-    }
+    e->kld_device_used = true;
+    e->kld_leaf = e->kld_bins = dev.bins;
   }
-  int k_stride = count;
-  if (!(zero_copy && wait_generation(e, A.generation)))
+  else
   {
-    if (zero_copy)  // the kernel wrote the host rows; wait for it the slow way
-      HIPCHK(e, hipStreamSynchronize(e->stream));
-    else
-    {
-      HIPCHK(e, hipMemcpyAsync(e->h_keys.p, e->d_keys.p, (size_t)count * 3 * sizeof(int), hipMemcpyDeviceToHost,
-                               e->stream));
-      HIPCHK(e, hipStreamSynchronize(e->stream));
-      k_stride = 0;
-    }
-  }
-  kld_host_reset(e, std::min(count, 1 << 20));
-  const int* keys = e->h_keys.p;
-  for (int m = 0; m < count; ++m)
-  {
-    const int k0 = k_stride ? keys[m] : keys[3 * m], k1 = k_stride ? keys[k_stride + m] : keys[3 * m + 1],
-              k2 = k_stride ? keys[2 * k_stride + m] : keys[3 * m + 2];
-    kld_host_insert(e, k0, k1, k2);
+    KeyView keys{ e->h_keys.p, count };
+    if (!zero_copy)
+      H2D_OR_RETURN(copy_key_triples(e, count, &keys));
+    else if (!wait_generation(e, A.generation))
+      HIPCHK(e, hipStreamSynchronize(e->stream));  // the kernel wrote only the host rows; wait for it the slow way
+    kld_host_reset(e, std::min(count, 1 << 20));
+    for (int m = 0; m < count; ++m)
+      kld_host_insert(e, keys.key(m, 0), keys.key(m, 1), keys.key(m, 2));
   }
   // :316-324: the random pose calls took 2 (retries + 1) uniforms each, right after the systematic start
   e->rng = lcg_skip_host(e->rng, random_consumed, e->jump);
@@ -1348,8 +1310,8 @@ int upload_samples(bpf_engine* e, const double* aos, int n, SampleSet& dst)
 {
   HIPCHK(e, e->d_aos.reserve((size_t)n));
   HIPCHK(e, dst.reserve((size_t)n));
-  // the caller's (pageable) buffer straight to the runtime, which pipelines its own bounce buffers: a staging memcpy of
-  // the whole set on this thread followed by one DMA serialises the two (0.37 against 0.31 ms per update at 100 k)
+  // the caller's buffer goes up the way h2d_from_host decides: through the engine's pinned bounce buffer, piece by
+  // piece, unless it is registered or BPF_OPT_HOST_DIRECT_PAGEABLE hands pageable memory to the runtime as it is
   H2D_OR_RETURN(h2d_from_host(e, e->d_aos.p, aos, (size_t)n * sizeof(double4), e->stream));
   hipLaunchKernelGGL(k_aos_to_soa, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, e->d_aos.p, dst.dev(), n);
   HIPCHK(e, hipGetLastError());

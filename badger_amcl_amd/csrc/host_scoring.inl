@@ -403,12 +403,7 @@ int launch_field(bpf_engine* e, ParticlesDev p, int n, ScanSlot* s, const FieldS
     {
       HIPCHK(e, e->d_chunk_partials.reserve((size_t)n_chunks * n));
       HIPCHK(e, e->d_plan.reserve(1));
-      if (!e->window_lds_attr_set)
-      {
-        HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score_window),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        e->window_lds_attr_set = true;
-      }
+      H2D_OR_RETURN(ensure_dynamic_lds(e, &k_score_window, 160 * 1024));
       {
         ProfScope pa(e, BPF_K_SCORE_AUX);
         hipLaunchKernelGGL(k_field_windows, dim3(1), dim3(1024), 0, e->stream, e->d_prep_stats.p, prep_blocks,

@@ -179,6 +179,50 @@ def test_update_resample_matches_oracle(engine, orc, cloud, n, resampler, serial
     assert st1.last_status == 0
 
 
+@pytest.mark.parametrize("cloud,n", [("converged", 5000), ("spread", 3000)])
+@pytest.mark.parametrize("resampler", [0, 1])
+def test_update_resample_with_copied_keys_matches_oracle(orc, monkeypatch, cloud, n, resampler):
+    """The ordered host replay from keys that were COPIED from the device (BPF_NO_ZEROCOPY, read when the filter is
+    created: an engine of its own): the resamplers then read AoS triples where the zero-copy hand-off leaves three
+    rows.  Serial CDF, no one-block kernel and no device tree, so both resamplers replay on the host.  The spread cloud
+    has many distinct keys (a rows-for-triples mix-up changes the leaf count), the converged one stops early in the
+    first window.  Exact, as in test_update_resample_matches_oracle."""
+    import badger_amcl_amd as bpf
+    import badger_amcl_amd.pf as hpf
+    monkeypatch.setenv("BPF_NO_ZEROCOPY", "1")
+    e = bpf.Engine(0)
+    try:
+        e.set_option(hpf.OPT_CDF_SERIAL, 1)
+        e.set_option(hpf.OPT_FUSED_RESAMPLE, 0)
+        e.set_option(hpf.OPT_KLD_DEVICE_MIN, 0)
+        sc_ = Scenario(orc, size=400, n=n, beams=91, cloud=cloud)
+        m, sc, pf, data = sc_.gpu_objects(e, 91, "lf", min_samples=100, seed=7)
+        pf.setResampleModel(resampler)
+        sc.updateSensor(pf, data)
+        before = pf.getCurrentSet()
+        st0 = pf.getState()
+        pf.updateResample()
+        after = pf.getCurrentSet()
+        st1 = pf.getState()
+        rng1 = pf.getRngState()
+    finally:
+        e.close()
+    opf, out = _oracle_resample_from(orc, before.samples, st0.w_slow, st0.w_fast, st0.leaf_count, 7, resampler,
+                                     100, n)
+    assert out.status == 0
+    assert st1.kld_on_device == 0
+    assert st1.sample_count == out.sample_count
+    assert st1.leaf_count == out.leaf_count
+    assert st1.bin_count == out.node_count
+    M = out.sample_count
+    assert np.array_equal(after.samples[:, :3], opf.samples[:M, :3])
+    assert np.all(after.samples[:, 3] == 1.0 / M)
+    assert rng1 == opf.pf.rng
+    assert st1.converged == out.converged
+    assert abs(st1.percent_converged - out.percent_converged) < 1e-4
+    assert st1.last_status == 0
+
+
 @pytest.mark.parametrize("cloud,n,pop", [("spread", 3000, None), ("converged", 3000, None), ("mixture", 20000, None),
                                          ("spread", 30000, (0.0025, 0.9975)), ("mixture", 9000, (0.05, 0.99))])
 @pytest.mark.parametrize("persistent", [0, 1])
