@@ -477,12 +477,16 @@ CYCLES = 2
 N2 = 6000
 
 
-def _scenario2():
+def _scenario2(geometry=None):
+    """geometry: None = the square 400 x 400 map, else a name of map_geometry.GEOMETRIES (a rectangle)."""
     from oracle import pyoracle as orc
-    return orc, Scenario(orc, size=400, n=256, beams=181)
+    if geometry is None:
+        return orc, Scenario(orc, size=400, n=256, beams=181)
+    from map_geometry import GeoScenario
+    return orc, GeoScenario.named(orc, geometry, n=256, beams=181)
 
 
-def _worker(rank, world, port, out_dir, resampler, exchange):
+def _worker(rank, world, port, out_dir, resampler, exchange, geometry=None):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, HERE)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -493,7 +497,7 @@ def _worker(rank, world, port, out_dir, resampler, exchange):
     import badger_amcl_amd as bpf
     import badger_amcl_amd.pf as hpf
     from badger_amcl_amd.sharded import HipShardBackend, ShardedFilter
-    orc, sc = _scenario2()
+    orc, sc = _scenario2(geometry)
     e = bpf.Engine(0)
     m, scn, _, data = sc.gpu_objects(e, 181, "lf")
     pf = bpf.ParticleFilter(e, 100, N2, 0.0, 0.0, 85.0)
@@ -535,13 +539,26 @@ def _worker(rank, world, port, out_dir, resampler, exchange):
 def test_two_processes_init_and_two_cycles_equal_single_engine(tmp_path, resampler, exchange):
     """ShardedFilter.init_with_random_poses() in two processes on the one GPU -- over the mailbox (the engine's one-call
     form does the exchanges) and over gloo (staged through the host) -- then two full cycles and get_max_weight_pose."""
+    _two_processes_against_single_engine(tmp_path, resampler, exchange, None)
+
+
+def test_two_processes_init_on_a_rectangular_map_equals_single_engine(tmp_path):
+    """The same on G1 of map_geometry.py (333 x 150, so that the free-space list's i-outer order and the two half
+    sizes of the conversion back to the world matter): the two ranks' random poses are the single engine's."""
+    _two_processes_against_single_engine(tmp_path, 0, "mailbox", "G1")
+
+
+def _two_processes_against_single_engine(tmp_path, resampler, exchange, geometry):
     import torch.multiprocessing as mp
     port = _free_port()
-    mp.spawn(_worker, args=(2, port, str(tmp_path), resampler, exchange), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, port, str(tmp_path), resampler, exchange, geometry), nprocs=2, join=True)
     recs = [np.load(os.path.join(str(tmp_path), "rank%d.npy" % r), allow_pickle=True) for r in range(2)]
     import badger_amcl_amd as bpf
     import badger_amcl_amd.pf as hpf
-    orc, sc = _scenario2()
+    orc, sc = _scenario2(geometry)
+    if geometry is not None:
+        first = np.concatenate([recs[0][0]["samples"], recs[1][0]["samples"]])
+        assert sc.transposed_blind_fraction(first) >= 0.2 and sc.in_map(first).all()
     e = bpf.Engine(0)
     try:
         m, scn, _, data = sc.gpu_objects(e, 181, "lf")

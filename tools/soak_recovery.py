@@ -2,6 +2,8 @@
 Node::randomFreeSpacePose, particle_filter.cpp:295-324,383-388) against the oracle over three cycles of progressively
 worse scans: which draws become random poses, the poses, the interleaved drand48 consumption, the grown systematic
 count, the reset of the running averages.  Serial CDF (as tests/test_gpu_parity.py::test_recovery_... runs it).
+About half of the cases run on a rectangular, off-centre map (tests/map_geometry.py, drawn as in soak_score.py), whose
+free-space list the random poses come from.
 usage: python tools/soak_recovery.py [cases] [seed]"""
 import os
 import sys
@@ -14,6 +16,8 @@ import badger_amcl_amd as bpf
 import badger_amcl_amd.pf as hpf
 from oracle import pyoracle as orc
 from scenario import Scenario
+from map_geometry import GeoScenario
+from soak_score import draw_geometry
 
 def run(cases=60, seed=1, e=None, quiet=False):
     """Returns the number of mismatching cases."""
@@ -31,15 +35,23 @@ def run(cases=60, seed=1, e=None, quiet=False):
         alpha = (float(rng.choice([0.001, 0.01])), float(rng.choice([0.1, 0.5])))
         e.set_option(hpf.OPT_KLD_DEVICE_MIN, int(rng.choice([1, 8192])))
         seed = int(rng.integers(1, 100000))
-        sc_ = Scenario(orc, size=200, n=n, beams=61, cloud=str(rng.choice(["mixture", "converged"])),
-                       seed=int(rng.integers(1, 10000)))
+        skw = dict(n=n, beams=61, cloud=str(rng.choice(["mixture", "converged"])), seed=int(rng.integers(1, 10000)))
+        geo = draw_geometry(rng) if rng.random() < 0.5 else None
+        sc_ = Scenario(orc, size=200, **skw) if geo is None else GeoScenario(orc, *geo, **skw)
         m, sc, pf, data = sc_.gpu_objects(e, 61, "lf", min_samples=int(rng.choice([10, 100])), seed=seed, alpha=alpha)
         pf.setResampleModel(resampler)
         pf.setRandomPoseGenerator(hpf.RANDOM_POSE_FREE_SPACE_2D)
         opf = orc.ParticleFilter(pf.min_samples, n, alpha[0], alpha[1], 85.0, seed=seed)
         opf.set_resample_model(resampler)
         opf.set_samples(sc_.samples)
-        opf.set_random_pose_source(sc_.omap, sc_.map_factors[2])
+        if opf.set_random_pose_source(sc_.omap, sc_.map_factors[2]) == 0:
+            # (a small map at the finest resolution: no cell farther than the radius from a wall, nothing to draw from)
+            sc_ = Scenario(orc, size=200, **skw)
+            m, sc, pf, data = sc_.gpu_objects(e, 61, "lf", min_samples=pf.min_samples, seed=seed, alpha=alpha)
+            pf.setResampleModel(resampler)
+            pf.setRandomPoseGenerator(hpf.RANDOM_POSE_FREE_SPACE_2D)
+            opf.set_samples(sc_.samples)
+            opf.set_random_pose_source(sc_.omap, sc_.map_factors[2])
         scans = [sc_.ranges, np.clip(sc_.ranges * float(rng.uniform(0.4, 0.8)), 0.05, 29.0),
                  np.full(61, float(rng.uniform(0.5, 3.0)))]
         ok = True
@@ -66,8 +78,8 @@ def run(cases=60, seed=1, e=None, quiet=False):
                 break
         if not ok:
             bad += 1
-            print("MISMATCH case %d cycle %d: n %d resampler %d alpha %s seed %d w_diff %g/%g M %d/%d" %
-                  (case, cycle, n, resampler, alpha, seed, st1.w_diff, out.w_diff, st1.sample_count, M), flush=True)
+            print("MISMATCH case %d cycle %d: map %s n %d resampler %d alpha %s seed %d w_diff %g/%g M %d/%d" %
+                  (case, cycle, geo, n, resampler, alpha, seed, st1.w_diff, out.w_diff, st1.sample_count, M), flush=True)
     e.set_option(hpf.OPT_CDF_SERIAL, 0)
     e.set_option(hpf.OPT_KLD_DEVICE_MIN, 8192)
     print("%d cases x 3 cycles, %d resamples with w_diff > 0, %d cases mismatching, %.0f s" % (cases, recovered, bad, time.time() - t0))
