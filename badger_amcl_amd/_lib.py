@@ -25,6 +25,11 @@ class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * BPF_K_COUNT), ("launches", C.c_longlong * BPF_K_COUNT)]
 
 
+class PoseHit(C.Structure):
+    _fields_ = [("pose", C.c_double * 3), ("score", C.c_double), ("candidate", C.c_longlong), ("i", C.c_int),
+                ("j", C.c_int), ("heading", C.c_int), ("reserved", C.c_int)]
+
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p
@@ -200,6 +205,11 @@ SIGNATURES = {
     "bpf_kld_insert_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "bpf_kld_stop_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _ip, _ip, _ip, _ip]),
     "bpf_kld_leaf_count": (C.c_int, [_vp, _ip, _ip]),
+    "bpf_planar_search_poses": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_longlong,
+                                          C.c_longlong, C.c_int, C.POINTER(PoseHit), _ip]),
+    "bpf_planar_search_space": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _ip]),
+    "bpf_pose_search_merge": (C.c_int, [C.POINTER(PoseHit), _ip, C.c_int, C.c_int, C.POINTER(PoseHit), _ip]),
+    "bpf_pose_search_window": (C.c_int, []),
     "bpf_device_memory_info": (C.c_int, [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "bpf_profile_enable": (C.c_int, [_vp, C.c_int]),
     "bpf_profile_reset": (C.c_int, [_vp]),

@@ -31,6 +31,7 @@
 #include "kernels_recovery.hpp"
 #include "kernels_pf.hpp"
 #include "kernels_pose_array.hpp"
+#include "kernels_pose_search.hpp"
 #include "kernels_fused.hpp"
 #include "kernels_stats.hpp"
 #include "kernels_shard_stats.hpp"
@@ -80,6 +81,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_shard_inplace_mn.inl"
 #include "abi_shard_rebalance.inl"
 #include "abi_pose_array.inl"
+#include "abi_pose_search.inl"
 #include "abi_bootstrap.inl"
 #include "abi_shard_local.inl"
 #include "abi_measure.inl"

@@ -433,6 +433,20 @@ struct bpf_engine
   DevBuf<long long> d_pa_gather;    // int64[3][count]: every rank's rows in global order
   DevBuf<double> d_pa_out;          // double[count][7]: the formed poses on their way to the host
 
+  // ---- exhaustive pose search (kernels_pose_search.hpp, abi_pose_search.inl): the strided free list F_s, cached per
+  // (map version, radius, stride) like d_free_ij (stride 1 is d_free_ij itself), and the selection's buffers.  The
+  // candidate poses live in `cand`; nothing here describes the particle set
+  DevBuf<int2> d_free_s;
+  int n_free_s = 0;
+  int free_s_map_version = -1, free_s_stride = 0;
+  double free_s_radius = -1.0;
+  DevBuf<SearchEntry> d_search_best;   // [kSearchMaxK] the running best-K list, best first
+  DevBuf<SearchEntry> d_search_tiles;  // [tiles of a window][k] what every block of k_search_select kept
+  DevBuf<int> d_search_counts;         // [0] entries in d_search_best, [1 ...] per tile
+  DevBuf<bpf_pose_hit> d_search_hits;  // [kSearchMaxK] the rows on their way to the host
+  PinnedBuf<bpf_pose_hit> h_search_hits;
+  PinnedBuf<int> h_search_count;
+
   // ---- KLD stop rule on the device (long draw streams)
   int kld_device_min = 8192;  // draws left after the first window from which the device tree takes over
   bool kld_device_used = false;

@@ -190,6 +190,55 @@ int launch_converged(bpf_engine* e)
 
 bool pose_check_scored(const bpf_engine* e);
 
+// The list of Node2D::updateFreeSpaceIndices (node_2d.cpp:317-337) on the device for the current 2-D map and
+// non_free_space_radius: FREE cells whose LUT distance (compared in double) is > radius, i outer, j inner; with
+// stride s > 1 the entries with i % s == 0 && j % s == 0, in the same order.  Built on the host once per (map version,
+// radius[, stride]) -- stride 1 in d_free_ij / n_free, the last other stride in d_free_s / n_free_s.  The caller has
+// checked have_map && have_lut; no generator mode is asked for (ensure_free_space keeps those checks).
+int ensure_free_list(bpf_engine* e, int stride, const int2** cells_out, int* n_out)
+{
+  const double radius = e->pm.non_free_radius;
+  const bool unit = stride == 1;
+  DevBuf<int2>& buf = unit ? e->d_free_ij : e->d_free_s;
+  int& n = unit ? e->n_free : e->n_free_s;
+  const bool cached = unit ? (e->free_map_version == e->map_version && e->free_radius == radius)
+                           : (e->free_s_map_version == e->map_version && e->free_s_radius == radius &&
+                              e->free_s_stride == stride);
+  if (!cached)
+  {
+    const int sx = e->map.size_x, sy = e->map.size_y;
+    std::vector<int2> ij;
+    ij.reserve(((size_t)sx / stride + 1) * ((size_t)sy / stride + 1) / 2);
+    for (int i = 0; i < sx; i += stride)
+      for (int j = 0; j < sy; j += stride)
+      {
+        const size_t idx = i + (size_t)j * sx;
+        if (e->h_cells8[idx] == -1 && (double)e->h_lut_f32[idx] > radius)
+          ij.push_back(make_int2(i, j));
+      }
+    n = (int)ij.size();
+    HIPCHK(e, buf.reserve(std::max<size_t>(ij.size(), 1)));
+    if (!ij.empty())
+      H2D_OR_RETURN(h2d_from_host_sync(e, buf.p, ij.data(), ij.size() * sizeof(int2)));
+    if (unit)
+    {
+      e->free_map_version = e->map_version;
+      e->free_radius = radius;
+    }
+    else
+    {
+      e->free_s_map_version = e->map_version;
+      e->free_s_radius = radius;
+      e->free_s_stride = stride;
+    }
+  }
+  if (cells_out)
+    *cells_out = buf.p;
+  if (n_out)
+    *n_out = n;
+  return BPF_OK;
+}
+
 // Node2D::updateFreeSpaceIndices (node_2d.cpp:317-337) for the current map and non_free_space_radius, cached; or
 // Node3D::updateFreeSpaceIndices (node_3d.cpp:306-318) over the 3-D map's cell bounds.  out->retries = the trials
 // every call of Node::uniformPoseGenerator rejects (bpf_pf_set_uniform_pose_check).
@@ -225,26 +274,9 @@ int ensure_free_space(bpf_engine* e, FreeSpaceDev* out)
   }
   if (!e->have_map || !e->have_lut)
     return e->fail(BPF_ERR_NOT_CONFIGURED, "random free-space poses need the 2-D map and its distance LUT");
-  const double radius = e->pm.non_free_radius;
-  if (e->free_map_version != e->map_version || e->free_radius != radius)
-  {
-    const int sx = e->map.size_x, sy = e->map.size_y;
-    std::vector<int2> ij;
-    ij.reserve((size_t)sx * sy / 2);
-    for (int i = 0; i < sx; ++i)
-      for (int j = 0; j < sy; ++j)
-      {
-        const size_t idx = i + (size_t)j * sx;
-        if (e->h_cells8[idx] == -1 && (double)e->h_lut_f32[idx] > radius)
-          ij.push_back(make_int2(i, j));
-      }
-    e->n_free = (int)ij.size();
-    HIPCHK(e, e->d_free_ij.reserve(std::max<size_t>(ij.size(), 1)));
-    if (!ij.empty())
-      H2D_OR_RETURN(h2d_from_host_sync(e, e->d_free_ij.p, ij.data(), ij.size() * sizeof(int2)));
-    e->free_map_version = e->map_version;
-    e->free_radius = radius;
-  }
+  int rcl = ensure_free_list(e, 1, nullptr, nullptr);
+  if (rcl != BPF_OK)
+    return rcl;
   if (e->n_free <= 0)
     return e->fail(BPF_ERR_NOT_CONFIGURED, "the map has no free cell to draw random poses from");
   out->ij = e->d_free_ij.p;

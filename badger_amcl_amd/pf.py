@@ -524,6 +524,57 @@ class PlanarScanner:
             self.e.check(status.value)
         return total
 
+    def searchSpace(self, headings, cell_stride=1):
+        """(candidates, free cells) of searchPoses for the current map and non_free_space_radius:
+        candidates = free cells kept by cell_stride x headings, what a caller splits into ranges."""
+        if self.map is not None:
+            self.map.upload()
+        total, cells = C.c_longlong(), C.c_int()
+        self.e.check(self.e.lib.bpf_planar_search_space(self.e.h, int(headings), int(cell_stride), C.byref(total),
+                                                        C.byref(cells)))
+        return total.value, cells.value
+
+    def searchPoses(self, data, headings, cell_stride, k, first=0, count=-1):
+        """NOT a reference method: every free cell (every cell_stride-th in i and j) at `headings` headings scored
+        against `data` on the device, the best k of candidates first .. first + count - 1 as a POSE_HIT_DTYPE array
+        (score descending, equal scores by candidate).  See bpf_planar_search_poses in include/badger_pf.h."""
+        if self.map is not None:
+            self.map.upload()
+        hits = np.zeros(max(int(k), 1), dtype=POSE_HIT_DTYPE)
+        n = C.c_int()
+        rp, ap = data.pointers()
+        self.e.check(self.e.lib.bpf_planar_search_poses(
+            self.e.h, rp, ap, data.range_count_, data.range_max_, int(headings), int(cell_stride), int(first),
+            int(count), int(k), hits.ctypes.data_as(C.POINTER(_lib.PoseHit)), C.byref(n)))
+        return hits[:n.value]
+
+
+# one row of a pose search: bpf_pose_hit
+POSE_HIT_DTYPE = np.dtype([("pose", "<f8", (3,)), ("score", "<f8"), ("candidate", "<i8"), ("i", "<i4"), ("j", "<i4"),
+                           ("heading", "<i4"), ("reserved", "<i4")])
+assert POSE_HIT_DTYPE.itemsize == C.sizeof(_lib.PoseHit)
+
+
+def pose_search_window():
+    """Candidates a pose search scores per window (an internal constant; needs no GPU)."""
+    return int(_lib.load().bpf_pose_search_window())
+
+
+def merge_pose_hits(lists, k):
+    """The best k rows of the hit lists of disjoint candidate ranges, in searchPoses' order (plain host code)."""
+    lists = [np.ascontiguousarray(h, dtype=POSE_HIT_DTYPE) for h in lists]
+    flat = np.concatenate(lists) if lists else np.zeros(0, dtype=POSE_HIT_DTYPE)
+    flat = np.ascontiguousarray(flat)
+    lengths = np.array([h.shape[0] for h in lists] + [0], dtype=np.int32)
+    out = np.zeros(max(int(k), 1), dtype=POSE_HIT_DTYPE)
+    n = C.c_int()
+    rc = _lib.load().bpf_pose_search_merge(flat.ctypes.data_as(C.POINTER(_lib.PoseHit)),
+                                           lengths.ctypes.data_as(C.POINTER(C.c_int)), len(lists), int(k),
+                                           out.ctypes.data_as(C.POINTER(_lib.PoseHit)), C.byref(n))
+    if rc != 0:
+        raise BpfError(rc, _lib.load().bpf_error_string(rc).decode())
+    return out[:n.value]
+
 
 # --------------------------------------------------------------------------------- 3-D
 class OctoMap:

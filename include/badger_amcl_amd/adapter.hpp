@@ -416,6 +416,50 @@ public:
     return total;
   }
 
+  // NOT a reference method (bpf_planar_search_poses): every free cell of the map (every cell_stride-th in i and j) at
+  // `headings` headings scored against `data` on the device; the best k of candidates first .. first + count - 1
+  // (count = -1: to the end), score descending, equal scores by candidate.  A global-localisation service turns the
+  // hits into a sample set (ParticleFilter::initWithSamples).
+  std::vector<bpf_pose_hit> searchPoses(std::shared_ptr<PlanarData> data, int headings, int cell_stride, int k,
+                                        long long first = 0, long long count = -1)
+  {
+    if (map_)
+      map_->upload();
+    std::vector<bpf_pose_hit> hits((size_t)(k > 0 ? k : 1));
+    int n = 0;
+    e_->check(bpf_planar_search_poses(e_->get(), data->ranges_.data(), data->angles_.data(), data->range_count_,
+                                      data->range_max_, headings, cell_stride, first, count, k, hits.data(), &n));
+    hits.resize((size_t)n);
+    return hits;
+  }
+  // candidates (free cells kept by cell_stride x headings) of searchPoses: what a caller splits into ranges
+  long long searchSpace(int headings, int cell_stride = 1, int* free_cells_out = nullptr)
+  {
+    if (map_)
+      map_->upload();
+    long long total = 0;
+    e_->check(bpf_planar_search_space(e_->get(), headings, cell_stride, &total, free_cells_out));
+    return total;
+  }
+  // the best k of the hit lists of disjoint ranges, in searchPoses' order (host code, no engine)
+  static std::vector<bpf_pose_hit> mergePoseHits(const std::vector<std::vector<bpf_pose_hit>>& lists, int k)
+  {
+    std::vector<bpf_pose_hit> flat;
+    std::vector<int> lengths;
+    for (const auto& l : lists)
+    {
+      flat.insert(flat.end(), l.begin(), l.end());
+      lengths.push_back((int)l.size());
+    }
+    std::vector<bpf_pose_hit> out((size_t)(k > 0 ? k : 1));
+    int n = 0;
+    const int rc = bpf_pose_search_merge(flat.data(), lengths.data(), (int)lists.size(), k, out.data(), &n);
+    if (rc != BPF_OK)
+      throw std::runtime_error(std::string("bpf_pose_search_merge: ") + bpf_error_string(rc));
+    out.resize((size_t)n);
+    return out;
+  }
+
 private:
   std::shared_ptr<Engine> e_;
   std::shared_ptr<OccupancyMap> map_;

@@ -1114,6 +1114,57 @@ int bpf_wire_decimate_cloud(const float* points_xyz, int n_points, int max_beams
  * with q = setRPY(0, 0, theta). */
 int bpf_wire_samples_to_pose_array(const double* samples, int sample_count, double* poses7_out);
 
+/* ------------------------------------------------------------------ exhaustive pose search
+ * Global localisation without the lottery of random trial poses: every free cell of the 2-D map at every one of
+ * `headings` headings is scored against one scan, and the best k candidates come back.  NOT a reference call (parity
+ * unpinned by construction); the score is the one BPF_POSE_CHECK_SENSOR_MODEL uses.
+ *
+ * Free list F: Node2D::updateFreeSpaceIndices for the current map and the non_free_space_radius of
+ * bpf_planar_set_map_factors (FREE cells whose LUT distance, compared in double, is > radius; i outer, j inner).
+ * cell_stride s >= 1 keeps the entries with i % s == 0 && j % s == 0, in the same order: F_s.
+ * Candidate c in [0, |F_s| * headings) is cell f = c / headings at heading h = c % headings, with the pose
+ *   x = origin_x + (i - size_x / 2) * resolution, y = origin_y + (j - size_y / 2) * resolution   (integer halves),
+ *   theta = (2.0 * pi * h) / headings - pi   (pi = 3.14159265358979323846, evaluated in double as written).
+ * Its score is the weight of the one-sample set {pose, 1.0} after PlanarScanner::applyModelToSampleSet with
+ * set->converged = 0 (no beam skipping) against the scan given here, under the planar model, map factors and scanner
+ * pose configured on the engine; with max_beams < 2 that is 1.0.  Status codes of the scoring path pass through
+ * (BPF_ERR_BEAM_STEP, BPF_ERR_NOT_CONFIGURED ...).
+ *
+ * Result: the best min(k, count) candidates of [first, first + count), by score descending, equal scores by
+ * candidate ascending; a NaN score ranks below every number.  count = -1: to the end of the space.
+ * Limits: 1 <= k <= 1024, headings >= 1, cell_stride >= 1 and first / count inside the space, otherwise
+ * BPF_ERR_INVALID_ARGUMENT; |F_s| * headings > 2^31 - 1 returns BPF_ERR_CAPACITY before anything is launched.
+ * A map without a free cell beyond the radius gives *n_hits_out = 0 and BPF_OK.
+ *
+ * The call needs the 2-D map, its LUT and a planar model (BPF_ERR_NOT_CONFIGURED without them, also when only the
+ * cloud scanner is configured); it needs no filter and leaves one as it found it: sets, weights and the caches
+ * behind them, the drand48 state, w_slow / w_fast, the beam-skip working data, the scan remembered for the pose
+ * check, last_status and the lazy statistics.  Candidates are generated, scored and selected on the device in
+ * windows of bpf_pose_search_window() candidates, all enqueued back to back; the host waits once. */
+typedef struct
+{
+  double pose[3];      /* x, y, theta of the candidate */
+  double score;
+  long long candidate; /* c */
+  int i, j;            /* its map cell */
+  int heading;         /* h */
+  int reserved;
+} bpf_pose_hit;
+
+int bpf_planar_search_poses(bpf_engine* e, const double* ranges, const double* angles, int range_count,
+                            double range_max, int headings, int cell_stride, long long first, long long count,
+                            int k, bpf_pose_hit* hits_out, int* n_hits_out);
+/* |F_s| * headings for the current map and radius: what a caller splits into ranges (the product itself, also when
+ * it is past the limit of a search) */
+int bpf_planar_search_space(bpf_engine* e, int headings, int cell_stride, long long* candidates_out,
+                            int* free_cells_out);
+/* merges hit lists of disjoint ranges (n_lists lists back to back in `lists`, list_lengths[l] rows each) into the
+ * best k, same order rule; plain host code, needs no engine */
+int bpf_pose_search_merge(const bpf_pose_hit* lists, const int* list_lengths, int n_lists, int k,
+                          bpf_pose_hit* hits_out, int* n_hits_out);
+/* candidates scored per window, an internal constant the tests size their cases from; needs no engine */
+int bpf_pose_search_window(void);
+
 /* ------------------------------------------------------------------ measurement */
 /* free / total device memory as hipMemGetInfo reports it (diagnostic; used by the leak test) */
 int bpf_device_memory_info(int device_ordinal, size_t* free_bytes, size_t* total_bytes);
