@@ -210,7 +210,7 @@ int bpf_pf_update_sensor_planar(bpf_engine* e, const double* ranges, const doubl
   if (e->pm.max_beams < 2)
     return BPF_OK;  // PlanarScanner::updateSensor returns false and touches nothing (:128-129)
   HIPCHK(e, hipSetDevice(e->device));
-  if (e->pm.model == BPF_MODEL_LIKELIHOOD_FIELD_PROB && e->pm.do_beamskip && e->converged_pending)
+  if (e->pm.beamskip_armed(e->converged_pending))
   {
     int rc = fetch_scalars(e);
     if (rc != BPF_OK)

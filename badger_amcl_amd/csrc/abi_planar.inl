@@ -119,7 +119,50 @@ bool seam_wait_word(const unsigned long long* word, unsigned long long value)
   return spin_until([&] { return __atomic_load_n(word, __ATOMIC_ACQUIRE) == value; }, 50);
 }
 
-// Seam A on a REGISTERED host buffer, one scoring launch and no copy in either direction (HOST_MODE 2 of
+// What both host-buffer forms below ask of the configuration (not the beam model, no beam skipping, a table that
+// fits LDS); without it the caller runs the plain sequence, which also reports what is missing.
+bool field_seam_takes(const bpf_engine* e, int set_converged, const double* ranges, const double* angles, int rc)
+{
+  const PlanarModel& pm = e->pm;
+  if (!e->have_map || !e->have_lut || !pm.configured || rc <= 0 || !ranges || !angles)
+    return false;
+  if (pm.model == BPF_MODEL_BEAM || pm.beamskip_armed(set_converged != 0))
+    return false;
+  return e->map.n_levels + 1 <= kTableLdsMax;
+}
+
+// the device's view of n records in a registered host range; nullptr when the range is not registered or has no view
+double4* seam_device_view(bpf_engine* e, double* samples, int n)
+{
+  const bpf_engine::HostReg* r = host_reg_find(e, samples, (size_t)n * sizeof(double4));
+  if (r == nullptr || r->dev_base == 0)
+    return nullptr;
+  return reinterpret_cast<double4*>(r->dev_base + (reinterpret_cast<uintptr_t>(samples) - r->base));
+}
+
+// BPF_DEBUG_SEAM: the stage clocks of every call on stderr.  Microseconds; 0 when off.
+bool seam_debug()
+{
+  static const bool on = getenv("BPF_DEBUG_SEAM") != nullptr;
+  return on;
+}
+double seam_clock()
+{
+  if (!seam_debug())
+    return 0.0;
+  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// An error after the scan was staged: the copy engine and the launches already issued read the caller's buffer and
+// the staging block -- let them finish before returning; the slot's guard then hands the block back to the ring.
+int seam_bail(bpf_engine* e, int rcode)
+{
+  (void)hipStreamSynchronize(e->copy_up);
+  (void)hipStreamSynchronize(e->stream);
+  return rcode;
+}
+
+// Seam A on a REGISTERED host buffer, one scoring launch and no copy in either direction (the HOST_RECORDS form of
 // k_score_field): the waves read the caller's records over PCIe as they reach them and write them back whole with the
 // new weight; k_seam_done folds the total and publishes the word this thread polls.  Nothing is left for the host to
 // do but wait.  Same per-particle arithmetic as the resident form (field_prep_of, same beams and table): the same
@@ -128,48 +171,37 @@ int apply_model_records(bpf_engine* e, double* samples, int n, int set_converged
                         const double* angles, int rc, double range_max, bool* done)
 {
   *done = false;
-  const PlanarModel& pm = e->pm;
-  if (e->seam_chunks != 0 || !e->have_map || !e->have_lut || !pm.configured || rc <= 0 || !ranges || !angles || n < 4096)
-    return BPF_OK;
-  if (pm.model == BPF_MODEL_BEAM || (pm.model == BPF_MODEL_LIKELIHOOD_FIELD_PROB && pm.do_beamskip && set_converged))
-    return BPF_OK;
-  if (e->map.n_levels + 1 > kTableLdsMax)
+  if (e->seam_chunks != 0 || n < 4096 || !field_seam_takes(e, set_converged, ranges, angles, rc))
     return BPF_OK;
   if (!host_buffer_pinned(e, samples, (size_t)n * sizeof(double4)))
     return BPF_OK;
-  const bpf_engine::HostReg* r = host_reg_find(e, samples, (size_t)n * sizeof(double4));
-  if (r == nullptr || r->dev_base == 0 || (reinterpret_cast<uintptr_t>(samples) & 15) != 0)
+  double4* rec = seam_device_view(e, samples, n);
+  if (rec == nullptr || (reinterpret_cast<uintptr_t>(samples) & 15) != 0)
     return BPF_OK;  // (the records are read and written as 16-byte pairs)
-  double4* rec = reinterpret_cast<double4*>(r->dev_base + (reinterpret_cast<uintptr_t>(samples) - r->base));
-  int rcode = seam_resources(e);
-  if (rcode != BPF_OK)
-    return rcode;
-  static const bool dbg = getenv("BPF_DEBUG_SEAM") != nullptr;
-  auto now = []() {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  };
-  const double t0 = dbg ? now() : 0.0;
+  H2D_OR_RETURN(seam_resources(e));
+  const double t0 = seam_clock();
   e->weights_overwritten();
-  ScanSlot* s = nullptr;
+  StagedSlot s;
   FieldScan fs;
-  rcode = stage_field_scan(e, ranges, angles, rc, range_max, &s, &fs);
-  if (rcode != BPF_OK)
-    return rcode;
+  H2D_OR_RETURN(stage_field_scan(e, ranges, angles, rc, range_max, &s, &fs));
+  auto bail = [e](int rcode) { return seam_bail(e, rcode); };
   e->evals_last = (long long)n * fs.n_valid;
   const unsigned long long gen = ++e->seam_generation;
   const FieldHostOut out{ rec, nullptr, e->h_seam_totals.p, e->d_seam_partials.p, e->h_seam_flags.p, gen };
-  rcode = launch_field(e, ParticlesDev{ nullptr, nullptr, nullptr, nullptr }, n, s, fs, nullptr, 0, false, nullptr, &out);
+  FieldRequest req;
+  req.host_out = &out;
+  int rcode = launch_field(e, ParticlesDev{ nullptr, nullptr, nullptr, nullptr }, n, s.get(), fs, req);
+  if (rcode == BPF_OK)
+    rcode = s.commit();
   if (rcode != BPF_OK)
-    return rcode;
-  rcode = release_slot(e, s);
-  if (rcode != BPF_OK)
-    return rcode;
-  const double t1 = dbg ? now() : 0.0;
+    return bail(rcode);
+  const double t1 = seam_clock();
   if (!seam_wait_word(e->h_seam_flags.p, gen))
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    HIPCHK_OR(e, hipStreamSynchronize(e->stream), bail);
   e->h_scalars.p->v[0] = *const_cast<const volatile double*>(e->h_seam_totals.p);
-  if (dbg)
-    fprintf(stderr, "seam: records in place, one launch: stage + issue %.1f us, waiting %.1f us\n", t1 - t0, now() - t1);
+  if (seam_debug())
+    fprintf(stderr, "seam: records in place, one launch: stage + issue %.1f us, waiting %.1f us\n", t1 - t0,
+            seam_clock() - t1);
   e->last_seam_chunks = -1;
   e->last_seam_registered = true;
   *done = true;
@@ -180,7 +212,7 @@ int apply_model_records(bpf_engine* e, double* samples, int n, int set_converged
 // tools/ubench/pcie_probe.hip): 64 us for the 3.2 MB upload (the link's rate, pinned or not), 5 + 77 us for the
 // launches, ~10 us for the total, 22-44 us for the download of the weights, ~30 us for this thread to write them into
 // the caller's records, and a stream synchronisation.  Here the set goes up in a few chunks on a copy stream; chunk k
-// is unpacked and scored (k_field_prep_aos + the HOST_OUT form of k_score_field on its range) while chunk k + 1 is
+// is unpacked and scored (k_field_prep_aos + the HOST_WEIGHTS form of k_score_field on its range) while chunk k + 1 is
 // still crossing PCIe; the scoring launch stores the weights into a pinned host array as it finishes them (dense
 // 8-byte stores, they leave while the kernel works: no download) and a one-block launch behind it folds the chunk's
 // total and publishes a word in pinned memory; this thread polls that word and writes chunk k's weights into the
@@ -189,18 +221,13 @@ int apply_model_records(bpf_engine* e, double* samples, int n, int set_converged
 // thread, and a cross-stream dependency ~10 us of latency, which is why the download stream and its events are gone.
 // The per-particle arithmetic is that of the one-launch form (same kernels, same beams and table), so the weights are
 // the same bits; the total is the sum of the chunks' totals, each the fixed-shape sum of its launch's block partials.
-// Sets *done = false when the configuration is not one it takes (beam model, beam skipping, a small set, a table
-// that does not fit LDS): the caller then runs the plain sequence.
+// Sets *done = false when the configuration is not one it takes (field_seam_takes, a small set): the caller then
+// runs the plain sequence.
 int apply_model_pipelined(bpf_engine* e, double* samples, int n, int set_converged, const double* ranges,
                           const double* angles, int rc, double range_max, bool* done)
 {
   *done = false;
-  const PlanarModel& pm = e->pm;
-  if (!e->have_map || !e->have_lut || !pm.configured || rc <= 0 || !ranges || !angles)
-    return BPF_OK;  // the plain sequence reports what is missing
-  if (pm.model == BPF_MODEL_BEAM || (pm.model == BPF_MODEL_LIKELIHOOD_FIELD_PROB && pm.do_beamskip && set_converged))
-    return BPF_OK;
-  if (e->map.n_levels + 1 > kTableLdsMax)
+  if (!field_seam_takes(e, set_converged, ranges, angles, rc))
     return BPF_OK;
   // two chunks by default: a chunk costs ~35 us of pipeline granularity on this platform (a copy's fixed 9 us, a
   // cross-stream dependency's ~10 us, ~15 us of API calls by this thread), which more chunks do not win back
@@ -208,15 +235,9 @@ int apply_model_pipelined(bpf_engine* e, double* samples, int n, int set_converg
   chunks = std::min(std::min(chunks, kSeamMaxChunks), n / 64);
   if (chunks < 2)
     return BPF_OK;
-  int rcode = seam_resources(e);
-  if (rcode != BPF_OK)
-    return rcode;
+  H2D_OR_RETURN(seam_resources(e));
   const bool pinned = host_buffer_pinned(e, samples, (size_t)n * sizeof(double4));
-  static const bool dbg = getenv("BPF_DEBUG_SEAM") != nullptr;  // stage clocks of every call on stderr
-  auto now = []() {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  };
-  const double t0 = dbg ? now() : 0.0;
+  const double t0 = seam_clock();
   e->weights_overwritten();
   HIPCHK(e, e->d_aos.reserve((size_t)n));
   HIPCHK(e, e->scratch.reserve((size_t)n));
@@ -227,11 +248,10 @@ int apply_model_pipelined(bpf_engine* e, double* samples, int n, int set_converg
   // and this thread would read the previous call's weights (seen once in ~20 runs of the test suite).
   e->h_seam_w.coherent = true;
   HIPCHK(e, e->h_seam_w.reserve((size_t)n));
-  ScanSlot* s = nullptr;
+  StagedSlot s;
   FieldScan fs;
-  rcode = stage_field_scan(e, ranges, angles, rc, range_max, &s, &fs);
-  if (rcode != BPF_OK)
-    return rcode;
+  H2D_OR_RETURN(stage_field_scan(e, ranges, angles, rc, range_max, &s, &fs));
+  auto bail = [e](int rcode) { return seam_bail(e, rcode); };
   e->evals_last = (long long)n * fs.n_valid;
   double* hw = e->h_seam_w.p;
   const double4* src = reinterpret_cast<const double4*>(samples);
@@ -240,82 +260,76 @@ int apply_model_pipelined(bpf_engine* e, double* samples, int n, int set_converg
   // (zero-copy, ~25 us per MB), in stream order -- a copy on the other stream costs 9 us of set-up and ~18 us until
   // the dependent launch starts, with nothing to hide them behind at the start of the call.  The first chunk is
   // the smaller one then (40 %): the second chunk's copy (which runs beside it from the start) is there when it ends.
-  const double4* dev_view = nullptr;
-  if (pinned)
-    if (const bpf_engine::HostReg* r = host_reg_find(e, samples, (size_t)n * sizeof(double4)))
-      if (r->dev_base != 0)
-        dev_view = reinterpret_cast<const double4*>(r->dev_base + (reinterpret_cast<uintptr_t>(samples) - r->base));
+  const double4* dev_view = pinned ? seam_device_view(e, samples, n) : nullptr;
   const bool first_direct = dev_view != nullptr && chunks == 2 && e->seam_chunks == 0;
-  auto lo_of = [&](int c) {
-    const long long num = first_direct && c == 1 ? (long long)n * 2 / 5 : (long long)n * c / chunks;
-    return (int)(num & ~63ll);
+  struct Range
+  {
+    int lo, hi;
+  };
+  auto chunk_range = [&](int c) {
+    auto lo_of = [&](int k) {
+      const long long num = first_direct && k == 1 ? (long long)n * 2 / 5 : (long long)n * k / chunks;
+      return (int)(num & ~63ll);
+    };
+    return Range{ lo_of(c), c + 1 == chunks ? n : lo_of(c + 1) };
   };
   // every upload first: a pinned buffer costs this thread a microsecond per call, and the copy engine then has its
   // whole queue; a pageable one is staged by this thread inside the call, so its chunks are issued one ahead of the
   // launches instead (the staging of chunk k + 1 then runs beside the scoring of chunk k)
   auto upload = [&](int c) -> int {
-    const int lo = lo_of(c), hi = c + 1 == chunks ? n : lo_of(c + 1);
-    H2D_OR_RETURN(h2d_from_host(e, e->d_aos.p + lo, src + lo, (size_t)(hi - lo) * sizeof(double4), e->copy_up));
+    const Range r = chunk_range(c);
+    H2D_OR_RETURN(h2d_from_host(e, e->d_aos.p + r.lo, src + r.lo, (size_t)(r.hi - r.lo) * sizeof(double4), e->copy_up));
     HIPCHK(e, hipEventRecord(e->seam_ev[c], e->copy_up));
     return BPF_OK;
   };
+  int rcode = BPF_OK;
   if (pinned)
     for (int c = first_direct ? 1 : 0; c < chunks; ++c)
       if ((rcode = upload(c)) != BPF_OK)
-        return rcode;
+        return bail(rcode);
   for (int c = 0; c < chunks; ++c)
   {
-    const int lo = lo_of(c), hi = c + 1 == chunks ? n : lo_of(c + 1), cnt = hi - lo;
+    const Range r = chunk_range(c);
     const bool direct = first_direct && c == 0;
     if (!pinned && (rcode = upload(c)) != BPF_OK)
-      return rcode;
+      return bail(rcode);
     if (!direct)
-      HIPCHK(e, hipStreamWaitEvent(e->stream, e->seam_ev[c], 0));
+      HIPCHK_OR(e, hipStreamWaitEvent(e->stream, e->seam_ev[c], 0), bail);
     ParticlesDev p = e->scratch.dev();
-    p.x += lo; p.y += lo; p.th += lo; p.w += lo;
+    p.x += r.lo; p.y += r.lo; p.th += r.lo; p.w += r.lo;
     FieldScan fc = fs;
     fc.copy_pending = fs.copy_pending && c == 0;  // the staging block rides with the first chunk's prep launch
-    const FieldHostOut out{ nullptr, hw + lo, e->h_seam_totals.p + c, e->d_seam_partials.p + (size_t)c * kSeamMaxBlocks,
-                            e->h_seam_flags.p + c, gen };
-    rcode = launch_field(e, p, cnt, s, fc, nullptr, 0, false, direct ? dev_view + lo : e->d_aos.p + lo, &out);
-    if (rcode != BPF_OK)
-    {
-      // the copy engine and the launches already issued read the caller's buffer: let them finish before returning
-      (void)hipStreamSynchronize(e->copy_up);
-      (void)hipStreamSynchronize(e->stream);
-      return rcode;
-    }
+    const FieldHostOut out{ nullptr, hw + r.lo, e->h_seam_totals.p + c,
+                            e->d_seam_partials.p + (size_t)c * kSeamMaxBlocks, e->h_seam_flags.p + c, gen };
+    FieldRequest req;
+    req.aos = direct ? dev_view + r.lo : e->d_aos.p + r.lo;
+    req.host_out = &out;
+    if ((rcode = launch_field(e, p, r.hi - r.lo, s.get(), fc, req)) != BPF_OK)
+      return bail(rcode);
   }
-  rcode = release_slot(e, s);
-  if (rcode != BPF_OK)
-    return rcode;
-  const double t1 = dbg ? now() : 0.0;
+  if ((rcode = s.commit()) != BPF_OK)
+    return bail(rcode);
+  const double t1 = seam_clock();
   double t_wait = 0.0, t_scatter = 0.0;
   bool synced = false;
   double total = 0.0;
   for (int c = 0; c < chunks; ++c)
   {
-    const double ta = dbg ? now() : 0.0;
-    const unsigned long long* word = e->h_seam_flags.p + c;
-    if (!synced && !seam_wait_word(word, gen))
+    const double ta = seam_clock();
+    if (!synced && !seam_wait_word(e->h_seam_flags.p + c, gen))
     {
-      HIPCHK(e, hipStreamSynchronize(e->stream));  // the slow way; everything is there afterwards
+      HIPCHK_OR(e, hipStreamSynchronize(e->stream), bail);  // the slow way; everything is there afterwards
       synced = true;
     }
-    const double tb = dbg ? now() : 0.0;
-    {
-      const int lo = lo_of(c), hi = c + 1 == chunks ? n : lo_of(c + 1);
-      for (int i = lo; i < hi; ++i)
-        samples[4 * (size_t)i + 3] = hw[i];
-      total += *const_cast<const volatile double*>(e->h_seam_totals.p + c);  // chunk totals in chunk order
-    }
-    if (dbg)
-    {
-      t_wait += tb - ta;
-      t_scatter += now() - tb;
-    }
+    const double tb = seam_clock();
+    const Range r = chunk_range(c);
+    for (int i = r.lo; i < r.hi; ++i)
+      samples[4 * (size_t)i + 3] = hw[i];
+    total += *const_cast<const volatile double*>(e->h_seam_totals.p + c);  // chunk totals in chunk order
+    t_wait += tb - ta;
+    t_scatter += seam_clock() - tb;
   }
-  if (dbg)
+  if (seam_debug())
     fprintf(stderr, "seam: %d chunks, %s: stage + issue %.1f us, waiting %.1f us, write-back %.1f us\n", chunks,
             pinned ? "pinned" : "pageable", t1 - t0, t_wait, t_scatter);
   e->h_scalars.p->v[0] = total;

@@ -112,6 +112,11 @@ struct PlanarModel
   double beam_skip_distance = 0, beam_skip_threshold = 0, beam_skip_error_threshold = 0;
   double off_map_factor = 1.0, non_free_factor = 1.0, non_free_radius = 0.0;  // planar_scanner.cpp:42-44
   double pose[3] = { 0, 0, 0 };
+  // the prob model's beam skipping (a counting pass, the mask, then the kept beams) runs only on a converged set
+  bool beamskip_armed(bool converged) const
+  {
+    return model == BPF_MODEL_LIKELIHOOD_FIELD_PROB && do_beamskip && converged;
+  }
 };
 
 struct ScanSlot
@@ -134,6 +139,28 @@ struct FieldScan
   std::vector<int> slot_of;    // staged beam -> beam_ind
   size_t beams_off = 0, table_off = 0, bytes = 0;
   int table_len = 0;
+};
+
+// where a host-out scoring launch (the host-buffer seam, abi_planar.inl) leaves its results
+struct FieldHostOut
+{
+  double4* rec;      // non-null: HOST_RECORDS -- the caller's records in registered host memory, read and written in place
+  double* w_host;    // HOST_WEIGHTS: the weights go to this pinned array as well
+  double* total_host;
+  double* partials;  // >= blocks of the launch
+  unsigned long long* flag;  // the done word and the value k_seam_done publishes in it
+  unsigned long long value;
+};
+
+// what one launch_field call is asked for (host_scoring.inl); the defaults are the plain scoring of a resident set
+struct FieldRequest
+{
+  int* obs_count = nullptr;    // non-null: the counting pass of beam skipping (per-beam counts, no weights) ...
+  int skip_level = 0;          // ... of the end points in a LUT level below this one
+  bool want_partials = false;  // leave per-block weight partials for the normalise launch (wc.fused_partials)
+  const double4* aos = nullptr;  // non-null: the n particles are still 32-byte records there (device-visible memory);
+                                 // the prep launch unpacks them into `p` as it goes (k_field_prep_aos)
+  const FieldHostOut* host_out = nullptr;  // non-null: a host-out form of the scoring kernel
 };
 
 // What the last weight pass left behind for the passes that follow it.  Invariant: a field that is set describes the
