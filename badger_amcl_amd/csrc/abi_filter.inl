@@ -367,25 +367,27 @@ int bpf_pf_update_resample(bpf_engine* e)
   rc = build_cdf(e, a.w.p, e->sample_count);
   if (rc != BPF_OK)
     return rc;
-  e->kld_device_used = false;
-  rc = (e->resample_model == BPF_RESAMPLE_SYSTEMATIC) ? resample_systematic(e, w_diff)
-                                                      : resample_multinomial(e, w_diff);
+  ResampleOutcome out;
+  rc = (e->resample_model == BPF_RESAMPLE_SYSTEMATIC) ? resample_systematic(e, w_diff, &out)
+                                                      : resample_multinomial(e, w_diff, &out);
   if (rc != BPF_OK)
     return rc;
   if (w_diff > 0.0)  // "Reset averages, to avoid spiraling off into complete randomness" (particle_filter.cpp:453-455)
     HIPCHK(e, hipMemsetAsync(&e->d_scalars.p->v[1], 0, 2 * sizeof(double), e->stream));
-  const int M = e->sample_count;
+  // the one place the outcome is committed: the new set with its tree counts, and what bpf_pf_get_state reports
+  const int M = out.M;
+  const bool by_block = out.counted_by == COUNTED_BY_BLOCK;
   SampleSet& b = e->sets[e->cur ^ 1];
-  const int bins = e->kld_device_used ? e->kld_bins : (kld_bins(e) ? e->kld_host_bins : e->hist.bin_count());
-  const int leaf = kld_bins(e) ? bins : (e->kld_device_used ? e->kld_leaf : e->hist.leaf_count());
   // k_resample_block already wrote the weights and counted the converged particles, the single-block tail below
   // does; a larger set gets launch_converged
-  e->new_set(M, true, e->tree.counted(leaf, bins), (e->fused_used || M <= 8192) ? M : 0);
+  e->new_set(M, true, e->tree.counted(out.leaf, out.bins), (by_block || M <= 8192) ? M : 0);
   e->slice_first = -1;  // (an unsharded resample: the set is no slice of a sharded one)
   // the device tree leaves no host histogram behind, nor does the host replay in BINS mode
-  if (!e->kld_device_used && !kld_bins(e))
+  if (out.counted_by == COUNTED_BY_HOST_TREE && !kld_bins(e))
     e->hist_built();
-  if (!e->fused_used && M <= 8192)
+  e->resample_windows = out.windows;
+  e->resample_counted_by = out.counted_by;
+  if (!by_block && M <= 8192)
   {
     // small resampled set: weights 1/M and updateConverged in one single-block launch
     ProfScope ps(e, BPF_K_FINALIZE);
@@ -393,7 +395,7 @@ int bpf_pf_update_resample(bpf_engine* e)
                        e->dist_threshold, e->d_scalars.p, e->d_flags.p + 1);
     HIPCHK(e, hipGetLastError());
   }
-  else if (!e->fused_used)
+  else if (!by_block)
   {
     {
       ProfScope ps(e, BPF_K_FINALIZE);
@@ -437,7 +439,7 @@ int bpf_pf_get_state(bpf_engine* e, bpf_pf_state* out)
   out->w_diff = e->w_diff_last;
   out->last_status = e->last_status;
   out->resample_windows = e->resample_windows;
-  out->kld_on_device = e->fused_used ? 2 : (e->kld_device_used ? 1 : 0);
+  out->kld_on_device = e->resample_counted_by;
   out->reserved = 0;
   out->evals = e->evals_last;
   return BPF_OK;

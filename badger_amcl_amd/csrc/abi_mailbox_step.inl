@@ -274,6 +274,234 @@ int shard_update_resample_in_place_mn(bpf_engine* e, void* flags_dev, uint64_t r
 int shard_rebalance_auto(bpf_engine* e);
 }  // namespace
 
+namespace
+{
+// ---- the window forms of the sharded resample: what one call's forms share ...
+struct ShardResample
+{
+  bpf_engine* e;
+  ShardExchange& X;
+  void* flags_dev;
+  uint64_t rng;  // the stream state the resample began from
+  int rank, W, max_global;
+};
+
+// ... and an exchanged window of candidate poses: rows x, y, theta (as doubles), then the three key rows
+struct ShardWindow
+{
+  long long* p = nullptr;
+  int stride = 0;
+  const double* row(int k) const { return reinterpret_cast<const double*>(p + (size_t)k * stride); }
+};
+
+// this rank's share of the new set of out.M samples out of the rows of all of them, weights 1/M, updateConverged
+int shard_adopt_from(const ShardResample& S, const ResampleOutcome& out, const double* x, const double* y,
+                     const double* th)
+{
+  bpf_engine* e = S.e;
+  const int M = out.M;
+  const int lo = (int)(((long long)M * S.rank) / S.W), hi = (int)(((long long)M * (S.rank + 1)) / S.W);
+  if (M <= 8192)
+    return bpf_shard_tail_small_dev(e, x, y, th, M, lo, hi, out.leaf, out.bins);
+  int rc = bpf_shard_adopt_dev(e, x + lo, y + lo, th + lo, hi - lo, M, out.leaf, out.bins);
+  if (rc != BPF_OK)
+    return rc;
+  return bpf_shard_converged_dev(e, x, y, M);
+}
+
+// The systematic window form: one window with every sample.  Tracking regime: the new set's tree (no stop rule), the
+// adoption and updateConverged in one launch; otherwise, or when that declines, the host's tree and the tail.
+int shard_systematic_window(const ShardResample& S, int sys_count, ResampleOutcome* out)
+{
+  bpf_engine* e = S.e;
+  ShardWindow win;
+  win.p = S.X.next_window(sys_count, &win.stride);
+  if (!win.p)
+    return e->last_status;
+  const bool tracking = e->fused_resample && sys_count <= kFusedWindow;
+  const bool merged = tracking && !S.X.collective();  // mailbox: the draws and their consumer in ONE launch
+  WindowArgs draw{};
+  int rc;
+  if (merged)
+  {
+    size_t lds_unused = 0;
+    rc = systematic_window_args(e, S.rng, sys_count, e->mb_totals, 1, S.rank, S.W, win.p, win.stride, S.flags_dev, &draw,
+                                &lds_unused);
+  }
+  else
+    rc = bpf_shard_systematic_window_dev(e, S.rng, sys_count, e->mb_totals, 1, S.rank, S.W, win.p, win.stride,
+                                         S.flags_dev);
+  if (rc != BPF_OK)
+    return rc;
+  H2D_OR_RETURN(S.X.assemble(win.p, win.stride));
+  out->windows = 1;
+  int fused_status = BPF_FUSED_TOO_MANY_BINS;
+  if (tracking)
+  {
+    rc = shard_stop_block(e, win.p, win.stride, sys_count, true, &fused_status, out, merged ? &draw : nullptr);
+    if (rc == BPF_OK && merged)
+      rc = systematic_targets_in_use(e);
+    if (rc != BPF_OK)
+      return rc;
+  }
+  if (fused_status == BPF_FUSED_OK)
+    return BPF_OK;
+  bpf_kld_reset(e);
+  H2D_OR_RETURN(bpf_kld_insert_dev(e, win.p, win.stride, sys_count));  // the host's tree
+  counted_by_host_tree(e, out);
+  out->M = sys_count;
+  return shard_adopt_from(S, *out, win.row(0), win.row(1), win.row(2));
+}
+
+// ---- the multinomial window form, by the schedule of resample_plan.hpp
+// what its windows leave behind for the adoption at the end
+struct ShardReplay
+{
+  int stop = -1;
+  ShardWindow last;      // the latest window: the set is adopted from it when nothing had to be kept
+  int host_windows = 0;  // windows the host replayed
+  bool kept = false;     // poses were copied to e->d_shard_out
+};
+
+// The sharded driver's tracking predicate: the first window (AFTER the schedule's cap at 4096) and the hint both fit
+// one block.  (The single engine's differs: multinomial_tracking in host_resample.inl.)
+bool shard_tracking(const bpf_engine* e, int m0, int count, int hint)
+{
+  return m0 == 0 && e->fused_resample && count <= kFusedWindow && hint <= kFusedWindow;
+}
+
+// a fresh window with the draws [m0, m1) of every shard; `merged_draw`: the arguments only, for a consumer that makes
+// the draws in its own launch
+int shard_draw_window(const ShardResample& S, int m0, int m1, ShardWindow* win, WindowArgs* merged_draw)
+{
+  bpf_engine* e = S.e;
+  win->p = S.X.next_window(m1 - m0, &win->stride);
+  if (!win->p)
+    return e->last_status;
+  int rc;
+  if (merged_draw)
+  {
+    size_t lds_unused = 0;
+    rc = draw_window_args(e, S.rng, m0, m1, e->mb_totals, 1, S.rank, S.W, win->p, win->stride, S.flags_dev, merged_draw,
+                          &lds_unused);
+  }
+  else
+    rc = bpf_shard_draw_window_dev(e, S.rng, m0, m1, e->mb_totals, 1, S.rank, S.W, win->p, win->stride, S.flags_dev);
+  if (rc != BPF_OK)
+    return rc;
+  return S.X.assemble(win->p, win->stride);
+}
+
+// No stop so far and a long stream ahead (a spread cloud): one window with every candidate, and the ordered kd-tree
+// replay runs on the device (every rank, redundantly).  *handled = false: this stream is outside what the device tree
+// takes, host replay.
+int shard_whole_stream_window(const ShardResample& S, ShardReplay* R, ResampleOutcome* out, bool* handled)
+{
+  ShardWindow whole;
+  H2D_OR_RETURN(shard_draw_window(S, 0, S.max_global, &whole, nullptr));
+  int ok = 0, stop = -1, leaf = 0, bins = 0;
+  H2D_OR_RETURN(bpf_kld_stop_dev(S.e, whole.p, whole.stride, S.max_global, &ok, &stop, &leaf, &bins));
+  ++out->windows;
+  *handled = ok != 0;
+  if (!*handled)
+    return BPF_OK;
+  R->stop = stop;
+  out->counted(COUNTED_BY_DEVICE_TREE, leaf, bins);
+  R->last = whole;
+  R->kept = false;
+  return BPF_OK;
+}
+
+// The tracking regime: the stream is expected to stop inside this first window, and the stop rule, the adoption of
+// this rank's share and updateConverged run in one single-block launch on every rank.  *adopted = false: no stop in
+// the window, or keys / bins beyond what the kernel takes -- the host replays this same window.
+int shard_tracking_window(const ShardResample& S, int m0, int m1, ShardWindow* win, ResampleOutcome* out, bool* adopted)
+{
+  const bool merged = !S.X.collective();  // mailbox: the draws and their consumer in ONE launch
+  WindowArgs draw{};
+  H2D_OR_RETURN(shard_draw_window(S, m0, m1, win, merged ? &draw : nullptr));
+  int fused_status = BPF_FUSED_TOO_MANY_BINS;
+  H2D_OR_RETURN(shard_stop_block(S.e, win->p, win->stride, m1 - m0, false, &fused_status, out, merged ? &draw : nullptr));
+  *adopted = fused_status == BPF_FUSED_OK;
+  if (*adopted)
+    ++out->windows;
+  return BPF_OK;
+}
+
+// A mailbox window is overwritten two exchanges later, and a set that spans windows is adopted from one buffer: keep
+// this window's poses
+int shard_keep_window(const ShardResample& S, const ShardWindow& win, int m0, int count, ShardReplay* R)
+{
+  bpf_engine* e = S.e;
+  HIPCHK(e, e->d_shard_out.reserve((size_t)3 * S.max_global));
+  for (int k = 0; k < 3; ++k)
+    HIPCHK(e, hipMemcpyAsync(e->d_shard_out.p + (size_t)k * S.max_global + m0, win.row(k), (size_t)count * sizeof(double),
+                             hipMemcpyDeviceToDevice, e->stream));
+  R->kept = true;
+  return BPF_OK;
+}
+
+// the host's ordered replay of the window's keys (the one host wait of the window)
+int shard_host_window(const ShardResample& S, const ShardWindow& win, int m0, int count, ShardReplay* R,
+                      ResampleOutcome* out)
+{
+  H2D_OR_RETURN(bpf_kld_feed_dev(S.e, win.p, win.stride, count, m0, &R->stop));
+  ++out->windows;
+  ++R->host_windows;
+  R->last = win;
+  if (R->stop < 0 || R->host_windows > 1)
+    return shard_keep_window(S, win, m0, count, R);
+  return BPF_OK;
+}
+
+int shard_multinomial_windows(const ShardResample& S, int* window_hint_io, ResampleOutcome* out)
+{
+  bpf_engine* e = S.e;
+  bpf_kld_reset(e);
+  // whole_stream_at_start = false: this driver replays a first window whatever the hint says
+  WindowSchedule s = window_schedule(*window_hint_io, S.max_global, e->kld_device_min, false);
+  ShardReplay R;
+  int limit = 0;  // the bound for the leaves the host has seen so far
+  bool adopted = false, on_device = false;
+  while (s.m0 < S.max_global && R.stop < 0)
+  {
+    if (s.whole_stream_due(limit))
+    {
+      H2D_OR_RETURN(shard_whole_stream_window(S, &R, out, &on_device));
+      if (on_device)
+        break;
+      s.device_declined = true;
+    }
+    const int m1 = s.m1(), count = m1 - s.m0;
+    ShardWindow win;
+    if (shard_tracking(e, s.m0, count, *window_hint_io))
+    {
+      H2D_OR_RETURN(shard_tracking_window(S, s.m0, m1, &win, out, &adopted));
+      if (adopted)
+        break;
+    }
+    else
+      H2D_OR_RETURN(shard_draw_window(S, s.m0, m1, &win, nullptr));
+    H2D_OR_RETURN(shard_host_window(S, win, s.m0, count, &R, out));
+    limit = resample_limit(kld_host_k(e), e->min_samples, e->max_samples, e->pop_err, e->pop_z);
+    s.next(limit);
+  }
+  if (!adopted)
+  {
+    out->M = R.stop > 0 ? R.stop : S.max_global;
+    if (!on_device)
+      counted_by_host_tree(e, out);
+    const size_t mg = (size_t)S.max_global;
+    H2D_OR_RETURN(R.kept ? shard_adopt_from(S, *out, e->d_shard_out.p, e->d_shard_out.p + mg, e->d_shard_out.p + 2 * mg)
+                         : shard_adopt_from(S, *out, R.last.row(0), R.last.row(1), R.last.row(2)));
+  }
+  *window_hint_io = resample_window_for(out->M);
+  return BPF_OK;
+}
+}  // namespace
+
+// The sharded resample in one call: validation, CDF, begin, the form (in place, or one of the window forms above),
+// end, commit, rebalance
 int bpf_shard_mailbox_update_resample(bpf_engine* e, void* flags_dev, int* global_count_io, int* leaf_count_io,
                                       int* bin_count_out, int* windows_out, int* window_hint_io)
 {
@@ -290,240 +518,60 @@ int bpf_shard_mailbox_update_resample(bpf_engine* e, void* flags_dev, int* globa
                    "sharded resample: needs the totals of bpf_shard_mailbox_update_sensor_planar of this update");
   HIPCHK(e, hipSetDevice(e->device));
   ShardExchange X{ e };
-  const int rank = e->shard_rank, W = e->shard_world;
-  const int max_global = e->max_samples;  // engines of a sharded filter carry the GLOBAL bounds
   rc = bpf_shard_build_cdf(e, flags_dev);
   if (rc != BPF_OK)
     return rc;
-  const uint64_t rng = e->rng;
+  // engines of a sharded filter carry the GLOBAL bounds
+  const ShardResample S{ e, X, flags_dev, e->rng, e->shard_rank, e->shard_world, e->max_samples };
   double w_diff = 0.0;
   int sys_count = 0;
-  rc = bpf_shard_begin_resample(e, rng, *leaf_count_io, &w_diff, &sys_count);
+  rc = bpf_shard_begin_resample(e, S.rng, *leaf_count_io, &w_diff, &sys_count);
   if (rc != BPF_OK)
     return rc;
-  int stride = 0;
-  int M = 0, leaf = 0, bins = 0;
+  ResampleOutcome out;
   *windows_out = 0;
-  auto rows = [&](long long* window, int k) { return reinterpret_cast<const double*>(window + (size_t)k * stride); };
-  auto adopt_from = [&](const double* x, const double* y, const double* th) -> int {
-    const int lo = (int)(((long long)M * rank) / W), hi = (int)(((long long)M * (rank + 1)) / W);
-    if (M <= 8192)
-      return bpf_shard_tail_small_dev(e, x, y, th, M, lo, hi, leaf, bins);
-    int r2 = bpf_shard_adopt_dev(e, x + lo, y + lo, th + lo, hi - lo, M, leaf, bins);
-    if (r2 != BPF_OK)
-      return r2;
-    return bpf_shard_converged_dev(e, x, y, M);
-  };
   bool in_place = false;
   if (e->resample_model == BPF_RESAMPLE_SYSTEMATIC && e->shard_form == BPF_SHARD_RESAMPLE_IN_PLACE)
   {
     // every rank resamples its own slice into its own slice; the imbalance cap hands this resample to the window below
-    rc = shard_update_resample_in_place(e, flags_dev, rng, sys_count, &in_place, &leaf, &bins);
-    if (rc != BPF_OK)
-      return rc;
-    M = sys_count;
+    rc = shard_update_resample_in_place(e, flags_dev, S.rng, sys_count, &in_place, &out.leaf, &out.bins);
+    out.M = sys_count;
   }
   else if (e->resample_model == BPF_RESAMPLE_MULTINOMIAL && e->shard_mn_form == BPF_SHARD_RESAMPLE_IN_PLACE)
-  {
     // every rank keeps the candidate draws of its own slice and finds the stop from the merged bin lists; the imbalance
     // cap, or a key outside the packing, hands this resample to the windows below
-    rc = shard_update_resample_in_place_mn(e, flags_dev, rng, &in_place, &M, &leaf, &bins);
-    if (rc != BPF_OK)
-      return rc;
-  }
+    rc = shard_update_resample_in_place_mn(e, flags_dev, S.rng, &in_place, &out.M, &out.leaf, &out.bins);
+  if (rc != BPF_OK)
+    return rc;
   if (in_place)
   {
     // nothing left to do: the slice is current, with the global set's tree counts and updateConverged's count
   }
-  else if (!X.collective() && max_global > e->mb.max_window)  // (the in-place form needs no window of that size)
+  else if (!X.collective() && S.max_global > e->mb.max_window)  // (the in-place form needs no window of that size)
     return e->fail(BPF_ERR_CAPACITY, "mailbox windows are smaller than max_samples");
-  else if (e->resample_model == BPF_RESAMPLE_SYSTEMATIC)
-  {
-    long long* window = X.next_window(sys_count, &stride);
-    if (!window)
-      return e->last_status;
-    const bool tracking = e->fused_resample && sys_count <= kFusedWindow;
-    const bool merged = tracking && !X.collective();  // mailbox: the draws and their consumer in ONE launch
-    WindowArgs draw{};
-    if (merged)
-    {
-      size_t lds_unused = 0;
-      rc = systematic_window_args(e, rng, sys_count, e->mb_totals, 1, rank, W, window, stride, flags_dev, &draw,
-                                  &lds_unused);
-    }
-    else
-      rc = bpf_shard_systematic_window_dev(e, rng, sys_count, e->mb_totals, 1, rank, W, window, stride, flags_dev);
-    if (rc != BPF_OK)
-      return rc;
-    rc = X.assemble(window, stride);
-    if (rc != BPF_OK)
-      return rc;
-    *windows_out = 1;
-    int fused_status = BPF_FUSED_TOO_MANY_BINS;
-    if (tracking)
-    {
-      // tree of the new set (every sample, no stop rule), adoption and updateConverged in one launch
-      rc = shard_stop_block(e, window, stride, sys_count, true, &fused_status, &M, &leaf, &bins,
-                            merged ? &draw : nullptr);
-      if (rc == BPF_OK && merged)
-        rc = systematic_targets_in_use(e);
-      if (rc != BPF_OK)
-        return rc;
-    }
-    if (fused_status != BPF_FUSED_OK)
-    {
-      bpf_kld_reset(e);
-      rc = bpf_kld_insert_dev(e, window, stride, sys_count);  // the host's tree
-      if (rc != BPF_OK)
-        return rc;
-      bpf_kld_leaf_count(e, &leaf, &bins);
-      M = sys_count;
-      rc = adopt_from(rows(window, 0), rows(window, 1), rows(window, 2));
-      if (rc != BPF_OK)
-        return rc;
-    }
-  }
   else
-  {
-    bpf_kld_reset(e);
-    int m0 = 0, stop = -1, need = 0;
-    int win = std::max(1024, std::min(*window_hint_io, max_global));
-    const int device_min = e->kld_device_min;
-    bool device_declined = false;
-    if (win > 4096 && max_global - 4096 >= device_min)
-      win = 4096;  // keep the host's first window short when the device tree can take over after it
-    long long* last_window = nullptr;
-    int n_windows = 0;
-    bool copied_any = false;
-    bool have_counts = false;
-    bool adopted = false;  // k_shard_stop_block has done the stop rule and the tail
-    while (m0 < max_global && stop < 0)
-    {
-      if (m0 > 0 && !device_declined && max_global - m0 >= device_min && need >= device_min)
-      {
-        // no stop so far and a long stream ahead (a spread cloud): one window with every candidate, and the ordered
-        // kd-tree replay runs on the device (every rank, redundantly)
-        long long* whole = X.next_window(max_global, &stride);
-        if (!whole)
-          return e->last_status;
-        rc = bpf_shard_draw_window_dev(e, rng, 0, max_global, e->mb_totals, 1, rank, W, whole, stride, flags_dev);
-        if (rc != BPF_OK)
-          return rc;
-        rc = X.assemble(whole, stride);
-        if (rc != BPF_OK)
-          return rc;
-        int handled = 0, dstop = -1, dleaf = 0, dbins = 0;
-        rc = bpf_kld_stop_dev(e, whole, stride, max_global, &handled, &dstop, &dleaf, &dbins);
-        if (rc != BPF_OK)
-          return rc;
-        ++*windows_out;
-        if (handled)
-        {
-          stop = dstop;
-          leaf = dleaf;
-          bins = dbins;
-          have_counts = true;
-          last_window = whole;
-          n_windows = 1;
-          copied_any = false;
-          m0 = 0;
-          break;
-        }
-        device_declined = true;  // this stream is outside what the device tree takes: host replay
-      }
-      const int m1 = std::min(max_global, m0 + win), cnt = m1 - m0;
-      long long* window = X.next_window(cnt, &stride);
-      if (!window)
-        return e->last_status;
-      const bool tracking = m0 == 0 && e->fused_resample && cnt <= kFusedWindow && *window_hint_io <= kFusedWindow;
-      WindowArgs draw{};
-      const bool merged = tracking && !X.collective();  // mailbox: the draws and their consumer in ONE launch
-      if (merged)
-      {
-        size_t lds_unused = 0;
-        rc = draw_window_args(e, rng, m0, m1, e->mb_totals, 1, rank, W, window, stride, flags_dev, &draw, &lds_unused);
-      }
-      else
-        rc = bpf_shard_draw_window_dev(e, rng, m0, m1, e->mb_totals, 1, rank, W, window, stride, flags_dev);
-      if (rc != BPF_OK)
-        return rc;
-      rc = X.assemble(window, stride);
-      if (rc != BPF_OK)
-        return rc;
-      if (tracking)
-      {
-        // the tracking regime: the stream is expected to stop inside this first window, and the stop rule, the
-        // adoption of this rank's share and updateConverged run in one single-block launch on every rank
-        int fused_status = BPF_FUSED_TOO_MANY_BINS;
-        rc = shard_stop_block(e, window, stride, cnt, false, &fused_status, &M, &leaf, &bins, merged ? &draw : nullptr);
-        if (rc != BPF_OK)
-          return rc;
-        if (fused_status == BPF_FUSED_OK)
-        {
-          ++*windows_out;
-          adopted = true;
-          break;
-        }
-        // no stop in the window, or keys / bins beyond what the kernel takes: the host replays this same window
-      }
-      rc = bpf_kld_feed_dev(e, window, stride, cnt, m0, &stop);  // the one host wait of the window
-      if (rc != BPF_OK)
-        return rc;
-      ++*windows_out;
-      ++n_windows;
-      last_window = window;
-      if (stop < 0 || n_windows > 1)
-      {
-        // a mailbox window is overwritten two exchanges later, and a set that spans windows is adopted from one
-        // buffer: keep this window's poses
-        HIPCHK(e, e->d_shard_out.reserve((size_t)3 * max_global));
-        for (int k = 0; k < 3; ++k)
-          HIPCHK(e, hipMemcpyAsync(e->d_shard_out.p + (size_t)k * max_global + m0, rows(window, k),
-                                   (size_t)cnt * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-        copied_any = true;
-      }
-      m0 = m1;
-      if (stop < 0)
-      {
-        // next window: up to a quarter past the bound for the leaves seen so far (a lower estimate of the stop)
-        int lc = 0, bc = 0;
-        bpf_kld_leaf_count(e, &lc, &bc);
-        int lim = 0;
-        bpf_pf_resample_limit(e, lc, &lim);
-        need = lim - m0;
-        win = resample_window_for(need);
-      }
-    }
-    if (!adopted)
-    {
-      M = stop > 0 ? stop : max_global;
-      if (!have_counts)
-        bpf_kld_leaf_count(e, &leaf, &bins);
-      if (copied_any)
-        rc = adopt_from(e->d_shard_out.p, e->d_shard_out.p + max_global, e->d_shard_out.p + 2 * (size_t)max_global);
-      else
-        rc = adopt_from(rows(last_window, 0), rows(last_window, 1), rows(last_window, 2));
-      if (rc != BPF_OK)
-        return rc;
-    }
-    *window_hint_io = resample_window_for(M);
-  }
-  uint64_t rng_after = 0;
-  rc = bpf_shard_end_resample(e, M, &rng_after);
+    rc = e->resample_model == BPF_RESAMPLE_SYSTEMATIC ? shard_systematic_window(S, sys_count, &out)
+                                                      : shard_multinomial_windows(S, window_hint_io, &out);
   if (rc != BPF_OK)
     return rc;
+  uint64_t rng_after = 0;
+  rc = bpf_shard_end_resample(e, out.M, &rng_after);
+  if (rc != BPF_OK)
+    return rc;
+  // commit: the stream, the split, and the caller's record of the new set
   e->rng = rng_after;
   e->mb_totals_valid = false;  // the weights are 1/M now
   if (!in_place)
   {
     // the window forms leave the even split
-    e->slice_first = ((long long)M * rank) / W;
-    e->slice_global = M;
+    e->slice_first = ((long long)out.M * S.rank) / S.W;
+    e->slice_global = out.M;
     e->shard_form_used = BPF_SHARD_RESAMPLE_WINDOW;
   }
-  *global_count_io = M;
-  *leaf_count_io = leaf;
-  *bin_count_out = bins;
+  *global_count_io = out.M;
+  *leaf_count_io = out.leaf;
+  *bin_count_out = out.bins;
+  *windows_out = out.windows;
   e->resample_committed = true;
   // the resample is complete and committed: a rebalance that fails from here on leaves the uneven set current and valid
   if (in_place && e->shard_rebalance == BPF_SHARD_REBALANCE_AUTO)

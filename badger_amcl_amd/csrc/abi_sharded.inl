@@ -292,15 +292,11 @@ MailboxDev shard_window_wait(bpf_engine* e, const void* window_dev, int consumer
 
 namespace
 {
-// the arguments of a multinomial draw window (k_draw_window, k_shard_resample_block); *lds_out = the dynamic LDS the
-// CDF subsample takes in k_draw_window (0: none)
-int draw_window_args(bpf_engine* e, uint64_t rng_state48, int m0, int m1, const void* sums_dev, int sums_are_totals,
-                     int rank, int world, void* window_dev, int stride, void* flags_dev, WindowArgs* out, size_t* lds_out)
+// what the arguments of every draw window start from: the source set and its CDF, the shard sums, the draws [m0, m1)
+// of the stream at rng_state48 and the exchanged window they go to
+void window_args_base(bpf_engine* e, uint64_t rng_state48, int m0, int m1, const void* sums_dev, int sums_are_totals,
+                      int rank, int world, void* window_dev, int stride, void* flags_dev, WindowArgs* out)
 {
-  if (!e || !e->have_pf || !sums_dev || !window_dev || !flags_dev || m1 <= m0 || stride < m1 - m0 || rank < 0 ||
-      rank >= world)
-    return e ? e->fail(BPF_ERR_INVALID_ARGUMENT, "bad draw window arguments") : BPF_ERR_INVALID_ARGUMENT;
-  HIPCHK(e, hipSetDevice(e->device));
   WindowArgs& A = *out;
   A = WindowArgs{};
   A.src = e->sets[e->cur].dev();
@@ -317,6 +313,30 @@ int draw_window_args(bpf_engine* e, uint64_t rng_state48, int m0, int m1, const 
   A.window = static_cast<long long*>(window_dev);
   A.stride = stride;
   A.flags = static_cast<int*>(flags_dev);
+}
+
+// A short window after k_normalize_gathered_cdf: the draws bracket themselves in the CDF subsample first.  Returns
+// the dynamic LDS the subsample takes in k_draw_window (0: none).
+size_t window_coarse_cdf(bpf_engine* e, WindowArgs* A)
+{
+  if (e->wc.cdf_coarse_n != A->n_src || A->n_src <= 0 || A->m1 - A->m0 > 2 * kFusedWindow)
+    return 0;
+  A->coarse = e->d_cdf_coarse.p;
+  A->coarse_shift = fused_coarse_shift(A->n_src);
+  return ((size_t)((A->n_src - 1) >> A->coarse_shift) + 2) * sizeof(double);
+}
+
+// the arguments of a multinomial draw window (k_draw_window, k_shard_resample_block); *lds_out = the dynamic LDS the
+// CDF subsample takes in k_draw_window (0: none)
+int draw_window_args(bpf_engine* e, uint64_t rng_state48, int m0, int m1, const void* sums_dev, int sums_are_totals,
+                     int rank, int world, void* window_dev, int stride, void* flags_dev, WindowArgs* out, size_t* lds_out)
+{
+  if (!e || !e->have_pf || !sums_dev || !window_dev || !flags_dev || m1 <= m0 || stride < m1 - m0 || rank < 0 ||
+      rank >= world)
+    return e ? e->fail(BPF_ERR_INVALID_ARGUMENT, "bad draw window arguments") : BPF_ERR_INVALID_ARGUMENT;
+  HIPCHK(e, hipSetDevice(e->device));
+  WindowArgs& A = *out;
+  window_args_base(e, rng_state48, m0, m1, sums_dev, sums_are_totals, rank, world, window_dev, stride, flags_dev, &A);
   int rcm = shard_window_exchange(e, window_dev, m1 - m0, world, &A);
   if (rcm != BPF_OK)
     return rcm;
@@ -339,15 +359,7 @@ int draw_window_args(bpf_engine* e, uint64_t rng_state48, int m0, int m1, const 
     A.jump_table = e->d_fused_jump.p;
     A.jump_table_n = kFusedWindow;
   }
-  size_t lds = 0;
-  if (e->wc.cdf_coarse_n == A.n_src && A.n_src > 0 && m1 - m0 <= 2 * kFusedWindow)
-  {
-    // a short window after k_normalize_gathered_cdf: the draws bracket themselves in the CDF subsample first
-    A.coarse = e->d_cdf_coarse.p;
-    A.coarse_shift = fused_coarse_shift(A.n_src);
-    lds = ((size_t)((A.n_src - 1) >> A.coarse_shift) + 2) * sizeof(double);
-  }
-  *lds_out = lds;
+  *lds_out = window_coarse_cdf(e, &A);
   return BPF_OK;
 }
 }  // namespace
@@ -416,11 +428,11 @@ int bpf_shard_tail_small_dev(bpf_engine* e, const void* x_all_dev, const void* y
 namespace
 {
 // The sharded resample's stop rule, adoption and updateConverged in one single-block launch from an exchanged window
-// (k_shard_stop_block): *status is BPF_FUSED_OK when it was handled (the engine then holds its share of the new set),
-// another BPF_FUSED_* when the window is outside what the kernel takes -- nothing was changed and the window stays
-// readable for the stage-by-stage path.
+// (k_shard_stop_block): *status is BPF_FUSED_OK when it was handled (the engine then holds its share of the new set,
+// *out its size and tree counts), another BPF_FUSED_* when the window is outside what the kernel takes -- nothing was
+// changed and the window stays readable for the stage-by-stage path.
 int shard_stop_block(bpf_engine* e, const long long* window, int stride, int count, bool systematic, int* status,
-                     int* M_out, int* leaf_out, int* bins_out, const WindowArgs* draw = nullptr)
+                     ResampleOutcome* out, const WindowArgs* draw = nullptr)
 {
   *status = BPF_FUSED_TOO_MANY_BINS;
   if (count <= 0 || count > kFusedWindow || stride < count)
@@ -477,9 +489,8 @@ int shard_stop_block(bpf_engine* e, const long long* window, int stride, int cou
   const int lo = (int)(((long long)M * A.rank) / W), hi = (int)(((long long)M * (A.rank + 1)) / W);
   if (hi - lo > e->max_samples)
     return e->fail(BPF_ERR_CAPACITY, "adopted shard larger than max_samples");
-  *M_out = M;
-  *leaf_out = r5[1];
-  *bins_out = r5[2];
+  out->M = M;
+  out->counted(COUNTED_BY_BLOCK, r5[1], r5[2]);
   e->new_set(hi - lo, true, e->tree.counted(r5[1], r5[2]), M);
   return BPF_OK;
 }
@@ -611,23 +622,14 @@ int bpf_shard_begin_resample(bpf_engine* e, uint64_t rng_state48, int leaf_count
   {
     if (e->resample_model == BPF_RESAMPLE_SYSTEMATIC)
     {
-      count *= (1.0 + w_diff);  // :295-306
-      if (count > e->max_samples)
-        count = e->max_samples;
-      e->shard_n_random = (int)(w_diff * count);
-      if (e->shard_n_random > 0)
-      {
-        FreeSpaceDev fs{};
-        int rc = ensure_free_space(e, &fs);
-        if (rc == BPF_OK && 1ll + (2ll * fs.retries + 2) * e->shard_n_random >= 0x7fffffffll)
-          rc = e->fail(BPF_ERR_CAPACITY, "random pose calls would pass 31-bit stream positions");
-        if (rc != BPF_OK)
-        {
-          e->shard_n_random = 0;
-          return rc;
-        }
-        e->shard_retries = fs.retries;
-      }
+      SystematicBudget budget;
+      FreeSpaceDev fs{};
+      int rc = systematic_budget_for(e, leaf_count, w_diff, &budget, &fs);  // :295-306
+      if (rc != BPF_OK)
+        return rc;  // (shard_n_random stays 0)
+      count = budget.count;
+      e->shard_n_random = budget.n_random;
+      e->shard_retries = fs.retries;
     }
     else
     {
@@ -656,22 +658,15 @@ int bpf_shard_end_resample(bpf_engine* e, int sample_count, uint64_t* rng_state4
   if (!e->have_pf)
     return e->fail(BPF_ERR_NOT_CONFIGURED, "bpf_pf_create first");
   HIPCHK(e, hipSetDevice(e->device));
-  uint64_t consumed;
-  if (e->resample_model == BPF_RESAMPLE_SYSTEMATIC)
-    consumed = 1ull + (2ull * (uint64_t)e->shard_retries + 2ull) * (uint64_t)e->shard_n_random;
-  else if (e->shard_chain)
-  {
-    if (sample_count > e->max_samples)
-      return e->fail(BPF_ERR_INVALID_ARGUMENT, "sample_count beyond the chain");
-    HIPCHK(e, e->h_chain_word.reserve(1));
-    HIPCHK(e, hipMemcpyAsync(e->h_chain_word.p, e->d_chain.p + (sample_count - 1), sizeof(int),
-                             hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    consumed = chain_consumed(e->h_chain_word.p[0]);
-  }
-  else
-    consumed = 2ull * (uint64_t)sample_count;
-  *rng_state48_out = lcg_skip_host(e->shard_rng0, consumed, e->jump);
+  StreamUse use;
+  use.regime = e->resample_model == BPF_RESAMPLE_SYSTEMATIC ? STREAM_SYSTEMATIC
+               : e->shard_chain                             ? STREAM_MULTINOMIAL_CHAIN
+                                                            : STREAM_MULTINOMIAL;
+  use.retries = e->shard_retries;
+  use.n_random = e->shard_n_random;
+  if (use.regime == STREAM_MULTINOMIAL_CHAIN && sample_count > e->max_samples)
+    return e->fail(BPF_ERR_INVALID_ARGUMENT, "sample_count beyond the chain");
+  H2D_OR_RETURN(stream_after_resample(e, e->shard_rng0, use, sample_count, rng_state48_out));
   if (e->shard_w_diff > 0.0)  // particle_filter.cpp:453-455
     HIPCHK(e, hipMemsetAsync(&e->d_scalars.p->v[1], 0, 2 * sizeof(double), e->stream));
   e->shard_chain = false;
@@ -701,37 +696,13 @@ int systematic_window_args(bpf_engine* e, uint64_t rng_state48, int count, const
       rank >= world)
     return e ? e->fail(BPF_ERR_INVALID_ARGUMENT, "bad systematic window arguments") : BPF_ERR_INVALID_ARGUMENT;
   HIPCHK(e, hipSetDevice(e->device));
-  HIPCHK(e, e->h_targets.reserve((size_t)std::max(count, e->max_samples)));
-  // the reference's serial chain (particle_filter.cpp:337-341): target += delta, -= 1 once it passes 1
-  const uint64_t st = lcg_skip_host(rng_state48 & ((1ull << 48) - 1), 1, e->jump);
-  double t = std::ldexp((double)st, -48);
+  const uint64_t state0 = rng_state48 & ((1ull << 48) - 1);
   const int n_random = e->shard_n_random;
   if (n_random < 0 || n_random >= count)
     return e->fail(BPF_ERR_INVALID_ARGUMENT, "systematic window: random pose count out of range");
-  const int n_systematic = count - n_random;
-  const double delta = 1.0 / n_systematic;
-  if (e->targets_read)  // a previous window kernel may still be reading the pinned targets
-    HIPCHK(e, hipEventSynchronize(e->targets_read));
-  for (int i = 0; i < n_systematic; ++i)
-  {
-    e->h_targets.p[i] = t;
-    t += delta;
-    if (t > 1.0)
-      t -= 1.0;
-  }
+  H2D_OR_RETURN(systematic_targets(e, lcg_skip_host(state0, 1, e->jump), count, count - n_random));
   WindowArgs& A = *out;
-  A = WindowArgs{};
-  A.src = e->sets[e->cur].dev();
-  A.n_src = e->sample_count;
-  A.cdf = e->d_cdf.p;
-  A.sums = static_cast<const double*>(sums_dev);
-  A.sums_are_totals = sums_are_totals;
-  A.rank = rank;
-  A.world = world;
-  A.m0 = 0;
-  A.m1 = count;
-  A.rng_state = rng_state48 & ((1ull << 48) - 1);
-  A.jump = e->jump;
+  window_args_base(e, state0, 0, count, sums_dev, sums_are_totals, rank, world, window_dev, stride, flags_dev, &A);
   A.n_random = n_random;
   A.write_random = rank == 0;
   if (n_random > 0)
@@ -740,21 +711,11 @@ int systematic_window_args(bpf_engine* e, uint64_t rng_state48, int count, const
     if (rcf != BPF_OK)
       return rcf;
   }
-  A.window = static_cast<long long*>(window_dev);
-  A.stride = stride;
-  A.flags = static_cast<int*>(flags_dev);
   A.targets = e->h_targets.p;
   int rcm = shard_window_exchange(e, window_dev, count, world, &A);
   if (rcm != BPF_OK)
     return rcm;
-  size_t lds = 0;
-  if (e->wc.cdf_coarse_n == A.n_src && A.n_src > 0 && count <= 2 * kFusedWindow)
-  {
-    A.coarse = e->d_cdf_coarse.p;
-    A.coarse_shift = fused_coarse_shift(A.n_src);
-    lds = ((size_t)((A.n_src - 1) >> A.coarse_shift) + 2) * sizeof(double);
-  }
-  *lds_out = lds;
+  *lds_out = window_coarse_cdf(e, &A);
   return BPF_OK;
 }
 

@@ -1,6 +1,8 @@
 // Engine state: device / pinned buffers, per-scan staging descriptors, the bpf_engine struct and the
 // HIPCHK error macro.  Part of the one translation unit engine.hip.
 #pragma once
+#include "resample_plan.hpp"  // the resample drivers' shared arithmetic (host code, namespace bpf)
+
 namespace
 {
 
@@ -321,7 +323,9 @@ struct bpf_engine
   int conv_n = 0;
   double w_diff_last = 0;
   int last_status = BPF_OK;
+  // the last single-engine resample, as bpf_pf_get_state reports it (written by bpf_pf_update_resample alone)
   int resample_windows = 0;
+  int resample_counted_by = 0;  // ResampleCountedBy: 0 host tree, 1 device tree, 2 one-block kernel
   int window_hint = 4096;
   long long evals_last = 0;
   bool cdf_serial = false;
@@ -341,7 +345,6 @@ struct bpf_engine
   DevBuf<unsigned> d_kld_bar;
   void* shard_cdf_flags = nullptr;     // the caller's miss flag that launch cleared (null: none)
   void* shard_flags_last = nullptr;    // flags_dev of the last bpf_shard_build_cdf
-  int fused_used = 0;         // the last resample ran as the one-block kernel
   int fused_generation = 0;
   PinnedBuf<int> h_fused;
   DevBuf<FusedJump> d_fused_jump;
@@ -476,8 +479,6 @@ struct bpf_engine
 
   // ---- KLD stop rule on the device (long draw streams)
   int kld_device_min = 8192;  // draws left after the first window from which the device tree takes over
-  bool kld_device_used = false;
-  int kld_leaf = 0, kld_bins = 0;
   int kld_count_mode = BPF_KLD_COUNT_LEAVES;  // bpf_pf_set_kld_count: what the stop rule's k counts
   int kld_host_bins = 0;  // BINS mode: distinct keys the host replay has seen (e->seen first occurrences)
   DevBuf<unsigned long long> d_kld_hkey;

@@ -244,13 +244,6 @@ int blocks_for(int n, int per_block)
   return (n + per_block - 1) / per_block;
 }
 
-// a resample window for a stop expected x draws ahead: a quarter more, in whole 1024s.  The window hint after a
-// resample that kept x samples, and the next window's size from the bound for the leaves seen so far.
-int resample_window_for(int x)
-{
-  return std::max(1024, (x + x / 4 + 1023) / 1024 * 1024);
-}
-
 // ------------------------------------------------------------------ map encoding
 int encode_lut(bpf_engine* e, const float* lut)
 {

@@ -429,12 +429,6 @@ int resolve_scored_chain(bpf_engine* e, const FreeSpaceDev& F, double w_diff, in
   return BPF_OK;
 }
 
-// stream elements the draws 0 .. m consumed, from chain[m]: up to r, or up to the second element of the accepted trial
-uint64_t chain_consumed(int chain_word)
-{
-  return (uint64_t)((unsigned)chain_word & 0x7fffffffu) + (chain_word < 0 ? 1ull : 0ull);
-}
-
 // Where every candidate draw 0 .. max_draws finds its stream elements when w_diff > 0 (kernels_recovery.hpp);
 // `retries` = FreeSpaceDev::retries
 int build_draw_chain(bpf_engine* e, double w_diff, int max_draws, int retries)
@@ -569,10 +563,39 @@ int fused_result_wait(bpf_engine* e, int generation, const char* kernel_name, in
   return BPF_OK;
 }
 
+// ---- what a resample made, whichever driver and regime ran.  The regimes fill it; bpf_pf_update_resample and
+// bpf_shard_mailbox_update_resample commit it, and nothing else writes the engine's record of the last resample.
+enum ResampleCountedBy  // (the values of bpf_pf_state::kld_on_device)
+{
+  COUNTED_BY_HOST_TREE = 0,    // the ordered replay into e->hist (or its distinct-key count in BINS mode)
+  COUNTED_BY_DEVICE_TREE = 1,  // kld_tree_on_device
+  COUNTED_BY_BLOCK = 2,        // a one-block kernel, which also wrote the weights and counted the converged particles
+};
+
+struct ResampleOutcome
+{
+  int M = 0, leaf = 0, bins = 0, windows = 0;
+  ResampleCountedBy counted_by = COUNTED_BY_HOST_TREE;
+
+  void counted(ResampleCountedBy by, int leaf_, int bins_)
+  {
+    counted_by = by;
+    leaf = leaf_;
+    bins = bins_;
+  }
+};
+
+// the counts of the host's replay, as the stop rule's count mode reads them
+void counted_by_host_tree(const bpf_engine* e, ResampleOutcome* out)
+{
+  out->counted(COUNTED_BY_HOST_TREE, kld_host_k(e), kld_bins(e) ? e->kld_host_bins : e->hist.bin_count());
+}
+
 // The whole resample for a candidate stream of at most kFusedWindow draws as one single-block launch
 // (k_resample_block): draws, histogram tree and KLD stop, weights 1/M, updateConverged.  *handled = false when the
 // stop lies beyond the window, a key does not fit the packing or the tree is too deep: the caller runs the general path.
-int resample_block(bpf_engine* e, int window, bool systematic, const double* targets, bool* handled)
+int resample_block(bpf_engine* e, int window, bool systematic, const double* targets, ResampleOutcome* out,
+                   bool* handled)
 {
   *handled = false;
   SampleSet& a = e->sets[e->cur];
@@ -617,12 +640,9 @@ int resample_block(bpf_engine* e, int window, bool systematic, const double* tar
   }
   if (r5[3] != BPF_FUSED_OK)
     return BPF_OK;
-  e->sample_count = r5[0];
-  e->kld_leaf = r5[1];
-  e->kld_bins = r5[2];
-  e->kld_device_used = true;
-  e->fused_used = 1;
-  e->resample_windows = 1;
+  out->M = r5[0];
+  out->counted(COUNTED_BY_BLOCK, kld_bins(e) ? r5[2] : r5[1], r5[2]);  // BINS mode: the leaf count IS the bin count
+  out->windows = 1;
   *handled = true;
   return BPF_OK;
 }
@@ -1075,210 +1095,235 @@ struct KldReplay
   }
 };
 
-// tracking regime: the previous cycle's stop (+ 25 %) fits one block's window and no recovery draws are due
-int resample_multinomial_block(bpf_engine* e, double w_diff, bool* handled)
+// ---- the drand48 stream behind a resample that kept M samples (resample_plan.hpp: stream_consumed), with the one
+// read-back of the draw chain's word: *state48_out = state0 advanced by what the resample consumed
+int stream_after_resample(bpf_engine* e, uint64_t state0, const StreamUse& use, int M, uint64_t* state48_out)
 {
-  *handled = false;
-  const int maxs = e->max_samples;
-  const int w0 = std::min(std::max(1024, std::min(e->window_hint, maxs)), maxs);
-  const bool long_stream0 = e->window_hint >= maxs && maxs >= e->kld_device_min;
-  if (!e->fused_resample || w_diff != 0.0 || w0 > kFusedWindow || long_stream0)
-    return BPF_OK;
-  H2D_OR_RETURN(resample_block(e, w0, false, nullptr, handled));
-  if (*handled)
+  int chain_word = 0;
+  if (use.regime == STREAM_MULTINOMIAL_CHAIN)
   {
-    const int M = e->sample_count;
-    e->rng = lcg_skip_host(e->rng, 2ull * (uint64_t)M, e->jump);
-    e->window_hint = resample_window_for(M);
+    HIPCHK(e, e->h_chain_word.reserve(1));
+    HIPCHK(e, hipMemcpyAsync(e->h_chain_word.p, e->d_chain.p + (M - 1), sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    chain_word = e->h_chain_word.p[0];
+  }
+  *state48_out = lcg_skip_host(state0, stream_consumed(use, M, chain_word), e->jump);
+  return BPF_OK;
+}
+
+// ---- the multinomial resampler (particle_filter.cpp:357-420)
+// w_diff > 0 (:383-388): every draw first tests a uniform against w_diff; where each draw finds its stream elements
+// is resolved up front for all candidate draws, into e->d_chain
+struct RecoveryDraws
+{
+  FreeSpaceDev free_space{};
+  const int* chain = nullptr;
+};
+
+int multinomial_recovery_chain(bpf_engine* e, double w_diff, RecoveryDraws* R)
+{
+  int rc = ensure_free_space(e, &R->free_space);
+  if (rc != BPF_OK)
+    return rc;
+  rc = pose_check_scored(e) ? resolve_scored_chain(e, R->free_space, w_diff, e->max_samples)
+                            : build_draw_chain(e, w_diff, e->max_samples, R->free_space.retries);
+  if (rc != BPF_OK)
+    return rc;
+  R->chain = e->d_chain.p;
+  return BPF_OK;
+}
+
+// The single engine's tracking predicate: the previous cycle's stop (+ 25 %) fits one block's window (*w0, the first
+// window BEFORE the schedule's cap at 4096), no recovery draws are due and no long stream is expected.  (The sharded
+// driver's differs: shard_tracking in abi_mailbox_step.inl.)
+bool multinomial_tracking(const bpf_engine* e, double w_diff, int* w0)
+{
+  const int maxs = e->max_samples;
+  *w0 = std::min(std::max(1024, std::min(e->window_hint, maxs)), maxs);
+  const bool long_stream0 = e->window_hint >= maxs && maxs >= e->kld_device_min;
+  return e->fused_resample && w_diff == 0.0 && *w0 <= kFusedWindow && !long_stream0;
+}
+
+// the arguments of a draw window, all but the window itself
+DrawArgs multinomial_draw_args(bpf_engine* e, const RecoveryDraws& R)
+{
+  DrawArgs A{};
+  A.src = e->sets[e->cur].dev();
+  A.n_src = e->sample_count;
+  A.cdf = e->d_cdf.p;
+  A.dst = e->sets[e->cur ^ 1].dev();
+  A.rng_state = e->rng;
+  A.jump = e->jump;
+  A.keys = e->d_keys.p;
+  A.src_index = e->d_src_index.p;
+  A.miss_flag = e->d_flags.p;
+  A.sharded = 0;
+  A.chain = R.chain;
+  A.free_space = R.free_space;
+  A.guide = e->wc.cdf_guide_valid ? e->d_cdf_guide.p : nullptr;
+  return A;
+}
+
+// No stop so far and a long stream ahead (a spread cloud): the ordered replay moves to the device for the whole
+// stream.  *handled = false: key range or depth outside what the device tree takes, host replay as before.
+int multinomial_device_stream(bpf_engine* e, const DrawArgs& A, ResampleOutcome* out, int* stop, bool* handled)
+{
+  KldOutcome dev;
+  int rc = kld_on_device(e, A, e->max_samples, &dev);
+  if (rc != BPF_OK)
+    return rc;
+  *handled = dev.handled;
+  if (dev.handled)
+  {
+    out->windows++;
+    *stop = dev.stop;
+    out->counted(COUNTED_BY_DEVICE_TREE, dev.leaf, dev.bins);
   }
   return BPF_OK;
 }
 
-int resample_multinomial(bpf_engine* e, double w_diff)
+// One window [m0, m1) replayed on the host: the draws, their keys through the zero-copy hand-off or a copy, and the
+// ordered insertion with the stop test; *stop = the stop count when the window held it
+int multinomial_host_window(bpf_engine* e, DrawArgs A, int m0, int m1, KldReplay* replay, int* stop)
 {
-  SampleSet& a = e->sets[e->cur];
-  SampleSet& b = e->sets[e->cur ^ 1];
-  const int n = e->sample_count;
-  const int maxs = e->max_samples;
-  FreeSpaceDev free_space{};
-  const int* chain = nullptr;
-  if (w_diff > 0.0)
+  A.m0 = m0;
+  A.m1 = m1;
+  const int wn = m1 - m0;
+  const bool zero_copy = e->zero_copy_keys && wn <= (1 << 20);
+  if (zero_copy)
+    arm_key_handoff(e, wn, &A);
   {
-    // :383-388: every draw first tests a uniform against w_diff; where each draw finds its stream elements is
-    // resolved up front for all candidate draws
-    int rcf = ensure_free_space(e, &free_space);
-    if (rcf != BPF_OK)
-      return rcf;
-    rcf = pose_check_scored(e) ? resolve_scored_chain(e, free_space, w_diff, maxs)
-                               : build_draw_chain(e, w_diff, maxs, free_space.retries);
-    if (rcf != BPF_OK)
-      return rcf;
-    chain = e->d_chain.p;
+    ProfScope ps(e, BPF_K_DRAW);
+    hipLaunchKernelGGL(k_draw_select, dim3(blocks_for(wn, 256)), dim3(256), 0, e->stream, A);
   }
-  e->fused_used = 0;
-  bool tracked = false;
-  H2D_OR_RETURN(resample_multinomial_block(e, w_diff, &tracked));
-  if (tracked)
-    return BPF_OK;
+  HIPCHK(e, hipGetLastError());
+  KeyView keys{ e->h_keys.p, wn };
+  if (!(zero_copy && wait_generation(e, A.generation)))
+    H2D_OR_RETURN(copy_key_triples(e, wn, &keys));  // (the kernel writes e->d_keys either way)
+  for (int m = m0; m < m1 && *stop < 0; ++m)
+    if (replay->feed(e, keys.key(m - m0, 0), keys.key(m - m0, 1), keys.key(m - m0, 2), m + 1))
+      *stop = m + 1;
+  return BPF_OK;
+}
+
+// The general path: windows of candidate draws by the schedule of resample_plan.hpp, replayed on the host in order
+// until the stop rule ends the stream, or the whole stream handed to the device tree
+int multinomial_windows(bpf_engine* e, const RecoveryDraws& R, ResampleOutcome* out)
+{
+  const int maxs = e->max_samples;
   HIPCHK(e, e->d_keys.reserve((size_t)maxs * 3));
   HIPCHK(e, e->d_src_index.reserve((size_t)maxs));
   HIPCHK(e, e->h_keys.reserve((size_t)maxs * 3));
   kld_host_reset(e, std::min(maxs, 1 << 20));
-  int m0 = 0, stop = -1;
-  int window = std::max(1024, std::min(e->window_hint, maxs));
-  e->resample_windows = 0;
+  const DrawArgs A = multinomial_draw_args(e, R);
+  // whole_stream_at_start: a previous cycle that ran to the end sends this one to the device tree at once
+  WindowSchedule s = window_schedule(e->window_hint, maxs, e->kld_device_min, true);
   KldReplay replay;
-  e->kld_device_used = false;
-  bool device_declined = false;
-  // keep the host's first window short when the device tree can take over after it
-  if (window > 4096 && maxs - 4096 >= e->kld_device_min)
-    window = 4096;
-  while (m0 < maxs && stop < 0)
+  int stop = -1;
+  bool on_device = false;
+  out->windows = 0;
+  while (s.m0 < maxs && stop < 0 && !on_device)
   {
-    const int m1 = std::min(maxs, m0 + window);
-    DrawArgs A{};
-    A.src = a.dev();
-    A.n_src = n;
-    A.cdf = e->d_cdf.p;
-    A.dst = b.dev();
-    A.m0 = m0;
-    A.m1 = m1;
-    A.rng_state = e->rng;
-    A.jump = e->jump;
-    A.keys = e->d_keys.p;
-    A.src_index = e->d_src_index.p;
-    A.miss_flag = e->d_flags.p;
-    A.sharded = 0;
-    A.chain = chain;
-    A.free_space = free_space;
-    A.guide = e->wc.cdf_guide_valid ? e->d_cdf_guide.p : nullptr;
-    // long stream ahead: the previous cycle ran to the end, or the windows so far found no stop and the bound for
-    // the leaves seen so far (a lower estimate of where the stop will be) is still far away
-    const bool long_stream = (m0 > 0 ? replay.limit - m0 >= e->kld_device_min : e->window_hint >= maxs) &&
-                             maxs - m0 >= e->kld_device_min;
-    if (long_stream && !device_declined)
+    if (s.whole_stream_due(replay.limit))
     {
-      // no stop inside the first window and a long stream ahead (a spread cloud): the ordered replay moves
-      // to the device for the whole stream
-      KldOutcome dev;
-      int rc = kld_on_device(e, A, maxs, &dev);
-      if (rc != BPF_OK)
-        return rc;
-      if (dev.handled)
-      {
-        e->resample_windows++;
-        stop = dev.stop;
-        e->kld_device_used = true;
-        e->kld_leaf = dev.leaf;
-        e->kld_bins = dev.bins;
+      H2D_OR_RETURN(multinomial_device_stream(e, A, out, &stop, &on_device));
+      if (on_device)
         break;
-      }
-      device_declined = true;  // key range or depth outside what the device tree takes: host replay as before
+      s.device_declined = true;
     }
-    const int wn = m1 - m0;
-    const bool zero_copy = e->zero_copy_keys && wn <= (1 << 20);
-    if (zero_copy)
-      arm_key_handoff(e, wn, &A);
-    {
-      ProfScope ps(e, BPF_K_DRAW);
-      hipLaunchKernelGGL(k_draw_select, dim3(blocks_for(wn, 256)), dim3(256), 0, e->stream, A);
-    }
-    HIPCHK(e, hipGetLastError());
-    KeyView keys{ e->h_keys.p, wn };
-    if (!(zero_copy && wait_generation(e, A.generation)))
-      H2D_OR_RETURN(copy_key_triples(e, wn, &keys));  // (the kernel writes e->d_keys either way)
-    e->resample_windows++;
-    for (int m = m0; m < m1 && stop < 0; ++m)
-      if (replay.feed(e, keys.key(m - m0, 0), keys.key(m - m0, 1), keys.key(m - m0, 2), m + 1))
-        stop = m + 1;
-    m0 = m1;
-    // next window: up to a quarter past the bound for the leaves seen so far
-    const int need = replay.limit - m0;
-    window = resample_window_for(need);
+    H2D_OR_RETURN(multinomial_host_window(e, A, s.m0, s.m1(), &replay, &stop));
+    out->windows++;
+    s.next(replay.limit);
   }
-  const int M = (stop > 0) ? stop : maxs;
+  out->M = (stop > 0) ? stop : maxs;
   // the window that found the stop also inserted nothing past it: hist is exactly set b's tree
-  if (chain != nullptr)
-  {
-    HIPCHK(e, e->h_chain_word.reserve(1));
-    HIPCHK(e, hipMemcpyAsync(e->h_chain_word.p, chain + (M - 1), sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    e->rng = lcg_skip_host(e->rng, chain_consumed(e->h_chain_word.p[0]), e->jump);
-  }
-  else
-    e->rng = lcg_skip_host(e->rng, 2ull * (uint64_t)M, e->jump);
-  e->window_hint = resample_window_for(M);
-  e->sample_count = M;
+  if (!on_device)
+    counted_by_host_tree(e, out);
   return BPF_OK;
 }
 
-// the systematic targets in e->h_targets: a serial floating-point chain (particle_filter.cpp:337-341), target +=
-// delta, and target -= 1 once it passes 1.  A CPU core runs that dependency chain several times faster than a GPU
-// lane, with the same IEEE arithmetic, so the host forms the targets and the kernel reads them from pinned memory.
-int systematic_targets(bpf_engine* e, double start, int num_systematic)
+int resample_multinomial(bpf_engine* e, double w_diff, ResampleOutcome* out)
 {
-  HIPCHK(e, e->h_targets.reserve((size_t)e->max_samples));
-  const double delta = 1.0 / num_systematic;
-  double t = start;
-  double* out = e->h_targets.p;
-  for (int i = 0; i < num_systematic; ++i)
-  {
-    out[i] = t;
-    t += delta;
-    if (t > 1.0)
-      t -= 1.0;
-  }
-  return BPF_OK;
-}
-
-int resample_systematic(bpf_engine* e, double w_diff)
-{
-  SampleSet& a = e->sets[e->cur];
-  SampleSet& b = e->sets[e->cur ^ 1];
-  const int n = e->sample_count;
-  e->fused_used = 0;
-  int count = resample_limit(e->tree.leaf_count, e->min_samples, e->max_samples, e->pop_err, e->pop_z);
-  FreeSpaceDev free_space{};
-  int num_random = 0;
-  uint64_t random_consumed = 0;  // stream elements of the random pose calls, after the systematic start
+  const uint64_t rng0 = e->rng;
+  RecoveryDraws recovery;
+  StreamUse stream;
   if (w_diff > 0.0)
   {
-    // particle_filter.cpp:295-306: room for random poses on top of the systematic ones
-    count *= (1.0 + w_diff);
-    if (count > e->max_samples)
-      count = e->max_samples;
-    num_random = (int)(w_diff * count);
-    if (num_random > 0)
-    {
-      int rcf = ensure_free_space(e, &free_space);
-      if (rcf != BPF_OK)
-        return rcf;
-      if (pose_check_scored(e))
-      {
-        unsigned end = 0;
-        rcf = resolve_scored_calls(e, free_space, e->rng, 2, num_random, &end);
-        if (rcf != BPF_OK)
-          return rcf;
-        free_space.accept = e->d_accept.p;
-        random_consumed = (uint64_t)end - 2ull;
-      }
-      else if (1ll + (2ll * free_space.retries + 2) * num_random >= 0x7fffffffll)
-        return e->fail(BPF_ERR_CAPACITY, "random pose calls would pass 31-bit stream positions");
-      else
-        random_consumed = (2ull * (uint64_t)free_space.retries + 2ull) * (uint64_t)num_random;
-    }
+    H2D_OR_RETURN(multinomial_recovery_chain(e, w_diff, &recovery));
+    stream.regime = STREAM_MULTINOMIAL_CHAIN;
   }
-  const int num_systematic = count - num_random;
+  int w0 = 0;
+  bool tracked = false;
+  if (multinomial_tracking(e, w_diff, &w0))
+    H2D_OR_RETURN(resample_block(e, w0, false, nullptr, out, &tracked));
+  if (!tracked)
+    H2D_OR_RETURN(multinomial_windows(e, recovery, out));
+  e->window_hint = resample_window_for(out->M);
+  return stream_after_resample(e, rng0, stream, out->M, &e->rng);
+}
+
+// ---- the systematic resampler (particle_filter.cpp:269-355)
+// The targets in e->h_targets: the serial chain of resample_plan.hpp from the stream state behind the systematic
+// start.  A CPU core runs that dependency chain several times faster than a GPU lane, with the same IEEE arithmetic,
+// so the host forms the targets and the kernel reads them from pinned memory.  A window kernel of the sharded filter
+// may still be reading the previous ones (systematic_targets_in_use; no event on an engine that never ran sharded).
+int systematic_targets(bpf_engine* e, uint64_t start_state48, int count, int num_systematic)
+{
+  HIPCHK(e, e->h_targets.reserve((size_t)std::max(count, e->max_samples)));
+  if (e->targets_read)
+    HIPCHK(e, hipEventSynchronize(e->targets_read));
+  systematic_target_chain(std::ldexp((double)start_state48, -48), num_systematic, e->h_targets.p);
+  return BPF_OK;
+}
+
+// The sample budget for a set of `leaf_count` leaves (resample_plan.hpp), with the free-space list when random pose
+// calls are due; calls that are not resolved by score must fit 31-bit stream positions
+int systematic_budget_for(bpf_engine* e, int leaf_count, double w_diff, SystematicBudget* B, FreeSpaceDev* free_space)
+{
+  *B = systematic_budget(resample_limit(leaf_count, e->min_samples, e->max_samples, e->pop_err, e->pop_z), w_diff,
+                         e->max_samples);
+  if (B->n_random <= 0)
+    return BPF_OK;
+  int rc = ensure_free_space(e, free_space);
+  if (rc != BPF_OK)
+    return rc;
+  if (!pose_check_scored(e) && !random_calls_fit(free_space->retries, B->n_random))
+    return e->fail(BPF_ERR_CAPACITY, "random pose calls would pass 31-bit stream positions");
+  return BPF_OK;
+}
+
+struct SystematicPlan
+{
+  SystematicBudget budget;
+  SystematicArgs A{};  // all but the targets and the key hand-off
+  StreamUse stream;
+};
+
+// budget, random pose calls, buffers, targets and the kernel arguments; e->rng stands behind the systematic start
+int systematic_plan(bpf_engine* e, double w_diff, SystematicPlan* P)
+{
+  FreeSpaceDev free_space{};
+  P->stream.regime = STREAM_SYSTEMATIC;
+  H2D_OR_RETURN(systematic_budget_for(e, e->tree.leaf_count, w_diff, &P->budget, &free_space));
+  const int count = P->budget.count, num_random = P->budget.n_random;
+  P->stream.retries = free_space.retries;
+  P->stream.n_random = num_random;
+  if (num_random > 0 && pose_check_scored(e))
+  {
+    H2D_OR_RETURN(resolve_scored_calls(e, free_space, e->rng, 2, num_random, &P->stream.scored_end));
+    free_space.accept = e->d_accept.p;
+    P->stream.regime = STREAM_SYSTEMATIC_SCORED;
+  }
   const uint64_t rng_before = e->rng;
   e->rng = lcg_skip_host(e->rng, 1, e->jump);
   HIPCHK(e, e->d_keys.reserve((size_t)e->max_samples * 3));
   HIPCHK(e, e->d_src_index.reserve((size_t)e->max_samples));
   HIPCHK(e, e->h_keys.reserve((size_t)e->max_samples * 3));
-  SystematicArgs A{};
-  A.src = a.dev();
-  A.n_src = n;
+  SystematicArgs& A = P->A;
+  A.src = e->sets[e->cur].dev();
+  A.n_src = e->sample_count;
   A.cdf = e->d_cdf.p;
-  A.dst = b.dev();
+  A.dst = e->sets[e->cur ^ 1].dev();
   A.count = count;
   A.n_random = num_random;
   A.rng_state = rng_before;
@@ -1287,21 +1332,15 @@ int resample_systematic(bpf_engine* e, double w_diff)
   A.keys = e->d_keys.p;
   A.src_index = e->d_src_index.p;
   A.miss_flag = e->d_flags.p;
-  H2D_OR_RETURN(systematic_targets(e, std::ldexp((double)e->rng, -48), num_systematic));
-  if (e->fused_resample && num_random == 0 && count <= kFusedWindow)
-  {
-    // the whole resample as one launch (k_resample_block): selection, the new set's histogram tree, weights,
-    // updateConverged; the targets are read straight from the pinned buffer
-    bool handled = false;
-    int rcb = resample_block(e, count, true, e->h_targets.p, &handled);
-    if (rcb != BPF_OK)
-      return rcb;
-    if (handled)
-      return BPF_OK;
-  }
-  // the kernel reads the targets straight from the pinned buffer (28 KB for 3.5 k samples) and, like the
-  // multinomial draw kernel, leaves the keys in pinned memory behind a generation word -- or, for a large set in BINS
-  // mode, in e->d_keys, where the device counts the new set's distinct keys (the key hash and one scan)
+  return systematic_targets(e, e->rng, count, count - num_random);
+}
+
+// The general path: the kernel reads the targets straight from the pinned buffer (28 KB for 3.5 k samples) and, like
+// the multinomial draw kernel, leaves the keys in pinned memory behind a generation word -- or, for a large set in
+// BINS mode, in e->d_keys, where the device counts the new set's distinct keys (the key hash and one scan)
+int systematic_select_and_count(bpf_engine* e, SystematicArgs A, ResampleOutcome* out)
+{
+  const int count = A.count;
   A.targets = e->h_targets.p;
   const bool device_count = kld_bins(e) && count >= 8192;
   const bool zero_copy = e->zero_copy_keys && count <= (1 << 20) && !device_count;
@@ -1316,10 +1355,7 @@ int resample_systematic(bpf_engine* e, double w_diff)
   if (device_count)
     H2D_OR_RETURN(kld_tree_on_device(e, count, &dev, true));
   if (dev.handled)
-  {
-    e->kld_device_used = true;
-    e->kld_leaf = e->kld_bins = dev.bins;
-  }
+    out->counted(COUNTED_BY_DEVICE_TREE, dev.bins, dev.bins);
   else
   {
     KeyView keys{ e->h_keys.p, count };
@@ -1330,12 +1366,26 @@ int resample_systematic(bpf_engine* e, double w_diff)
     kld_host_reset(e, std::min(count, 1 << 20));
     for (int m = 0; m < count; ++m)
       kld_host_insert(e, keys.key(m, 0), keys.key(m, 1), keys.key(m, 2));
+    counted_by_host_tree(e, out);
   }
-  // :316-324: the random pose calls took 2 (retries + 1) uniforms each, right after the systematic start
-  e->rng = lcg_skip_host(e->rng, random_consumed, e->jump);
-  e->resample_windows = 1;
-  e->sample_count = count;
+  out->M = count;
+  out->windows = 1;
   return BPF_OK;
+}
+
+int resample_systematic(bpf_engine* e, double w_diff, ResampleOutcome* out)
+{
+  SystematicPlan P;
+  H2D_OR_RETURN(systematic_plan(e, w_diff, &P));
+  bool handled = false;
+  // the whole resample as one launch (k_resample_block): selection, the new set's histogram tree, weights,
+  // updateConverged; the targets are read straight from the pinned buffer
+  if (e->fused_resample && P.budget.n_random == 0 && P.budget.count <= kFusedWindow)
+    H2D_OR_RETURN(resample_block(e, P.budget.count, true, e->h_targets.p, out, &handled));
+  if (!handled)
+    H2D_OR_RETURN(systematic_select_and_count(e, P.A, out));
+  // :316-324: the random pose calls took their uniforms right after the systematic start
+  return stream_after_resample(e, P.A.rng_state, P.stream, out->M, &e->rng);
 }
 
 int upload_samples(bpf_engine* e, const double* aos, int n, SampleSet& dst)

@@ -646,6 +646,11 @@ def even_counts(n, W):
     return [(n * (r + 1)) // W - (n * r) // W for r in range(W)]
 
 
+def resample_window_for(x):
+    """A resample window for a stop expected x draws ahead: a quarter more, in whole 1024s (csrc/resample_plan.hpp)."""
+    return max(1024, (x + x // 4 + 1023) // 1024 * 1024)
+
+
 class ShardedState:
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -1227,7 +1232,7 @@ class ShardedFilter:
             if stop < 0:
                 # next window: up to a quarter past the bound for the leaves seen so far (a lower estimate of the stop)
                 need = b.resample_limit(b.kld_counts()[0]) - m0
-                win = max(1024, (need + need // 4 + 1023) // 1024 * 1024)
+                win = resample_window_for(need)
         M = stop if stop > 0 else self.max_global
         leaf, bins = device_counts if device_counts is not None else b.kld_counts()
         lo, hi = (M * self.rank) // W, (M * (self.rank + 1)) // W
@@ -1245,7 +1250,7 @@ class ShardedFilter:
         self.counts = self._even_counts(M)
         self.sample_count = M
         self.leaf_count, self.bin_count = leaf, bins
-        self.window_hint = max(1024, ((M + M // 4) + 1023) // 1024 * 1024)
+        self.window_hint = resample_window_for(M)
         self.totals = None  # the weights are 1/M now; the old totals no longer describe them
 
     def restore(self, counts, leaf_count=0):
