@@ -555,6 +555,9 @@ int score_cloud(bpf_engine* e, ParticlesDev p, int n, const float* points_xyz, i
 #define BPF_CLOUD_LAUNCH(X, P, D) \
   LAUNCH_TIMED(e, BPF_K_SCORE, (k_cloud_score<X, P, D>), dim3(n_chunks, A.slabs), dim3(256), 0, A)
     const bool border = BPF_CLOUD_BORDER != 0 && planar && dense && e->map3.border_code >= 0;
+    // (BORDER is a form of the planar dense kernel: the bits name the template instance below)
+    e->last_cloud_form = 32 | (exact_rinv ? 1 : 0) | (planar ? 2 : 0) | (dense ? 4 : 0) | (border ? 8 : 0) |
+                         (A.round_count[0] > 0 ? 16 : 0);
     if (exact_rinv && border)
       LAUNCH_TIMED(e, BPF_K_SCORE, (k_cloud_score<true, true, true, true>), dim3(n_chunks, A.slabs), dim3(256), 0, A);
     else if (border)

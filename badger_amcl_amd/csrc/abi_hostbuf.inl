@@ -158,6 +158,14 @@ int bpf_kld_last_form(bpf_engine* e, int* form_out)
   return BPF_OK;
 }
 
+int bpf_cloud_last_form(bpf_engine* e, int* form_out)
+{
+  if (!e || !form_out)
+    return BPF_ERR_INVALID_ARGUMENT;
+  *form_out = e->last_cloud_form;
+  return BPF_OK;
+}
+
 int bpf_seam_last_plan(bpf_engine* e, int* chunks_out, int* pinned_out)
 {
   if (!e)

@@ -626,6 +626,7 @@ struct bpf_engine
   int tile_parity = 0;              // which half of hist the last tile-sorted update counted into
   DevBuf<double4> d_prep_sorted;
   int last_score_form = 0;          // diagnostics: 3 = the last scoring launch walked the particles in tile order
+  int last_cloud_form = 0;          // diagnostics: 32 | the k_cloud_score instance of the last launch (badger_pf.h)
 
   // ---- profiling
   bool profiling = false;

@@ -125,6 +125,13 @@ class Engine:
         self.check(self.lib.bpf_kld_last_form(self.h, C.byref(a)))
         return a.value
 
+    def cloud_last_form(self):
+        """0 = no point-cloud launch yet, otherwise 32 | bits of the k_cloud_score instance the last one took:
+        1 = exact reciprocal, 2 = PLANAR, 4 = DENSE, 8 = BORDER, 16 = graded partition on."""
+        a = C.c_int()
+        self.check(self.lib.bpf_cloud_last_form(self.h, C.byref(a)))
+        return a.value
+
     def seam_last_plan(self):
         """(chunks, pinned) of the last applyModelToSampleSet: 0 chunks = the plain upload / score / download, -1 = one
         launch that read and wrote the registered records in place."""

@@ -124,6 +124,11 @@ int bpf_score_last_form(bpf_engine* e, int* form_out);
  * pair per level (also after the pieces declined a stream), 3 = the persistent launch, 4 = no tree: the distinct-key
  * count of BPF_KLD_COUNT_BINS (bpf_pf_set_kld_count), 0 = none yet */
 int bpf_kld_last_form(bpf_engine* e, int* form_out);
+/* which instance of the 3-D scoring kernel the last point-cloud launch of this engine took: 0 = none yet, otherwise
+ * 32 | bits with 1 = the exact-reciprocal voxel form (1 / resolution representable), 2 = PLANAR (mounting without roll
+ * or pitch), 4 = DENSE (gathers from the dense tiled copy of the LUT), 8 = BORDER (off-map cells read the volume's
+ * border ring), 16 = the graded partition of the particles was on.  Read-only: it has no effect on any launch. */
+int bpf_cloud_last_form(bpf_engine* e, int* form_out);
 /* what the last bpf_planar_apply_model_to_sample_set did: chunks of the pipelined form (0 = the plain upload / score /
  * download sequence, -1 = one scoring launch that read and wrote the registered records in place); pinned = the buffer
  * lies in a registered range */
