@@ -211,6 +211,9 @@ SIGNATURES = {
     "bpf_planar_search_space": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _ip]),
     "bpf_pose_search_merge": (C.c_int, [C.POINTER(PoseHit), _ip, C.c_int, C.c_int, C.POINTER(PoseHit), _ip]),
     "bpf_pose_search_window": (C.c_int, []),
+    "bpf_cloud_search_poses": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_longlong,
+                                         C.c_longlong, C.c_int, C.POINTER(PoseHit), _ip]),
+    "bpf_cloud_search_space": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _ip]),
     "bpf_device_memory_info": (C.c_int, [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "bpf_profile_enable": (C.c_int, [_vp, C.c_int]),
     "bpf_profile_reset": (C.c_int, [_vp]),

@@ -463,15 +463,12 @@ int bpf_cloud_set_scanner_to_footprint_tf(bpf_engine* e, const double xyz[3], co
 
 namespace
 {
-int score_cloud(bpf_engine* e, ParticlesDev p, int n, const float* points_xyz, int n_points)
+// score_cloud in its two parts (the pose search of abi_pose_search_cloud.inl stages once and launches per window; the
+// callers' checks of the map, the model and the arguments are score_cloud's).
+// The staging: the one stream wait the single-slot buffers need, the points as float SoA, and the table of per-ratio
+// terms, which follows point_cloud_scanner.cpp:137-159,177-191
+int stage_cloud(bpf_engine* e, const float* points_xyz, int n_points)
 {
-  if (!e->have_map3d)
-    return e->fail(BPF_ERR_NOT_CONFIGURED, "no 3-D map set");
-  if (!e->cloud_configured)
-    return e->fail(BPF_ERR_NOT_CONFIGURED, "point-cloud model not set");
-  if (!points_xyz || n_points <= 0 || n <= 0)
-    return e->fail(BPF_ERR_INVALID_ARGUMENT, "empty cloud or sample set");
-  // stage points as float SoA; the table of per-ratio terms follows point_cloud_scanner.cpp:137-159,177-191
   HIPCHK(e, hipStreamSynchronize(e->stream));  // staging buffers are single-slot
   HIPCHK(e, e->h_points.reserve((size_t)n_points * 3));
   HIPCHK(e, e->d_points.reserve((size_t)n_points * 3));
@@ -506,6 +503,13 @@ int score_cloud(bpf_engine* e, ParticlesDev p, int n, const float* points_xyz, i
   }
   HIPCHK(e, hipMemcpyAsync(e->d_cloud_table.p, e->h_cloud_table.p, 257 * sizeof(double), hipMemcpyHostToDevice,
                            e->stream));
+  return BPF_OK;
+}
+
+// The launches, against what stage_cloud left on the device: k_cloud_affine, the k_cloud_score instance,
+// k_cloud_finish.  Enqueues only (the scratch grows here when n is larger than any before).
+int launch_cloud(bpf_engine* e, ParticlesDev p, int n, int n_points)
+{
   const int n_chunks = blocks_for(n_points, kCloudChunk);
   HIPCHK(e, e->d_affine.reserve((size_t)n * 12));
   HIPCHK(e, e->d_cloud_partials.reserve((size_t)n_chunks * n));
@@ -592,6 +596,20 @@ int score_cloud(bpf_engine* e, ParticlesDev p, int n, const float* points_xyz, i
   HIPCHK(e, hipGetLastError());
   e->evals_last = (long long)n * n_points;
   return BPF_OK;
+}
+
+int score_cloud(bpf_engine* e, ParticlesDev p, int n, const float* points_xyz, int n_points)
+{
+  if (!e->have_map3d)
+    return e->fail(BPF_ERR_NOT_CONFIGURED, "no 3-D map set");
+  if (!e->cloud_configured)
+    return e->fail(BPF_ERR_NOT_CONFIGURED, "point-cloud model not set");
+  if (!points_xyz || n_points <= 0 || n <= 0)
+    return e->fail(BPF_ERR_INVALID_ARGUMENT, "empty cloud or sample set");
+  const int rc = stage_cloud(e, points_xyz, n_points);
+  if (rc != BPF_OK)
+    return rc;
+  return launch_cloud(e, p, n, n_points);
 }
 }  // namespace
 

@@ -38,6 +38,59 @@ int search_space_of(bpf_engine* e, int headings, int cell_stride, SearchSpace* S
   return BPF_OK;
 }
 
+// ---- the selection around the scoring, shared with the cloud search (abi_pose_search_cloud.inl)
+// its buffers, for windows of up to kSearchWindow candidates, and the running best-k list emptied
+int search_begin(bpf_engine* e)
+{
+  const int max_tiles = kSearchWindow / kSearchTile;
+  HIPCHK(e, e->d_search_best.reserve(kSearchMaxK));
+  HIPCHK(e, e->d_search_tiles.reserve((size_t)max_tiles * kSearchMaxK));
+  HIPCHK(e, e->d_search_counts.reserve(1 + max_tiles));
+  HIPCHK(e, e->d_search_hits.reserve(kSearchMaxK));
+  HIPCHK(e, e->h_search_hits.reserve(kSearchMaxK));
+  HIPCHK(e, e->h_search_count.reserve(1));
+  HIPCHK(e, hipMemsetAsync(e->d_search_counts.p, 0, sizeof(int), e->stream));
+  return BPF_OK;
+}
+
+// the scores of candidates c0 .. c0 + n - 1, as they stand in e->cand.w, folded into the running best-k list
+int search_fold_window(bpf_engine* e, int n, long long c0, int k)
+{
+  int kp = 2;
+  while (kp < k)
+    kp <<= 1;
+  const int tiles = blocks_for(n, kSearchTile);
+  hipLaunchKernelGGL(k_search_select, dim3(tiles), dim3(kSearchThreads), 0, e->stream, (const double*)e->cand.w.p, n,
+                     c0, k, (const SearchEntry*)e->d_search_best.p, (const int*)e->d_search_counts.p,
+                     e->d_search_tiles.p, e->d_search_counts.p + 1);
+  hipLaunchKernelGGL(k_search_merge, dim3(1), dim3(kSearchThreads), 0, e->stream, e->d_search_best.p,
+                     e->d_search_counts.p, k, kp, (const SearchEntry*)e->d_search_tiles.p,
+                     (const int*)(e->d_search_counts.p + 1), tiles);
+  if (hipGetLastError() != hipSuccess)
+    return e->fail(BPF_ERR_HIP, "pose search selection launch");
+  return BPF_OK;
+}
+
+// the list as rows for the caller: k_search_hits, the copy of the rows, and the call's wait for them
+int search_finish(bpf_engine* e, const SearchSpace& S, int k, bpf_pose_hit* hits_out, int* n_hits_out)
+{
+  hipLaunchKernelGGL(k_search_hits, dim3(blocks_for(k, 256)), dim3(256), 0, e->stream,
+                     (const SearchEntry*)e->d_search_best.p, (const int*)e->d_search_counts.p, S, e->d_search_hits.p);
+  if (hipGetLastError() != hipSuccess)
+    return e->fail(BPF_ERR_HIP, "k_search_hits launch");
+  hipError_t r = hipMemcpyAsync(e->h_search_count.p, e->d_search_counts.p, sizeof(int), hipMemcpyDeviceToHost, e->stream);
+  if (r == hipSuccess)
+    r = hipMemcpyAsync(e->h_search_hits.p, e->d_search_hits.p, (size_t)k * sizeof(bpf_pose_hit), hipMemcpyDeviceToHost,
+                       e->stream);
+  if (r != hipSuccess)
+    return e->fail_hip(r, "pose search: copy of the hits");
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  const int n_hits = std::max(0, std::min(e->h_search_count.p[0], k));
+  std::memcpy(hits_out, e->h_search_hits.p, (size_t)n_hits * sizeof(bpf_pose_hit));
+  *n_hits_out = n_hits;
+  return BPF_OK;
+}
+
 int search_poses(bpf_engine* e, const double* ranges, const double* angles, int range_count, double range_max,
                  int headings, int cell_stride, long long first, long long count, int k, bpf_pose_hit* hits_out,
                  int* n_hits_out)
@@ -65,18 +118,10 @@ int search_poses(bpf_engine* e, const double* ranges, const double* angles, int 
   if (count == 0)
     return BPF_OK;
 
-  const int max_tiles = kSearchWindow / kSearchTile;
-  HIPCHK(e, e->d_search_best.reserve(kSearchMaxK));
-  HIPCHK(e, e->d_search_tiles.reserve((size_t)max_tiles * kSearchMaxK));
-  HIPCHK(e, e->d_search_counts.reserve(1 + max_tiles));
-  HIPCHK(e, e->d_search_hits.reserve(kSearchMaxK));
-  HIPCHK(e, e->h_search_hits.reserve(kSearchMaxK));
-  HIPCHK(e, e->h_search_count.reserve(1));
   HIPCHK(e, e->cand.reserve((size_t)std::min<long long>(count, kSearchWindow)));
-  HIPCHK(e, hipMemsetAsync(e->d_search_counts.p, 0, sizeof(int), e->stream));
-  int kp = 2;
-  while (kp < k)
-    kp <<= 1;
+  rc = search_begin(e);
+  if (rc != BPF_OK)
+    return rc;
   // from the first launch on, a failure returns with the stream drained
   auto drained = [&](int code) {
     (void)hipStreamSynchronize(e->stream);
@@ -96,31 +141,12 @@ int search_poses(bpf_engine* e, const double* ranges, const double* angles, int 
       if (rc != BPF_OK)
         return drained(rc);
     }
-    const int tiles = blocks_for(n, kSearchTile);
-    hipLaunchKernelGGL(k_search_select, dim3(tiles), dim3(kSearchThreads), 0, e->stream, (const double*)e->cand.w.p, n,
-                       c0, k, (const SearchEntry*)e->d_search_best.p, (const int*)e->d_search_counts.p,
-                       e->d_search_tiles.p, e->d_search_counts.p + 1);
-    hipLaunchKernelGGL(k_search_merge, dim3(1), dim3(kSearchThreads), 0, e->stream, e->d_search_best.p,
-                       e->d_search_counts.p, k, kp, (const SearchEntry*)e->d_search_tiles.p,
-                       (const int*)(e->d_search_counts.p + 1), tiles);
-    if (hipGetLastError() != hipSuccess)
-      return drained(e->fail(BPF_ERR_HIP, "pose search selection launch"));
+    rc = search_fold_window(e, n, c0, k);
+    if (rc != BPF_OK)
+      return drained(rc);
   }
-  hipLaunchKernelGGL(k_search_hits, dim3(blocks_for(k, 256)), dim3(256), 0, e->stream,
-                     (const SearchEntry*)e->d_search_best.p, (const int*)e->d_search_counts.p, S, e->d_search_hits.p);
-  if (hipGetLastError() != hipSuccess)
-    return drained(e->fail(BPF_ERR_HIP, "k_search_hits launch"));
-  hipError_t r = hipMemcpyAsync(e->h_search_count.p, e->d_search_counts.p, sizeof(int), hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess)
-    r = hipMemcpyAsync(e->h_search_hits.p, e->d_search_hits.p, (size_t)k * sizeof(bpf_pose_hit), hipMemcpyDeviceToHost,
-                       e->stream);
-  if (r != hipSuccess)
-    return drained(e->fail_hip(r, "pose search: copy of the hits"));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  const int n_hits = std::max(0, std::min(e->h_search_count.p[0], k));
-  std::memcpy(hits_out, e->h_search_hits.p, (size_t)n_hits * sizeof(bpf_pose_hit));
-  *n_hits_out = n_hits;
-  return BPF_OK;
+  rc = search_finish(e, S, k, hits_out, n_hits_out);
+  return rc == BPF_OK ? rc : drained(rc);
 }
 
 // the order of the result: score descending, equal scores by candidate, NaN behind every number

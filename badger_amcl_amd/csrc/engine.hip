@@ -82,6 +82,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_shard_rebalance.inl"
 #include "abi_pose_array.inl"
 #include "abi_pose_search.inl"
+#include "abi_pose_search_cloud.inl"
 #include "abi_bootstrap.inl"
 #include "abi_shard_local.inl"
 #include "abi_measure.inl"

@@ -1,5 +1,7 @@
-// Exhaustive pose search (bpf_planar_search_poses, abi_pose_search.inl): every free cell of the 2-D map at every one
-// of H headings, scored against one scan by the planar scoring path, the best K kept.  Four kernels of its own:
+// Exhaustive pose search (bpf_planar_search_poses, abi_pose_search.inl; bpf_cloud_search_poses,
+// abi_pose_search_cloud.inl): every free cell of the 2-D map -- or every column of the 3-D map's rectangle -- at every
+// one of H headings, scored against one scan by the planar scoring path (one cloud by the 3-D one), the best K kept.
+// Four kernels of its own:
 //
 //   k_search_candidates   one window of candidate poses into the engine's candidate set (one lane per candidate)
 //   k_search_select       a block sorts its tile of the window's scores in LDS (bitonic network) and emits its best
@@ -30,7 +32,9 @@ struct SearchEntry
   unsigned long long key, inv;
 };
 
-// geometry of the candidate enumeration
+// geometry of the candidate enumeration.  Planar search: the strided free list F_s.  Cloud search (cells == nullptr):
+// the columns of Node3D::updateFreeSpaceIndices kept by the stride, as rectangle arithmetic the way FreeSpaceDev
+// carries its 3-D form -- column f is (i0 + (f / n_j) * stride, j0 + (f % n_j) * stride), n_cells = n_i * n_j
 struct SearchSpace
 {
   const int2* cells;  // F_s
@@ -38,6 +42,7 @@ struct SearchSpace
   int headings;
   int size_x, size_y;
   double origin_x, origin_y, resolution;
+  int i0, j0, n_j, stride;  // rectangle form
 };
 
 __host__ __device__ __forceinline__ unsigned long long search_key_of(double score)
@@ -72,8 +77,9 @@ __device__ __forceinline__ bool search_better(const SearchEntry& a, const Search
   return a.key > b.key || (a.key == b.key && a.inv > b.inv);
 }
 
-// the pose of candidate c: the cell expression of random_free_space_pose (integer halves, no contraction), the
-// heading evaluated in double as written
+// the pose of candidate c: the cell expression of random_free_space_pose (2-D: integer halves; 3-D: i * res, j * res
+// of OctoMap::convertMapToWorld; no contraction), the heading evaluated in double as written.  The branch on the form
+// is uniform over the launch.
 __device__ __forceinline__ void search_pose_of(const SearchSpace& S, long long c, int* i, int* j, int* h, double* x,
                                                double* y, double* th)
 {
@@ -82,12 +88,24 @@ __device__ __forceinline__ void search_pose_of(const SearchSpace& S, long long c
   const unsigned cu = (unsigned)c, H = (unsigned)S.headings;
   const unsigned f = cu / H;
   const unsigned hh = cu - f * H;
-  const int2 cell = S.cells[f];
-  *i = cell.x;
-  *j = cell.y;
   *h = (int)hh;
-  *x = S.origin_x + (cell.x - S.size_x / 2) * S.resolution;
-  *y = S.origin_y + (cell.y - S.size_y / 2) * S.resolution;
+  if (S.cells != nullptr)
+  {
+    const int2 cell = S.cells[f];
+    *i = cell.x;
+    *j = cell.y;
+    *x = S.origin_x + (cell.x - S.size_x / 2) * S.resolution;
+    *y = S.origin_y + (cell.y - S.size_y / 2) * S.resolution;
+  }
+  else
+  {
+    const unsigned fi = f / (unsigned)S.n_j;
+    const int ci = S.i0 + (int)fi * S.stride, cj = S.j0 + (int)(f - fi * (unsigned)S.n_j) * S.stride;
+    *i = ci;
+    *j = cj;
+    *x = ci * S.resolution;
+    *y = cj * S.resolution;
+  }
   *th = (2.0 * 3.14159265358979323846 * (double)hh) / (double)S.headings - 3.14159265358979323846;
 }
 

@@ -682,6 +682,27 @@ class PointCloudScanner:
             self.e.check(status.value)
         return total
 
+    def searchSpace(self, headings, cell_stride=1):
+        """(candidates, columns) of searchPoses for the current 3-D map: candidates = columns of
+        Node3D::updateFreeSpaceIndices kept by cell_stride x headings, what a caller splits into ranges."""
+        total, cols = C.c_longlong(), C.c_int()
+        self.e.check(self.e.lib.bpf_cloud_search_space(self.e.h, int(headings), int(cell_stride), C.byref(total),
+                                                       C.byref(cols)))
+        return total.value, cols.value
+
+    def searchPoses(self, data, headings, cell_stride, k, first=0, count=-1):
+        """NOT a reference method: every column of the 3-D map's rectangle (every cell_stride-th in i and j) at
+        `headings` headings scored against the cloud `data` on the device, the best k of candidates first ..
+        first + count - 1 as a POSE_HIT_DTYPE array (score descending, equal scores by candidate).  See
+        bpf_cloud_search_poses in include/badger_pf.h."""
+        hits = np.zeros(max(int(k), 1), dtype=POSE_HIT_DTYPE)
+        n = C.c_int()
+        pts = data.points_
+        self.e.check(self.e.lib.bpf_cloud_search_poses(
+            self.e.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], int(headings), int(cell_stride),
+            int(first), int(count), int(k), hits.ctypes.data_as(C.POINTER(_lib.PoseHit)), C.byref(n)))
+        return hits[:n.value]
+
 
 def uniform_pose_retries(threshold, multiplier):
     """Trials every call of Node::uniformPoseGenerator rejects under POSE_CHECK_AS_REFERENCE (the reference's score

@@ -7,6 +7,9 @@
 //   badger_amcl_amd::ParticleFilter    <- ParticleFilter    (include/amcl/pf/particle_filter.h:92-184)
 //   badger_amcl_amd::PFSample / PFSampleSet                 (include/amcl/pf/particle_filter.h:41-87)
 //   badger_amcl_amd::OdomData / Odom   <- OdomData / Odom   (include/amcl/sensors/odom.h:43-90)
+//   badger_amcl_amd::OctoMap           <- OctoMap           (include/amcl/map/octomap.h:96-110, the LUT state)
+//   badger_amcl_amd::PointCloudData    <- PointCloudData    (include/amcl/sensors/point_cloud_scanner.h:45-51)
+//   badger_amcl_amd::PointCloudScanner <- PointCloudScanner (include/amcl/sensors/point_cloud_scanner.h:53-120)
 //   badger_amcl_amd::ShardedParticleFilter       one rank of a filter sharded over several engines (one process each)
 //   badger_amcl_amd::LocalShardedParticleFilter  all ranks of it in this process (bpf_shard_connect_local)
 //
@@ -463,6 +466,151 @@ public:
 private:
   std::shared_ptr<Engine> e_;
   std::shared_ptr<OccupancyMap> map_;
+  int max_beams_ = 0;
+};
+
+// LUT state of the reference's OctoMap (include/amcl/map/octomap.h:96-110): pose_indices_, distance_ratios_ and the
+// cropped cell bounds.  Building it from an octree is the caller's job: either the finished LUT is adopted, or the
+// engine builds it from the occupied voxels' indices.
+class OctoMap
+{
+public:
+  OctoMap(std::shared_ptr<Engine> e, double resolution) : e_(std::move(e)), resolution_(resolution) {}
+  // adopt a host-built LUT: pose_indices (one per column of the bounds, j-major) and distance_ratios
+  void setDistancesLUT(const std::vector<uint32_t>& pose_indices, const std::vector<uint8_t>& distance_ratios,
+                       const std::array<int, 3>& min_cells, const std::array<int, 3>& max_cells,
+                       double max_distance_to_object)
+  {
+    e_->check(bpf_map3d_set(e_->get(), pose_indices.data(), pose_indices.size(), distance_ratios.data(),
+                            distance_ratios.size(), min_cells.data(), max_cells.data(), resolution_,
+                            max_distance_to_object));
+    adopt(min_cells, max_cells, max_distance_to_object);
+  }
+  // OctoMap::updateDistancesLUT (octomap.cpp:175-333) from the occupied voxels' indices, i j k packed, in octree leaf
+  // order
+  void updateDistancesLUT(const std::vector<int>& occupied_ijk, const std::array<int, 3>& min_cells,
+                          const std::array<int, 3>& max_cells, double max_distance_to_object)
+  {
+    e_->check(bpf_map3d_build_distances_lut(e_->get(), occupied_ijk.data(), occupied_ijk.size() / 3, min_cells.data(),
+                                            max_cells.data(), resolution_, max_distance_to_object));
+    adopt(min_cells, max_cells, max_distance_to_object);
+  }
+  // pose_indices_ and distance_ratios_ as the engine holds them
+  void getDistancesLUT(std::vector<uint32_t>* pose_indices, std::vector<uint8_t>* distance_ratios)
+  {
+    size_t n_pose = 0, n_ratios = 0;
+    e_->check(bpf_map3d_get_distances_lut(e_->get(), nullptr, 0, &n_pose, nullptr, 0, &n_ratios));
+    pose_indices->resize(n_pose);
+    distance_ratios->resize(n_ratios);
+    e_->check(bpf_map3d_get_distances_lut(e_->get(), pose_indices->data(), n_pose, nullptr, distance_ratios->data(),
+                                          n_ratios, nullptr));
+  }
+  double getMaxDistanceToObject() const { return max_dist_; }
+  double getResolution() const { return resolution_; }
+  std::array<int, 3> getMinCells() const { return min_cells_; }
+  std::array<int, 3> getMaxCells() const { return max_cells_; }
+
+private:
+  void adopt(const std::array<int, 3>& min_cells, const std::array<int, 3>& max_cells, double max_dist)
+  {
+    min_cells_ = min_cells;
+    max_cells_ = max_cells;
+    max_dist_ = max_dist;
+  }
+  std::shared_ptr<Engine> e_;
+  double resolution_;
+  double max_dist_ = 0;
+  std::array<int, 3> min_cells_{}, max_cells_{};
+};
+
+// include/amcl/sensors/point_cloud_scanner.h:45-51; points_: packed float xyz in the scanner frame
+struct PointCloudData
+{
+  std::vector<float> points_;
+  int pointCount() const { return (int)(points_.size() / 3); }
+};
+
+// include/amcl/sensors/point_cloud_scanner.h:53-120
+class PointCloudScanner
+{
+public:
+  explicit PointCloudScanner(std::shared_ptr<Engine> e) : e_(std::move(e)) {}
+  void init(int max_beams, std::shared_ptr<OctoMap> map)
+  {
+    max_beams_ = max_beams;
+    map_ = std::move(map);
+    e_->check(bpf_cloud_init(e_->get(), max_beams));
+  }
+  void setPointCloudModel(double z_hit, double z_rand, double sigma_hit)
+  {
+    e_->check(bpf_cloud_set_model(e_->get(), z_hit, z_rand, sigma_hit));
+  }
+  void setPointCloudModelGompertz(double z_hit, double z_rand, double sigma_hit, double gompertz_a, double gompertz_b,
+                                  double gompertz_c, double input_shift, double input_scale, double output_shift)
+  {
+    e_->check(bpf_cloud_set_model_gompertz(e_->get(), z_hit, z_rand, sigma_hit, gompertz_a, gompertz_b, gompertz_c,
+                                           input_shift, input_scale, output_shift));
+  }
+  void setMapFactors(double off_map_factor, double non_free_space_factor, double non_free_space_radius)
+  {
+    e_->check(bpf_cloud_set_map_factors(e_->get(), off_map_factor, non_free_space_factor, non_free_space_radius));
+  }
+  // translation and rotation (quaternion x y z w) of the scanner in the robot's footprint frame
+  void setPointCloudScannerToFootprintTF(const std::array<double, 3>& xyz, const std::array<double, 4>& quat_xyzw)
+  {
+    e_->check(bpf_cloud_set_scanner_to_footprint_tf(e_->get(), xyz.data(), quat_xyzw.data()));
+  }
+
+  // PointCloudScanner::updateSensor(pf, data): false and no effect when max_beams_ < 2
+  bool updateSensor(std::shared_ptr<ParticleFilter> pf, std::shared_ptr<PointCloudData> data)
+  {
+    if (max_beams_ < 2)
+      return false;
+    e_->check(bpf_pf_update_sensor_cloud(e_->get(), data->points_.data(), data->pointCount()));
+    (void)pf;
+    return true;
+  }
+  // PointCloudScanner::applyModelToSampleSet(data, set) on a host-resident set
+  double applyModelToSampleSet(std::shared_ptr<PointCloudData> data, std::shared_ptr<PFSampleSet> set)
+  {
+    int status = BPF_OK;
+    const double total = bpf_cloud_apply_model_to_sample_set(e_->get(), reinterpret_cast<double*>(set->samples.data()),
+                                                             set->sample_count, data->points_.data(),
+                                                             data->pointCount(), &status);
+    e_->check(status);
+    return total;
+  }
+
+  // NOT a reference method (bpf_cloud_search_poses): every column of the 3-D map's rectangle (every cell_stride-th in
+  // i and j) at `headings` headings scored against `data` on the device; the best k of candidates first ..
+  // first + count - 1 (count = -1: to the end), score descending, equal scores by candidate.  A Node3D's global
+  // localisation turns the hits into a sample set (ParticleFilter::initWithSamples).
+  std::vector<bpf_pose_hit> searchPoses(std::shared_ptr<PointCloudData> data, int headings, int cell_stride, int k,
+                                        long long first = 0, long long count = -1)
+  {
+    std::vector<bpf_pose_hit> hits((size_t)(k > 0 ? k : 1));
+    int n = 0;
+    e_->check(bpf_cloud_search_poses(e_->get(), data->points_.data(), data->pointCount(), headings, cell_stride, first,
+                                     count, k, hits.data(), &n));
+    hits.resize((size_t)n);
+    return hits;
+  }
+  // candidates (columns kept by cell_stride x headings) of searchPoses: what a caller splits into ranges
+  long long searchSpace(int headings, int cell_stride = 1, int* columns_out = nullptr)
+  {
+    long long total = 0;
+    e_->check(bpf_cloud_search_space(e_->get(), headings, cell_stride, &total, columns_out));
+    return total;
+  }
+  // the best k of the hit lists of disjoint ranges, in searchPoses' order (host code, no engine)
+  static std::vector<bpf_pose_hit> mergePoseHits(const std::vector<std::vector<bpf_pose_hit>>& lists, int k)
+  {
+    return PlanarScanner::mergePoseHits(lists, k);
+  }
+
+private:
+  std::shared_ptr<Engine> e_;
+  std::shared_ptr<OctoMap> map_;
   int max_beams_ = 0;
 };
 

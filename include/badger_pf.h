@@ -1170,6 +1170,44 @@ int bpf_pose_search_merge(const bpf_pose_hit* lists, const int* list_lengths, in
 /* candidates scored per window, an internal constant the tests size their cases from; needs no engine */
 int bpf_pose_search_window(void);
 
+/* The same search with the 3-D map and the cloud scanner: Node3D's global localisation without the lottery over the
+ * columns of the map's bounding rectangle.  NOT a reference call (parity unpinned by construction).
+ *
+ * Column list C: Node3D::updateFreeSpaceIndices (node_3d.cpp:306-318) for the current 3-D map -- every column (i, j)
+ * with min_i <= i < max_i and min_j <= j < max_j of its cell bounds, i outer, j inner.  cell_stride s >= 1 keeps the
+ * columns whose i and j are both divisible by s (the bounds may be negative: i0 = the first multiple of s that is
+ * >= min_i, likewise j0), in the same order: C_s, n_i x n_j columns.  C_s is arithmetic, never a list.
+ * Candidate c in [0, |C_s| * headings) is column f = c / headings at heading h = c % headings, with
+ *   (i, j) = (i0 + (f / n_j) * s, j0 + (f % n_j) * s),
+ *   x = i * resolution, y = j * resolution   (OctoMap::convertMapToWorld, octomap.cpp:83-95: one double multiply each),
+ *   theta = (2.0 * pi * h) / headings - pi   (pi = 3.14159265358979323846, evaluated in double as written).
+ * Its score is the weight of the one-sample set {pose, 1.0} after PointCloudScanner::applyModelToSampleSet against
+ * the n_points packed float xyz triples given here -- exactly what bpf_cloud_apply_model_to_sample_set returns for
+ * that sample --, under the cloud model, off_map_factor and scanner-to-footprint tf configured on the engine; with
+ * cloud max_beams < 2 that is 1.0.  The points are taken as given: decimation (bpf_wire_decimate_cloud) stays with the
+ * caller, as at bpf_cloud_apply_model_to_sample_set.
+ *
+ * Result: the best min(k, count) candidates of [first, first + count), by score descending, equal scores by
+ * candidate ascending; a NaN score ranks below every number.  count = -1: to the end of the space.  The rows are
+ * bpf_pose_hit (i, j = the column's cell indices); lists of disjoint ranges merge with bpf_pose_search_merge.
+ * Limits: a cloud and the outputs non-null, n_points >= 1, 1 <= k <= 1024, headings >= 1, cell_stride >= 1 and
+ * first / count inside the space, otherwise BPF_ERR_INVALID_ARGUMENT; |C_s| * headings > 2^31 - 1 returns
+ * BPF_ERR_CAPACITY before anything is launched.  Bounds or a stride that leave no column give *n_hits_out = 0 and
+ * BPF_OK.
+ *
+ * The call needs the 3-D map and a cloud model (BPF_ERR_NOT_CONFIGURED without them, also when only the planar scanner
+ * is configured); it needs no filter and leaves one as it found it: sets, weights and the caches behind them, the
+ * drand48 state, w_slow / w_fast, the scan remembered for the pose check, the lazy statistics, and what describes the
+ * engine's last scoring call (evaluations, bpf_cloud_last_form, last_status, the profile: the search's launches are
+ * not timed).  The cloud and the term table are staged once per call; candidates are generated, scored and selected on
+ * the device in windows of bpf_pose_search_window() candidates, all enqueued back to back; the host waits once before
+ * the first launch (for the staging buffers) and once for the rows. */
+int bpf_cloud_search_poses(bpf_engine* e, const float* points_xyz, int n_points, int headings, int cell_stride,
+                           long long first, long long count, int k, bpf_pose_hit* hits_out, int* n_hits_out);
+/* |C_s| * headings for the current 3-D map (needs the map only): what a caller splits into ranges (the product
+ * itself, also when it is past the limit of a search); *columns_out = |C_s| */
+int bpf_cloud_search_space(bpf_engine* e, int headings, int cell_stride, long long* candidates_out, int* columns_out);
+
 /* ------------------------------------------------------------------ measurement */
 /* free / total device memory as hipMemGetInfo reports it (diagnostic; used by the leak test) */
 int bpf_device_memory_info(int device_ordinal, size_t* free_bytes, size_t* total_bytes);
