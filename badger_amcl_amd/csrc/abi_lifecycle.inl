@@ -22,6 +22,7 @@ int bpf_create(int device_ordinal, bpf_engine** out)
     return BPF_ERR_HIP;
   }
   e->stream = e->own_stream;
+  e->stage_on_host = getenv("BPF_STAGE_ON_HOST") != nullptr;  // (A/B runs of tools that set no options)
   lcg_tables(e->jump);
   *out = e;
   return BPF_OK;

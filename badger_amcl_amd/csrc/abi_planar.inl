@@ -183,7 +183,7 @@ int apply_model_records(bpf_engine* e, double* samples, int n, int set_converged
   e->weights_overwritten();
   StagedSlot s;
   FieldScan fs;
-  H2D_OR_RETURN(stage_field_scan(e, ranges, angles, rc, range_max, &s, &fs));
+  H2D_OR_RETURN(stage_field_scan(e, ranges, angles, rc, range_max, &s, &fs, nullptr, true));  // (no prep launch)
   auto bail = [e](int rcode) { return seam_bail(e, rcode); };
   e->evals_last = (long long)n * fs.n_valid;
   const unsigned long long gen = ++e->seam_generation;

@@ -135,11 +135,14 @@ struct FieldScan
   int n_valid = 0;             // beams that pass the range_max / NaN tests
   int n_staged = 0;            // of those, the ones uploaded (all, or the kept ones of beam skipping)
   bool copy_pending = false;   // pinned staging not yet copied to the device slot
+  bool ranges_staged = false;  // the pinned slot holds the decimated ranges (8 B per beam), not the end points: the
+                               // prep launch forms them (copy_pending says whether that is still to come)
+  int step = 1;                // decimation: staged beam k has bearing k * step
   int n_always_off = 0;        // valid beams too long / non-finite to stage: off the map for every pose
   double off_map_term = 0.0;   // table[K]
   int n_slots = 0;             // beam_ind range of the prob model
   std::vector<int> slot_of;    // staged beam -> beam_ind
-  size_t beams_off = 0, table_off = 0, bytes = 0;
+  size_t beams_off = 0, bytes = 0;  // the beams in the slot (the term table is e->d_term_table)
   int table_len = 0;
 };
 
@@ -261,6 +264,11 @@ struct bpf_engine
   // only on the model parameters, range_max and the map)
   std::vector<double> trig_angles, trig_cos, trig_sin;
   std::vector<double> term_table;
+  // their device copies: cos then sin, rc doubles each (for the prep launch that forms the end points itself), and the
+  // term table every scoring launch reads; uploaded in stream order when the host cache changes
+  DevBuf<double> d_trig, d_term_table;
+  bool trig_on_device = false, term_on_device = false;
+  bool stage_on_host = false;  // BPF_OPT_STAGE_ON_HOST: the end points always formed by the host
   struct TermKey
   {
     int model = -1, map_version = -1;

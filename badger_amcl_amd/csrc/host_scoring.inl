@@ -59,21 +59,40 @@ int acquire_slot(bpf_engine* e, size_t bytes, StagedSlot* out)
   return BPF_OK;
 }
 
+// The cosines and sines of the scan's bearings, kept under the content of `angles`.
+void trig_cache(bpf_engine* e, const double* angles, int rc)
+{
+  if ((int)e->trig_angles.size() == rc && std::memcmp(e->trig_angles.data(), angles, (size_t)rc * sizeof(double)) == 0)
+    return;
+  e->trig_angles.assign(angles, angles + rc);
+  e->trig_cos.resize(rc);
+  e->trig_sin.resize(rc);
+  for (int i = 0; i < rc; ++i)
+  {
+    e->trig_cos[i] = std::cos(angles[i]);
+    e->trig_sin[i] = std::sin(angles[i]);
+  }
+  e->trig_on_device = false;
+}
+
+// Their device copy for the prep launch that forms the end points (cos first, then sin), brought up to date in stream
+// order: the launches that read the previous content are ahead of the copy, the prep launch of this update behind it.
+int trig_to_device(bpf_engine* e)
+{
+  if (e->trig_on_device)
+    return BPF_OK;
+  const size_t rc = e->trig_cos.size();
+  HIPCHK(e, e->d_trig.reserve(2 * rc));
+  H2D_OR_RETURN(h2d_from_host(e, e->d_trig.p, e->trig_cos.data(), rc * sizeof(double), e->stream));
+  H2D_OR_RETURN(h2d_from_host(e, e->d_trig.p + rc, e->trig_sin.data(), rc * sizeof(double), e->stream));
+  e->trig_on_device = true;
+  return BPF_OK;
+}
+
 // The end points of every step-th beam in the scanner's frame, in cells (e->stage_bx / stage_by), from the cached
 // cosines and sines of the scan's angles.  No test and no branch per beam: the compiler vectorises the loops.
-void stage_end_points(bpf_engine* e, const double* ranges, const double* angles, int rc, int step, int m_beams)
+void stage_end_points(bpf_engine* e, const double* ranges, int rc, int step, int m_beams)
 {
-  if ((int)e->trig_angles.size() != rc || std::memcmp(e->trig_angles.data(), angles, (size_t)rc * sizeof(double)) != 0)
-  {
-    e->trig_angles.assign(angles, angles + rc);
-    e->trig_cos.resize(rc);
-    e->trig_sin.resize(rc);
-    for (int i = 0; i < rc; ++i)
-    {
-      e->trig_cos[i] = std::cos(angles[i]);
-      e->trig_sin[i] = std::sin(angles[i]);
-    }
-  }
   if ((int)e->stage_bx.size() < m_beams)
   {
     e->stage_bx.resize(m_beams);
@@ -98,24 +117,11 @@ void stage_end_points(bpf_engine* e, const double* ranges, const double* angles,
     }
 }
 
-// The per-level term table of the configured model (K levels and the off-map entry) into `table`; kept between
-// updates under the key of what it depends on.
-void field_term_table(bpf_engine* e, double range_max, double* table)
+// The table's entries, with the same libm expressions as the reference.
+void fill_term_table(const bpf_engine* e, double range_max, double* table)
 {
   const PlanarModel& pm = e->pm;
   const int K = e->map.n_levels;
-  bpf_engine::TermKey key;
-  key.model = pm.model;
-  key.map_version = e->map_version;
-  key.z_hit = pm.z_hit;
-  key.z_rand = pm.z_rand;
-  key.sigma = pm.sigma_hit;
-  key.range_max = range_max;
-  if (key == e->term_key && (int)e->term_table.size() == K + 1)
-  {
-    std::memcpy(table, e->term_table.data(), (size_t)(K + 1) * sizeof(double));
-    return;
-  }
   const double denom = 2 * pm.sigma_hit * pm.sigma_hit;
   const double rand_mult = 1.0 / range_max;
   for (int k = 0; k <= K; ++k)
@@ -148,14 +154,44 @@ void field_term_table(bpf_engine* e, double range_max, double* table)
       table[k] = std::log(pz);
     }
   }
-  e->term_table.assign(table, table + K + 1);
-  e->term_key = key;
+}
+
+// The per-level term table of the configured model (K levels and the off-map entry): e->term_table and its device copy
+// e->d_term_table, which every scoring launch reads; both kept between updates under the key of what they depend on.
+// A new table goes up in stream order, behind the launches that read the previous one.
+int field_term_table(bpf_engine* e, double range_max)
+{
+  const PlanarModel& pm = e->pm;
+  const int K = e->map.n_levels;
+  bpf_engine::TermKey key;
+  key.model = pm.model;
+  key.map_version = e->map_version;
+  key.z_hit = pm.z_hit;
+  key.z_rand = pm.z_rand;
+  key.sigma = pm.sigma_hit;
+  key.range_max = range_max;
+  if (!(key == e->term_key && (int)e->term_table.size() == K + 1))
+  {
+    e->term_table.resize((size_t)K + 1);
+    fill_term_table(e, range_max, e->term_table.data());
+    e->term_key = key;
+    e->term_on_device = false;
+  }
+  if (!e->term_on_device)
+  {
+    HIPCHK(e, e->d_term_table.reserve((size_t)K + 1));
+    H2D_OR_RETURN(h2d_from_host(e, e->d_term_table.p, e->term_table.data(), ((size_t)K + 1) * sizeof(double), e->stream));
+    e->term_on_device = true;
+  }
+  return BPF_OK;
 }
 
 // Host half of calcLikelihoodFieldModel{,Prob,Gompertz}: beam decimation and validity
 // (planar_scanner.cpp:265-282, :339-343,410-425, :578-597) and the per-level term table.
+// host_only: the caller's launch has no prep launch to form the end points (the HOST_RECORDS form).
 int stage_field_scan(bpf_engine* e, const double* ranges, const double* angles, int rc, double range_max,
-                     StagedSlot* slot_out, FieldScan* fs, const std::vector<uint8_t>* keep_slot = nullptr)
+                     StagedSlot* slot_out, FieldScan* fs, const std::vector<uint8_t>* keep_slot = nullptr,
+                     bool host_only = false)
 {
   const PlanarModel& pm = e->pm;
   int step;
@@ -167,89 +203,121 @@ int stage_field_scan(bpf_engine* e, const double* ranges, const double* angles, 
     step = 1;
   const int K = e->map.n_levels;
   fs->table_len = K + 1;
-  // This runs between the launch that wrote the poses and the prep launch, with the GPU waiting (9 us for 1081 beams as
-  // one loop with its tests and push_backs): the products and the two divisions per beam first, for every decimated
-  // beam and without a branch (the compiler vectorises it), then the tests, writing the kept beams straight into the
-  // pinned slot: 4.7 us.  Same expressions, same bits.
+  fs->step = step;
+  fs->ranges_staged = false;
   const int m_beams = (rc + step - 1) / step;
-  stage_end_points(e, ranges, angles, rc, step, m_beams);
-  // the usual scan: every decimated beam is a valid return of sane length -- one branch-free pass finds that out, and
-  // the kept beams are then all of them, in order (the loop with its tests below costs ~2 us per 1 000 beams with the
-  // GPU waiting)
-  bool all_kept = keep_slot == nullptr && m_beams <= kMaxBeams;
-  if (all_kept)
-  {
-    int okc = 1;
-    const double* bx = e->stage_bx.data();
-    const double* by = e->stage_by.data();
-    for (int k = 0, i = 0; i < rc; i += step, ++k)
-      okc &= (int)(ranges[i] < range_max) & (int)(std::fabs(bx[k]) < 268435456.0) & (int)(std::fabs(by[k]) < 268435456.0);
-    all_kept = okc != 0;  // (a NaN range fails the first test, a NaN or huge product the others)
-  }
+  trig_cache(e, angles, rc);
   fs->beams_off = 0;
   StagedSlot& s = *slot_out;
-  int rcode = acquire_slot(e, (((size_t)m_beams * sizeof(double2) + 255) & ~(size_t)255) +
-                                  (size_t)fs->table_len * sizeof(double), &s);  // room for every decimated beam
+  int rcode = acquire_slot(e, (size_t)m_beams * sizeof(double2), &s);  // room for every decimated beam
   if (rcode != BPF_OK)
     return rcode;
-  double2* out = reinterpret_cast<double2*>(s->host.p + fs->beams_off);
   fs->slot_of.clear();
-  fs->slot_of.reserve((size_t)m_beams);
   fs->n_valid = 0;
   fs->n_always_off = 0;
   int slot = 0, n_out = 0;
-  if (all_kept)
+  bool in_order = false;
+  // All of this runs between the launch that wrote the poses and the prep launch, with the GPU waiting.  The usual
+  // scan -- every decimated beam a valid return of sane length -- therefore leaves the host with one branch-free pass
+  // (the compiler vectorises it) that moves the decimated ranges into the pinned slot and finds out that the scan is
+  // such a one; the prep launch forms the end points (stage_scan, kernels_score.hpp).  |cos|, |sin| <= 1, so
+  // |fl(r c)| <= |r| and, the division being monotonic, |fl(fl(r c) / res)| <= fl(max |r| / res): below 2^28 cells that
+  // bounds every end point, and the magnitude tests of the host path below cannot fail.  The beams kept are the same.
+  bool on_device = !e->stage_on_host && !host_only && keep_slot == nullptr && m_beams <= kMaxBeams;
+  if (on_device)
   {
+    double* out_r = reinterpret_cast<double*>(s->host.p);
+    int okc = 1;
+    double amax = 0.0;
+    for (int k = 0, i = 0; i < rc; i += step, ++k)
+    {
+      const double r = ranges[i];
+      const double a = std::fabs(r);
+      out_r[k] = r;
+      okc &= (int)(r < range_max);  // (a NaN fails it)
+      amax = a > amax ? a : amax;
+    }
+    on_device = okc != 0 && amax / e->map.resolution < 268435456.0;
+  }
+  if (on_device)
+  {
+    H2D_OR_RETURN(trig_to_device(e));
+    fs->ranges_staged = in_order = true;
+    fs->n_valid = n_out = slot = m_beams;
+  }
+  else
+  {
+    // The host forms the end points (4.7 us for 1081 beams): the products and the two divisions per beam first, for
+    // every decimated beam and without a branch, then the tests, writing the kept beams straight into the pinned slot.
+    stage_end_points(e, ranges, rc, step, m_beams);
+    double2* out = reinterpret_cast<double2*>(s->host.p + fs->beams_off);
     const double* bx = e->stage_bx.data();
     const double* by = e->stage_by.data();
-    for (int k = 0; k < m_beams; ++k)
+    // a scan whose beams are all kept is found out by one branch-free pass (the loop with its tests below costs ~2 us
+    // per 1 000 beams)
+    bool all_kept = keep_slot == nullptr && m_beams <= kMaxBeams;
+    if (all_kept)
     {
-      out[k].x = bx[k];
-      out[k].y = by[k];
+      int okc = 1;
+      for (int k = 0, i = 0; i < rc; i += step, ++k)
+        okc &= (int)(ranges[i] < range_max) & (int)(std::fabs(bx[k]) < 268435456.0) & (int)(std::fabs(by[k]) < 268435456.0);
+      all_kept = okc != 0;  // (a NaN range fails the first test, a NaN or huge product the others)
     }
+    if (all_kept)
+    {
+      for (int k = 0; k < m_beams; ++k)
+      {
+        out[k].x = bx[k];
+        out[k].y = by[k];
+      }
+      in_order = true;
+      fs->n_valid = n_out = slot = m_beams;
+    }
+    else
+      fs->slot_of.reserve((size_t)m_beams);
+    for (int i = 0; !all_kept && i < rc; i += step, ++slot)
+    {
+      const double r = ranges[i];
+      if (r >= range_max)
+        continue;
+      if (r != r)
+        continue;
+      ++fs->n_valid;
+      if (keep_slot && !(slot < (int)keep_slot->size() && (*keep_slot)[slot]))
+        continue;
+      const double b_x = bx[slot], b_y = by[slot];
+      // a non-finite or absurdly long beam (> 2^28 cells) ends off the map for every pose in the
+      // reference ((int) of a NaN or huge double is INT_MIN on x86): it is not staged, its constant
+      // off-map term is added in the epilogue instead
+      if (!(std::fabs(b_x) < 268435456.0 && std::fabs(b_y) < 268435456.0))
+      {
+        ++fs->n_always_off;
+        continue;
+      }
+      if (n_out < kMaxBeams)
+      {
+        out[n_out].x = b_x;
+        out[n_out].y = b_y;
+      }
+      ++n_out;
+      fs->slot_of.push_back(slot);
+    }
+  }
+  if (in_order)  // every decimated beam staged: beam k is slot k
+  {
     fs->slot_of.resize((size_t)m_beams);
     for (int k = 0; k < m_beams; ++k)
       fs->slot_of[(size_t)k] = k;
-    fs->n_valid = n_out = slot = m_beams;
-  }
-  for (int i = 0; !all_kept && i < rc; i += step, ++slot)
-  {
-    const double r = ranges[i];
-    if (r >= range_max)
-      continue;
-    if (r != r)
-      continue;
-    ++fs->n_valid;
-    if (keep_slot && !(slot < (int)keep_slot->size() && (*keep_slot)[slot]))
-      continue;
-    const double b_x = e->stage_bx[slot], b_y = e->stage_by[slot];
-    // a non-finite or absurdly long beam (> 2^28 cells) ends off the map for every pose in the
-    // reference ((int) of a NaN or huge double is INT_MIN on x86): it is not staged, its constant
-    // off-map term is added in the epilogue instead
-    if (!(std::fabs(b_x) < 268435456.0 && std::fabs(b_y) < 268435456.0))
-    {
-      ++fs->n_always_off;
-      continue;
-    }
-    if (n_out < kMaxBeams)
-    {
-      out[n_out].x = b_x;
-      out[n_out].y = b_y;
-    }
-    ++n_out;
-    fs->slot_of.push_back(slot);
   }
   fs->n_slots = slot;
   fs->n_staged = n_out;
   if (fs->n_staged > kMaxBeams)  // (the caller's guard hands the slot back)
     return e->fail(BPF_ERR_CAPACITY, "more than 4096 beams per scan after decimation");
-  fs->table_off = ((size_t)fs->n_staged * sizeof(double2) + 255) & ~(size_t)255;
-  fs->bytes = fs->table_off + (size_t)fs->table_len * sizeof(double);
-  double* table = reinterpret_cast<double*>(s->host.p + fs->table_off);
-  field_term_table(e, range_max, table);
-  fs->off_map_term = table[K];
-  // the copy to the device slot is done by k_field_prep (launch_field) unless the staging block is
-  // larger than what its grid covers
+  fs->bytes = (size_t)fs->n_staged * sizeof(double2);
+  H2D_OR_RETURN(field_term_table(e, range_max));
+  fs->off_map_term = e->term_table[(size_t)K];
+  // the prep launch (launch_field) forms the end points in the device slot, or copies the host's there unless the
+  // staging block is larger than what its grid covers
   fs->copy_pending = true;
   return BPF_OK;
 }
@@ -282,7 +350,7 @@ FieldScoreArgs field_args(const bpf_engine* e, ParticlesDev p, int n, const Scan
   A.n = n;
   A.beams = reinterpret_cast<const double2*>(s->dev.p + fs.beams_off);
   A.n_beams = fs.n_staged;
-  A.table = reinterpret_cast<const double*>(s->dev.p + fs.table_off);
+  A.table = e->d_term_table.p;
   A.table_len = fs.table_len;
   A.map = e->map;
   A.sp_x = e->pm.pose[0];
@@ -319,10 +387,11 @@ int field_prep(bpf_engine* e, int n, ScanSlot* s, const FieldScan& fs, const Fie
   A->prep = e->d_prep.p;
   const int n16 = (int)((fs.bytes + 15) / 16);
   uint4* dev16 = reinterpret_cast<uint4*>(s->dev.p);
+  const bool pending = fs.copy_pending && n16 > 0;  // (a scan without a valid beam stages nothing)
   if (form == FieldForm::HOST_RECORDS)
   {
-    // no prep launch to ride on: a small copy launch brings the scan's staging block over
-    if (fs.copy_pending)
+    // no prep launch to ride on (its scan is staged host_only): a small copy launch brings the staging block over
+    if (pending)
     {
       ProfScope pa(e, BPF_K_SCORE_AUX);
       hipLaunchKernelGGL(k_copy16, dim3(blocks_for(n16, 256)), dim3(256), 0, e->stream,
@@ -330,11 +399,27 @@ int field_prep(bpf_engine* e, int n, ScanSlot* s, const FieldScan& fs, const Fie
     }
     return BPF_OK;
   }
-  const bool ride = fs.copy_pending && n16 <= prep_blocks * 256;
-  if (fs.copy_pending && !ride)
+  ScanStage stage{};
+  if (pending && fs.ranges_staged)
+  {
+    // the end points are formed by the launch, a thread taking every (grid size)-th beam
+    stage.ranges = reinterpret_cast<const double*>(s->host.p);
+    stage.tc = e->d_trig.p;
+    stage.ts = e->d_trig.p + e->trig_cos.size();
+    stage.beams = reinterpret_cast<double2*>(s->dev.p + fs.beams_off);
+    stage.n_beams = fs.n_staged;
+    stage.step = fs.step;
+    stage.resolution = e->map.resolution;
+  }
+  else if (pending && n16 <= prep_blocks * 256)
+  {
+    stage.src = reinterpret_cast<const uint4*>(s->host.p);
+    stage.dst = dev16;
+    stage.n16 = n16;
+  }
+  else if (pending)
     HIPCHK(e, hipMemcpyAsync(s->dev.p, s->host.p, fs.bytes, hipMemcpyHostToDevice, e->stream));
   ProfScope pa(e, BPF_K_SCORE_AUX);
-  const uint4* src = ride ? reinterpret_cast<const uint4*>(s->host.p) : static_cast<const uint4*>(nullptr);
   const ParticlesDev& p = A->p;
   if (form == FieldForm::TILE)
   {
@@ -355,7 +440,7 @@ int field_prep(bpf_engine* e, int n, ScanSlot* s, const FieldScan& fs, const Fie
     int* tile = cursor + kTileBins;
     int* perm = tile + n;
     hipLaunchKernelGGL(k_field_prep_tile, dim3(prep_blocks), dim3(256), 0, e->stream, p, n, e->map, A->sp_x, A->sp_y,
-                       A->sp_th, e->d_prep.p, tile, hist, hist_next, cursor, shift, txc, tyc, src, dev16, n16);
+                       A->sp_th, e->d_prep.p, tile, hist, hist_next, cursor, shift, txc, tyc, stage);
     hipLaunchKernelGGL(k_tile_scatter, dim3(prep_blocks), dim3(256), 0, e->stream, n, (const int*)tile,
                        (const int*)hist, cursor, (const double4*)e->d_prep.p, perm, e->d_prep_sorted.p);
     A->perm = perm;
@@ -363,13 +448,13 @@ int field_prep(bpf_engine* e, int n, ScanSlot* s, const FieldScan& fs, const Fie
   }
   else if (req.aos != nullptr)
     hipLaunchKernelGGL(k_field_prep_aos, dim3(prep_blocks), dim3(256), 0, e->stream, req.aos, p, n, e->map, A->sp_x,
-                       A->sp_y, A->sp_th, e->d_prep.p, src, dev16, n16);
+                       A->sp_y, A->sp_th, e->d_prep.p, stage);
   else if (e->window_enabled)
     hipLaunchKernelGGL(k_field_prep<true>, dim3(prep_blocks), dim3(256), 0, e->stream, p, n, e->map, A->sp_x, A->sp_y,
-                       A->sp_th, e->d_prep.p, e->d_prep_stats.p, src, dev16, n16);
+                       A->sp_th, e->d_prep.p, e->d_prep_stats.p, stage);
   else
     hipLaunchKernelGGL(k_field_prep<false>, dim3(prep_blocks), dim3(256), 0, e->stream, p, n, e->map, A->sp_x, A->sp_y,
-                       A->sp_th, e->d_prep.p, e->d_prep_stats.p, src, dev16, n16);
+                       A->sp_th, e->d_prep.p, e->d_prep_stats.p, stage);
   return BPF_OK;
 }
 

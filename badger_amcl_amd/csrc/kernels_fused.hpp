@@ -541,14 +541,16 @@ __device__ __forceinline__ void fused_stop_init(FusedStatics& S, const FusedLdsM
 {
   constexpr int W = kFusedWindow;
   const int tid = threadIdx.x;
-  for (int k = tid; k <= kFusedMaxBins; k += 1024)
-    S.limit[k] = (k <= window && !systematic) ? limit[k] : INT_MAX;
+  // (the limits last: their loads are waited for, and the clearing runs while they -- and whatever the caller has
+  // asked for in front of them -- are on their way)
   for (int s = tid; s < W; s += 1024)
     L.first[s] = INT_MAX;
   for (int s = tid; s < W / 32; s += 1024)
     S.nodelta[s] = 0u;
   for (int s = tid; s < 2 * W; s += 1024)
     L.hash[s] = INT_MAX;
+  for (int k = tid; k <= kFusedMaxBins; k += 1024)
+    S.limit[k] = (k <= window && !systematic) ? limit[k] : INT_MAX;
   if (tid == 0)
   {
     S.stop = INT_MAX;
@@ -670,7 +672,9 @@ __device__ __forceinline__ void fused_stop_rule(FusedStatics& S, const FusedLdsM
       unsigned h = (unsigned)((pk[q] * 0x9E3779B97F4A7C15ull) >> 40) & kHashMask;
       for (;;)
       {
-        int held = *reinterpret_cast<volatile int*>(&L.hash[h]);
+        // (an atomic load, not a volatile one: that would go out as a flat load, which waits for every global load the
+        // thread has in flight -- the poses -- and is the slower way into LDS)
+        int held = __hip_atomic_load(&L.hash[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (held == INT_MAX)
         {
           held = atomicCAS(&L.hash[h], INT_MAX, m);
@@ -679,7 +683,10 @@ __device__ __forceinline__ void fused_stop_rule(FusedStatics& S, const FusedLdsM
         }
         if (L.key[held] == pk[q])
         {
-          atomicMin(&L.hash[h], m);
+          // (a slot only ever goes down: behind an earlier draw there is nothing to do, and the ~64 draws per key of a
+          // converged window mostly find one -- same-address LDS atomics serialise)
+          if (held > m)
+            atomicMin(&L.hash[h], m);
           break;
         }
         h = (h + 1) & kHashMask;
@@ -1045,21 +1052,34 @@ __device__ __forceinline__ void resample_block_body(const ResampleBlockArgs& A)
   const long long shader_clk0 = clock64();
 
   // ================================================================== the last block: every draw of the window
-  // thread t owns draws m = 4t .. 4t + 3 from here on; their loads are in flight while the tables are cleared
+  // thread t owns draws m = 4t .. 4t + 3 from here on.  The stop rule reads the keys alone: they are asked for first
+  // and arrive while the tables are cleared (fused_stop_init ends with the wait for its own loads of the limits, which
+  // are behind them: loads return in issue order).  The poses are asked for behind that wait and stay in flight across
+  // the stop rule; the tail, behind fused_publish, is the first to need them, and it needs pose t, t + 1024, ... in
+  // thread t (its summation shape): those are the ones the thread loads, and they stay in its registers.  Every
+  // thread loads (past the window: the last draw again), so that the loads sit in straight-line code and the waits
+  // count them exactly.
   const int m_base = tid * Q;
   bool act[Q];
   unsigned long long pk[Q];
   double lx[Q], ly[Q];
+  static_assert(Q * 1024 == kFusedWindow, "thread t holds poses t + 1024 j, j < Q");
 #pragma unroll
   for (int q = 0; q < Q; ++q)
   {
-    const int m = m_base + q;
-    act[q] = m < A.window;
-    pk[q] = act[q] ? __hip_atomic_load(&A.keys[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : kKldEmpty;
-    lx[q] = act[q] ? __hip_atomic_load(&A.dst.x[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-    ly[q] = act[q] ? __hip_atomic_load(&A.dst.y[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+    act[q] = m_base + q < A.window;
+    const unsigned long long v =
+        __hip_atomic_load(&A.keys[min(m_base + q, A.window - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    pk[q] = act[q] ? v : kKldEmpty;
   }
   fused_stop_init(S, L, A.window, A.systematic, A.limit);
+#pragma unroll
+  for (int j = 0; j < Q; ++j)
+  {
+    const int i = min(tid + 1024 * j, A.window - 1);
+    lx[j] = __hip_atomic_load(&A.dst.x[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ly[j] = __hip_atomic_load(&A.dst.y[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   {
     bool bad_key = false;
 #pragma unroll
@@ -1069,8 +1089,6 @@ __device__ __forceinline__ void resample_block_body(const ResampleBlockArgs& A)
         const int m = m_base + q;
         bad_key |= pk[q] == kKldEmpty;
         L.key[m] = pk[q];
-        L.x[m] = lx[q];
-        L.y[m] = ly[q];
       }
     __syncthreads();  // S.bad = 0 is in place
     if (bad_key)
@@ -1088,17 +1106,19 @@ __device__ __forceinline__ void resample_block_body(const ResampleBlockArgs& A)
     fused_publish(A.result_host, A.generation, M, S.leaf, S.bins, status, S.levels);
 
   // ---- weights 1 / M (:409,458-462) and updateConverged (:170-220) in k_resample_tail_small's summation shape,
-  // from the poses staged in LDS
+  // from the poses in the thread's registers (M <= window: pose i = tid + 1024 j of the new set is draw i)
   if (status == 0)
   {
     const double weight = 1.0 / (double)M;
     double ax = 0.0, ay = 0.0;
-    for (int i = tid; i < M; i += 1024)
-    {
-      A.dst.w[i] = weight;
-      ax += L.x[i];
-      ay += L.y[i];
-    }
+#pragma unroll
+    for (int j = 0; j < Q; ++j)
+      if (tid + 1024 * j < M)
+      {
+        A.dst.w[tid + 1024 * j] = weight;
+        ax += lx[j];
+        ay += ly[j];
+      }
     ax = wave_sum(ax);
     ay = wave_sum(ay);
     double* s_px = reinterpret_cast<double*>(L.key);  // the keys are done with
@@ -1118,8 +1138,9 @@ __device__ __forceinline__ void resample_block_body(const ResampleBlockArgs& A)
     }
     const double mx = sxx / M, my = syy / M;
     int cnt = 0;
-    for (int i = tid; i < M; i += 1024)
-      if (fabs(L.x[i] - mx) <= A.thr && fabs(L.y[i] - my) <= A.thr)
+#pragma unroll
+    for (int j = 0; j < Q; ++j)
+      if (tid + 1024 * j < M && fabs(lx[j] - mx) <= A.thr && fabs(ly[j] - my) <= A.thr)
         cnt++;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1)

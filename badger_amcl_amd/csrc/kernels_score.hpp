@@ -163,6 +163,38 @@ __device__ __forceinline__ double4 field_prep_of(const MapDev& M, double px, dou
   return make_double4(Qx, Qy, sp.c, sp.s);
 }
 
+// What the prep launch carries for the scan (stage_field_scan): either the host-staged block, copied 16 bytes per
+// thread into the device slot (src != nullptr), or the decimated ranges in the pinned slot, from which the launch
+// forms the beams' end points in cells itself (ranges != nullptr).  Neither: nothing to do (already on the device).
+struct ScanStage
+{
+  const uint4* src;      // pinned staging block of n16 16-byte words ...
+  uint4* dst;            // ... and the device slot it goes to
+  int n16;
+  const double* ranges;  // pinned: range of decimated beam k
+  const double* tc;      // device: cos / sin of bearing i, beam k has bearing k * step
+  const double* ts;
+  double2* beams;        // device slot: B_k = r_k (cos, sin) / resolution
+  int n_beams;
+  int step;
+  double resolution;
+};
+
+// Thread q of the prep launch (`stride` threads in all) does its part of the staging.  The end points are the host's
+// expressions in the host's order (stage_end_points): an IEEE product and an IEEE division each, the same bits.
+__device__ __forceinline__ void stage_scan(const ScanStage& S, int q, int stride)
+{
+  if (S.src != nullptr && q < S.n16)
+    S.dst[q] = S.src[q];
+  if (S.ranges != nullptr)
+    for (int k = q; k < S.n_beams; k += stride)
+    {
+      const double r = S.ranges[k];
+      const size_t i = (size_t)k * (size_t)S.step;
+      S.beams[k] = make_double2((r * S.tc[i]) / S.resolution, (r * S.ts[i]) / S.resolution);
+    }
+}
+
 // One likelihood-field evaluation up to the cell: byte offset of the end point's LUT entry.
 // |B| < 2^28 (checked when the beam table is staged) and |Q| < 2^30 keep the sum inside int range,
 // so the conversion never saturates onto the map.

@@ -49,23 +49,17 @@ struct WindowPlan
 };
 
 // ---------------------------------------------------------------------------------------
-// The per-scan staging block (beam table + term table, ~25 KB, written by the host into pinned
-// memory) rides along: the first blocks copy it into the device slot the scoring kernel reads, which
-// saves a separate copy operation on the stream (stage_src == nullptr: already copied).
+// The per-scan staging rides along (stage_scan, kernels_score.hpp): the first threads form the beams' end points from
+// the ranges in the pinned slot, or copy the block the host staged there, into the device slot the scoring kernel
+// reads, which saves a separate copy operation on the stream.
 template <bool WITH_STATS>
 __global__ __launch_bounds__(256) void k_field_prep(ParticlesDev p, int n, MapDev M, double ax, double ay, double ath,
                                                    double4* __restrict__ prep, double* __restrict__ stats,
-                                                   const uint4* __restrict__ stage_src, uint4* __restrict__ stage_dst,
-                                                   int stage_n16)
+                                                   const ScanStage stage)
 {
   __shared__ double s_red[4][kPrepStats];
-  if (stage_src != nullptr)
-  {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q < stage_n16)
-      stage_dst[q] = stage_src[q];
-  }
   const int i = blockIdx.x * 256 + threadIdx.x;
+  stage_scan(stage, i, gridDim.x * 256);
   double v[kPrepStats] = { 0, 0, 0, 0, 0, 0, 0, 0 };
   if (i < n)
   {
@@ -99,12 +93,10 @@ __global__ __launch_bounds__(256) void k_field_prep(ParticlesDev p, int n, MapDe
 // along exactly as in k_field_prep.
 __global__ __launch_bounds__(256) void k_field_prep_aos(const double4* __restrict__ aos, ParticlesDev p, int n, MapDev M,
                                                        double ax, double ay, double ath, double4* __restrict__ prep,
-                                                       const uint4* __restrict__ stage_src,
-                                                       uint4* __restrict__ stage_dst, int stage_n16)
+                                                       const ScanStage stage)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (stage_src != nullptr && i < stage_n16)
-    stage_dst[i] = stage_src[i];
+  stage_scan(stage, i, gridDim.x * 256);
   if (i >= n)
     return;
   const double4 v = aos[i];
@@ -157,12 +149,10 @@ __global__ __launch_bounds__(256) void k_field_prep_tile(ParticlesDev p, int n, 
                                                         double4* __restrict__ prep, int* __restrict__ tile,
                                                         int* __restrict__ hist, int* __restrict__ hist_next,
                                                         int* __restrict__ cursor, int shift, int tx_count, int ty_count,
-                                                        const uint4* __restrict__ stage_src,
-                                                        uint4* __restrict__ stage_dst, int stage_n16)
+                                                        const ScanStage stage)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (stage_src != nullptr && i < stage_n16)
-    stage_dst[i] = stage_src[i];
+  stage_scan(stage, i, gridDim.x * 256);
   if (blockIdx.x == 0)
     for (int k = threadIdx.x; k < kTileBins; k += 256)
     {

@@ -39,6 +39,7 @@ OPT_KLD_LOCAL = 13
 OPT_TILE_SORT = 14
 OPT_HOST_DIRECT_PAGEABLE = 15  # pageable buffers straight to the HIP runtime (the caller promises they never move)
 OPT_FUSED_LDS_TREE = 16  # the LDS form of the single-block resample's histogram tree (tests)
+OPT_STAGE_ON_HOST = 17  # the host forms the scan's end points always (A/B switch of the device staging)
 CELL_FREE, CELL_UNKNOWN, CELL_OCCUPIED = -1, 0, 1
 
 

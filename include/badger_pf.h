@@ -343,6 +343,12 @@ enum
   BPF_OPT_FUSED_LDS_TREE = 16, /* default 0: the single-block resample grows a histogram tree of at most 64 keys in wave 0's
                                * registers (cross-lane ballots, no LDS traffic inside the level loop); 1 = the LDS form
                                * with atomics (a reference for tests).  Same tree, same results. */
+  BPF_OPT_STAGE_ON_HOST = 17, /* default 0: for the usual scan (every decimated beam shorter than range_max and than
+                               * 2^28 cells, no beam skipping mask) the host hands the decimated ranges over and the
+                               * scoring's prep launch forms the beams' end points; 1 = the host forms them always,
+                               * as it does for every other scan.  Same bits either way.  (BPF_STAGE_ON_HOST set in
+                               * the environment makes 1 the value an engine starts with: A/B runs of tools that set
+                               * no options.) */
   BPF_OPT_FUSED_RESAMPLE = 5  /* default 1: normalisation + CDF in one launch, and a resample whose candidate stream
                                * fits 4096 draws as one single-block launch (draws, KLD stop rule, weights,
                                * updateConverged); 0 = the separate launches with the host's ordered replay.
