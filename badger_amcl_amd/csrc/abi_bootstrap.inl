@@ -378,8 +378,7 @@ int bpf_shard_update_resample(bpf_engine* e, int* global_count_io, int* leaf_cou
   if (cdf_miss_out)
   {
     int flag = 0;
-    HIPCHK(e, hipMemcpyAsync(&flag, e->d_shard_flags.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    H2D_OR_RETURN(small_down_sync(e, &flag, (const int*)e->d_shard_flags.p, 1, e->stream));
     *cdf_miss_out = flag;
   }
   return BPF_OK;

@@ -144,9 +144,7 @@ int build_lut3d_device(bpf_engine* e, const int* occupied_ijk, size_t n_occupied
     HIPCHK(e, hipMemsetAsync(counter.p, 0, sizeof(unsigned long long), st));
     if (n)
       hipLaunchKernelGGL(k_count_valid_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, keys, n, counter.p);
-    HIPCHK(e, hipMemcpyAsync(out, counter.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(e, hipStreamSynchronize(st));
-    return BPF_OK;
+    return small_down_sync(e, out, (const unsigned long long*)counter.p, 1, st);
   };
   // ---- generation 0
   size_t n_entries = 0;
@@ -200,9 +198,10 @@ int build_lut3d_device(bpf_engine* e, const int* occupied_ijk, size_t n_occupied
     HIPCHK(e, ensure_tmp(bytes));
     HIPCHK(e, rocprim::exclusive_scan(tmp.p, bytes, pushed.p, position.p, 0, n_att, rocprim::plus<int>(), st));
     int last[2] = { 0, 0 };
-    HIPCHK(e, hipMemcpyAsync(&last[0], position.p + (n_att - 1), sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(e, hipMemcpyAsync(&last[1], pushed.p + (n_att - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    H2D_OR_RETURN(small_down(e, 0, (const int*)position.p + (n_att - 1), 1, st));
+    H2D_OR_RETURN(small_down(e, sizeof(int), (const int*)pushed.p + (n_att - 1), 1, st));
     HIPCHK(e, hipStreamSynchronize(st));
+    small_read(e, 0, last, 2);
     const size_t n_next = (size_t)last[0] + (size_t)last[1];
     HIPCHK(e, cell_nxt->reserve(std::max<size_t>(n_next, 1)));
     HIPCHK(e, src_nxt->reserve(std::max<size_t>(n_next, 1)));
@@ -478,8 +477,7 @@ int stage_cloud(bpf_engine* e, const float* points_xyz, int n_points)
     e->h_points.p[(size_t)n_points + q] = points_xyz[3 * q + 1];
     e->h_points.p[2 * (size_t)n_points + q] = points_xyz[3 * q + 2];
   }
-  HIPCHK(e, hipMemcpyAsync(e->d_points.p, e->h_points.p, (size_t)n_points * 3 * sizeof(float), hipMemcpyHostToDevice,
-                           e->stream));
+  H2D_OR_RETURN(pinned_up(e, e->d_points, 0, e->h_points, 0, (size_t)n_points * 3, e->stream));
   HIPCHK(e, e->h_cloud_table.reserve(257));
   HIPCHK(e, e->d_cloud_table.reserve(257));
   const double denom = 2 * e->cloud_sigma * e->cloud_sigma;
@@ -501,8 +499,7 @@ int stage_cloud(bpf_engine* e, const float* points_xyz, int n_points)
       e->h_cloud_table.p[k] = pz;
     }
   }
-  HIPCHK(e, hipMemcpyAsync(e->d_cloud_table.p, e->h_cloud_table.p, 257 * sizeof(double), hipMemcpyHostToDevice,
-                           e->stream));
+  H2D_OR_RETURN(pinned_up(e, e->d_cloud_table, 0, e->h_cloud_table, 0, 257, e->stream));
   return BPF_OK;
 }
 

@@ -132,14 +132,13 @@ int bpf_pf_get_samples(bpf_engine* e, double* samples_out, int capacity, int* sa
   HIPCHK(e, hipGetLastError());
   if (host_buffer_pinned(e, samples_out, (size_t)n * sizeof(double4)))
   {
-    // a registered buffer of the caller: the copy engine writes it directly
-    HIPCHK(e, hipMemcpyAsync(samples_out, e->d_aos.p, (size_t)n * sizeof(double4), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    // a registered buffer of the caller: d2h_to_host finds the registration and lets the copy engine write it directly
+    H2D_OR_RETURN(d2h_to_host(e, samples_out, e->d_aos.p, (size_t)n * sizeof(double4), e->stream));
   }
   else
   {
-    HIPCHK(e, hipMemcpyAsync(e->h_aos.p, e->d_aos.p, (size_t)n * sizeof(double4), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    // a pageable one: the whole set at once through the set-sized pinned staging buffer (not the bounce pieces)
+    H2D_OR_RETURN(pinned_down_sync(e, e->h_aos, 0, e->d_aos, 0, (size_t)n, e->stream));
     std::memcpy(samples_out, e->h_aos.p, (size_t)n * sizeof(double4));
   }
   if (sample_count_out)
@@ -160,10 +159,10 @@ int bpf_pf_snapshot(bpf_engine* e)
   const size_t n = (size_t)e->sample_count;
   HIPCHK(e, e->snap.reserve(n));
   SampleSet& s = e->sets[e->cur];
-  HIPCHK(e, hipMemcpyAsync(e->snap.x.p, s.x.p, n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-  HIPCHK(e, hipMemcpyAsync(e->snap.y.p, s.y.p, n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-  HIPCHK(e, hipMemcpyAsync(e->snap.th.p, s.th.p, n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-  HIPCHK(e, hipMemcpyAsync(e->snap.w.p, s.w.p, n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+  HIPCHK(e, copy_d2d(e->snap.x.p, (const double*)s.x.p, n, e->stream));
+  HIPCHK(e, copy_d2d(e->snap.y.p, (const double*)s.y.p, n, e->stream));
+  HIPCHK(e, copy_d2d(e->snap.th.p, (const double*)s.th.p, n, e->stream));
+  HIPCHK(e, copy_d2d(e->snap.w.p, (const double*)s.w.p, n, e->stream));
   e->snap_count = e->sample_count;
   e->snap_leaf = e->tree.leaf_count;
   e->snap_bins = e->tree.bin_count;

@@ -1,9 +1,11 @@
 // C-ABI: caller-owned host buffers (the reference keeps its particles in a host std::vector<PFSample> that is
 // allocated once, particle_filter.cpp:62-89, and hands it to the sensor model every cycle).
 // ---------------------------------------------------------------------- host buffers
-// A pageable buffer crosses PCIe through the ENGINE's bounce buffer (h2d_from_host, host_common.inl: the runtime's own
-// on-the-fly pinning keeps stale pins of buffers that were freed and allocated again); handed to the runtime directly
-// (BPF_OPT_HOST_DIRECT_PAGEABLE) 3.2 MB go up at the link's rate too
+// A pageable buffer crosses PCIe through the ENGINE's bounce buffer (h2d_from_host / d2h_to_host, host_copy.hpp: the
+// runtime's own on-the-fly pinning keeps stale pins of buffers that were freed and allocated again).  That file holds
+// every copy call of the engine, and only those two functions take a plain host address, so no other site can hand
+// pageable memory to the runtime; host_reg_find there is the one test for "inside a registered range".  Handed to the
+// runtime directly (BPF_OPT_HOST_DIRECT_PAGEABLE) 3.2 MB go up at the link's rate too
 // (64 us, tools/ubench/pcie_probe.hip), but the calling thread is busy inside the call for that long and a download
 // into it takes 44 us per 0.8 MB instead of 22; a buffer pinned with hipHostRegister is read and written by the copy
 // engine -- or by a kernel -- directly, with the calling thread free.  Registration costs 60 us to a millisecond, so
@@ -14,15 +16,6 @@
 // (BPF_OPT_HOST_AUTO_REGISTER is the caller's explicit promise for every buffer it hands over).
 namespace
 {
-bpf_engine::HostReg* host_reg_find(bpf_engine* e, const void* ptr, size_t bytes)
-{
-  const uintptr_t a = reinterpret_cast<uintptr_t>(ptr);
-  for (auto& r : e->host_regs)
-    if (a >= r.base && a + bytes <= r.base + r.bytes)
-      return &r;
-  return nullptr;
-}
-
 int host_reg_add(bpf_engine* e, void* ptr, size_t bytes, bool automatic)
 {
   const uintptr_t a = reinterpret_cast<uintptr_t>(ptr);

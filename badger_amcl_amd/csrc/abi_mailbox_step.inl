@@ -117,8 +117,7 @@ struct ShardExchange
     HIPCHK(e, e->coll.recv.reserve(per * (size_t)W));
     HIPCHK(e, hipMemsetAsync(e->coll.send.p, 0, per * sizeof(long long), e->stream));
     for (int k = 0; k < rows && counts[rank] > 0; ++k)
-      HIPCHK(e, hipMemcpyAsync(e->coll.send.p + (size_t)k * widest, src[k], (size_t)counts[rank] * sizeof(long long),
-                               hipMemcpyDeviceToDevice, e->stream));
+      HIPCHK(e, copy_d2d(e->coll.send.p + (size_t)k * widest, src[k], (size_t)counts[rank], e->stream));
     if (e->coll.fn.allgather_i64(e->coll.comm, e->coll.send.p, e->coll.recv.p, per, e->stream) != 0)
       return e->fail(BPF_ERR_EXCHANGE, std::string("RCCL all-gather: ") + e->coll.fn.last_error());
     for (int r = 0; r < W; ++r)
@@ -435,8 +434,8 @@ int shard_keep_window(const ShardResample& S, const ShardWindow& win, int m0, in
   bpf_engine* e = S.e;
   HIPCHK(e, e->d_shard_out.reserve((size_t)3 * S.max_global));
   for (int k = 0; k < 3; ++k)
-    HIPCHK(e, hipMemcpyAsync(e->d_shard_out.p + (size_t)k * S.max_global + m0, win.row(k), (size_t)count * sizeof(double),
-                             hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(e, copy_d2d(e->d_shard_out.p + (size_t)k * S.max_global + m0, (const double*)win.row(k), (size_t)count,
+                       e->stream));
   R->kept = true;
   return BPF_OK;
 }

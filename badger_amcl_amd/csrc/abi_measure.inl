@@ -76,12 +76,12 @@ int bpf_get_window_plan(bpf_engine* e, int* used_window, int* chunks_covered, in
   if (e->last_used_window_path && e->d_plan.p)
   {
     HIPCHK(e, hipSetDevice(e->device));
-    WindowPlan plan;
-    HIPCHK(e, hipMemcpyAsync(&plan, e->d_plan.p, sizeof(int) * 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    uw = plan.use_window;
-    cov = plan.covered;
-    tot = plan.n_chunks;
+    static_assert(offsetof(WindowPlan, d) == 4 * sizeof(int), "WindowPlan begins with four ints");
+    int head[4];  // use_window, n_chunks, covered, pad
+    H2D_OR_RETURN(small_down_sync(e, head, reinterpret_cast<const int*>(e->d_plan.p), 4, e->stream));
+    uw = head[0];
+    cov = head[2];
+    tot = head[1];
   }
   if (used_window)
     *used_window = uw;

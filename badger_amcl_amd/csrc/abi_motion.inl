@@ -103,9 +103,7 @@ int generate_gaussians(bpf_engine* e, long long need, long long first, long long
       after_gauss();
       HIPCHK(e, hipGetLastError());
     }
-    HIPCHK(e, hipMemcpyAsync(e->h_motion_result.p, e->d_motion_result.p, 4 * sizeof(long long), hipMemcpyDeviceToHost,
-                             e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    H2D_OR_RETURN(pinned_down_sync(e, e->h_motion_result, 0, e->d_motion_result, 0, 4, e->stream));
     const long long consumed = e->h_motion_result.p[0], zero_seen = e->h_motion_result.p[1],
                     accepted = e->h_motion_result.p[2];
     if (zero_at == kNoZero && zero_seen > 0)
@@ -230,8 +228,7 @@ int bpf_pf_init_with_gaussian(bpf_engine* e, const double mean[3], const double 
   HIPCHK(e, hipSetDevice(e->device));
   const int n = e->max_samples;
   HIPCHK(e, e->d_init_rot.reserve(9));
-  HIPCHK(e, hipMemcpyAsync(e->d_init_rot.p, rotation, 9 * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));  // `rotation` is the caller's memory
+  H2D_OR_RETURN(h2d_from_host_sync(e, e->d_init_rot.p, rotation, 9 * sizeof(double)));  // the caller's memory
   SampleSet& dst = e->sets[e->cur];
   long long consumed = 0;
   int rc = generate_gaussians(e, 3ll * n, 0, 3ll * n, sigma, &consumed, [&]() {

@@ -78,13 +78,8 @@ int search_finish(bpf_engine* e, const SearchSpace& S, int k, bpf_pose_hit* hits
                      (const SearchEntry*)e->d_search_best.p, (const int*)e->d_search_counts.p, S, e->d_search_hits.p);
   if (hipGetLastError() != hipSuccess)
     return e->fail(BPF_ERR_HIP, "k_search_hits launch");
-  hipError_t r = hipMemcpyAsync(e->h_search_count.p, e->d_search_counts.p, sizeof(int), hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess)
-    r = hipMemcpyAsync(e->h_search_hits.p, e->d_search_hits.p, (size_t)k * sizeof(bpf_pose_hit), hipMemcpyDeviceToHost,
-                       e->stream);
-  if (r != hipSuccess)
-    return e->fail_hip(r, "pose search: copy of the hits");
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  H2D_OR_RETURN(pinned_down(e, e->h_search_count, 0, e->d_search_counts, 0, 1, e->stream));
+  H2D_OR_RETURN(pinned_down_sync(e, e->h_search_hits, 0, e->d_search_hits, 0, (size_t)k, e->stream));
   const int n_hits = std::max(0, std::min(e->h_search_count.p[0], k));
   std::memcpy(hits_out, e->h_search_hits.p, (size_t)n_hits * sizeof(bpf_pose_hit));
   *n_hits_out = n_hits;

@@ -21,8 +21,7 @@ int shard_init_gaussian_write(bpf_engine* e, const double mean[3], const double 
                               long long first, int n, long long global_count, uint64_t* rng_after)
 {
   HIPCHK(e, e->d_init_rot.reserve(9));
-  HIPCHK(e, hipMemcpyAsync(e->d_init_rot.p, rotation, 9 * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));  // `rotation` is the caller's memory
+  H2D_OR_RETURN(h2d_from_host_sync(e, e->d_init_rot.p, rotation, 9 * sizeof(double)));  // the caller's memory
   SampleSet& dst = e->sets[e->cur ^ 1];
   long long consumed = 0;
   int rc = generate_gaussians(e, 3 * global_count, 3 * first, 3ll * n, sigma, &consumed, [&]() {
@@ -73,8 +72,7 @@ int shard_init_commit(bpf_engine* e, int n, uint64_t rng_after, bool spread)
 int gtree_flags(bpf_engine* e)
 {
   HIPCHK(e, e->h_gt_flags.reserve(4));
-  HIPCHK(e, hipMemcpyAsync(e->h_gt_flags.p, e->d_gt_flags.p, 4 * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  H2D_OR_RETURN(pinned_down_sync(e, e->h_gt_flags, 0, e->d_gt_flags, 0, 4, e->stream));
   if (e->h_gt_flags.p[3] != 0)
     return e->fail(BPF_ERR_HIP, "global tree: a bounded table walk ran out (corrupt bin list?)");
   return BPF_OK;

@@ -13,19 +13,13 @@ struct InplacePlan
   bool in_place = false;               // false: the imbalance cap sends this resample to the window form
 };
 
-// The ascending targets into e->h_targets and every rank's share of them.  The targets are the reference's serial
-// chain (particle_filter.cpp:337-341) as systematic_window_args forms it; the teeth formed after the subtraction are
-// the small ones, so the ascending order is the chain rotated by i_wrap.  The slices are shard_slice's: the same
-// additions and quotients in the same order, so every rank -- and the window kernel -- gets the same doubles.
-int inplace_plan(bpf_engine* e, uint64_t rng_state48, int count, const void* sums_dev, int sums_are_totals, int world,
-                 InplacePlan* P)
+// The slices of the global CDF, edge[0 .. world], from the ranks' weight sums on the device (one wait for the stream).
+// They are shard_slice's: the same additions and quotients in the same order, so every rank -- and the window kernel
+// -- gets the same doubles.  Both in-place resamples, systematic and multinomial, take their slices from here.
+int inplace_edges(bpf_engine* e, const void* sums_dev, int sums_are_totals, int world, double* edge)
 {
-  const int n_random = e->shard_n_random;
-  if (n_random < 0 || n_random >= count)
-    return e->fail(BPF_ERR_INVALID_ARGUMENT, "in-place resample: random pose count out of range");
   double sums[kMailboxMaxWorld];
-  HIPCHK(e, hipMemcpyAsync(sums, sums_dev, (size_t)world * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  H2D_OR_RETURN(small_down_sync(e, sums, static_cast<const double*>(sums_dev), (size_t)world, e->stream));
   double T = 1.0;
   if (sums_are_totals)
   {
@@ -34,14 +28,27 @@ int inplace_plan(bpf_engine* e, uint64_t rng_state48, int count, const void* sum
       T += sums[r];
   }
   double offset = 0.0;
-  P->edge[0] = 0.0;
+  edge[0] = 0.0;
   for (int r = 0; r < world; ++r)
   {
     offset += sums_are_totals ? sums[r] / T : sums[r];
-    if (!(offset >= P->edge[r]))
+    if (!(offset >= edge[r]))
       return e->fail(BPF_ERR_INVALID_ARGUMENT, "in-place resample: a shard's weight sum is negative or not a number");
-    P->edge[r + 1] = offset;
+    edge[r + 1] = offset;
   }
+  return BPF_OK;
+}
+
+// The ascending targets into e->h_targets and every rank's share of them.  The targets are the reference's serial
+// chain (particle_filter.cpp:337-341) as systematic_window_args forms it; the teeth formed after the subtraction are
+// the small ones, so the ascending order is the chain rotated by i_wrap.
+int inplace_plan(bpf_engine* e, uint64_t rng_state48, int count, const void* sums_dev, int sums_are_totals, int world,
+                 InplacePlan* P)
+{
+  const int n_random = e->shard_n_random;
+  if (n_random < 0 || n_random >= count)
+    return e->fail(BPF_ERR_INVALID_ARGUMENT, "in-place resample: random pose count out of range");
+  H2D_OR_RETURN(inplace_edges(e, sums_dev, sums_are_totals, world, P->edge));
   const int n = count - n_random;
   HIPCHK(e, e->h_targets.reserve((size_t)std::max(count, e->max_samples)));
   if (e->targets_read)  // a previous kernel may still be reading the pinned targets
@@ -194,7 +201,7 @@ int inplace_count(bpf_engine* e, SampleSet& s, int n, const void* reduced_dev, i
 int inplace_converged_install(bpf_engine* e, const void* reduced_count_dev, int global_count)
 {
   HIPCHK(e, e->d_flags.reserve(8));
-  HIPCHK(e, hipMemcpyAsync(e->d_flags.p + 1, reduced_count_dev, sizeof(int), hipMemcpyDeviceToDevice, e->stream));
+  HIPCHK(e, copy_d2d(e->d_flags.p + 1, static_cast<const int*>(reduced_count_dev), 1, e->stream));
   e->converged_pending = true;
   e->conv_n = global_count;
   return BPF_OK;

@@ -18,31 +18,6 @@ int mn_check_begin(bpf_engine* e, uint64_t rng_state48, const void* sums_dev, in
   return BPF_OK;
 }
 
-// the slices of the global CDF: shard_slice's additions and quotients in the same order (see inplace_plan)
-int mn_edges(bpf_engine* e, const void* sums_dev, int sums_are_totals, int world, double* edge)
-{
-  double sums[kMailboxMaxWorld];
-  HIPCHK(e, hipMemcpyAsync(sums, sums_dev, (size_t)world * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  double T = 1.0;
-  if (sums_are_totals)
-  {
-    T = 0.0;
-    for (int r = 0; r < world; ++r)
-      T += sums[r];
-  }
-  double offset = 0.0;
-  edge[0] = 0.0;
-  for (int r = 0; r < world; ++r)
-  {
-    offset += sums_are_totals ? sums[r] / T : sums[r];
-    if (!(offset >= edge[r]))
-      return e->fail(BPF_ERR_INVALID_ARGUMENT, "in-place resample: a shard's weight sum is negative or not a number");
-    edge[r + 1] = offset;
-  }
-  return BPF_OK;
-}
-
 // what the draws of this resample read from the stream (draw_window_args' branches, without a window)
 int mn_draw_args(bpf_engine* e, int rank, int world, WindowArgs* out)
 {
@@ -329,7 +304,7 @@ int shard_update_resample_in_place_mn(bpf_engine* e, void* flags_dev, uint64_t r
   if (rc != BPF_OK)
     return rc;
   double edge[kMailboxMaxWorld + 1];
-  rc = mn_edges(e, e->mb_totals, 1, W, edge);
+  rc = inplace_edges(e, e->mb_totals, 1, W, edge);
   if (rc != BPF_OK)
     return rc;
   int n_kept = 0, n_bins = 0, out_of_range = 0;
@@ -397,7 +372,7 @@ int bpf_shard_inplace_mn_select_dev(bpf_engine* e, uint64_t rng_state48, const v
   if (rc != BPF_OK)
     return rc;
   HIPCHK(e, hipSetDevice(e->device));
-  rc = mn_edges(e, sums_dev, sums_are_totals, world, e->mn.edge);
+  rc = inplace_edges(e, sums_dev, sums_are_totals, world, e->mn.edge);
   if (rc != BPF_OK)
     return rc;
   rc = mn_select(e, rank, world, e->mn.edge, n_kept_out);

@@ -199,7 +199,7 @@ int local_reduce(LocalRank* me, void* buf, size_t n, bool i32)
     return local_fail("local exchange: staging allocation");
   }
   char* stage = reinterpret_cast<char*>(me->stage.p) + (reinterpret_cast<uintptr_t>(buf) & 15u);
-  if (bytes > 0 && hipMemcpyAsync(stage, buf, bytes, hipMemcpyDeviceToDevice, e->stream) != hipSuccess)
+  if (bytes > 0 && copy_d2d(stage, static_cast<const char*>(buf), bytes, e->stream) != hipSuccess)
   {
     me->world->mark_broken();
     return local_fail("local exchange: staging copy");
@@ -418,13 +418,12 @@ int bpf_shard_local_selftest(bpf_engine* e, int rounds)
           h_send[(size_t)(i + lead)] = lx_pattern(rank, round, 1, i);
         h_recv.assign((size_t)(total + 2 * kGuard), kFill);
         if (!h_send.empty())
-          HIPCHK(e, hipMemcpyAsync(d_send.p, h_send.data(), h_send.size() * 8, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(e, hipMemcpyAsync(d_recv.p, h_recv.data(), h_recv.size() * 8, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(e, hipStreamSynchronize(e->stream));  // (the pageable sources are reused below)
+          H2D_OR_RETURN(h2d_from_host(e, d_send.p, h_send.data(), h_send.size() * 8, e->stream));
+        // (the pageable sources are reused below: the pageable way up has read them when it returns)
+        H2D_OR_RETURN(h2d_from_host_sync(e, d_recv.p, h_recv.data(), h_recv.size() * 8));
         if (local_exchange(me, kLxGather, d_send.p + lead, counts[rank], d_recv.p, off) != 0)
           return exchange_failed();
-        HIPCHK(e, hipMemcpyAsync(h_recv.data(), d_recv.p, h_recv.size() * 8, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(e, hipStreamSynchronize(e->stream));
+        H2D_OR_RETURN(d2h_to_host(e, h_recv.data(), d_recv.p, h_recv.size() * 8, e->stream));
         want.assign(h_recv.size(), kFill);
         for (int r = 0; r < W; ++r)
           for (long long i = 0; i < counts[r]; ++i)
@@ -439,14 +438,12 @@ int bpf_shard_local_selftest(bpf_engine* e, int rounds)
           hs[(size_t)i] = (double)(rank + 1) + 1e-3 * (double)i + 1e-7 * round;
         std::fill(hr.begin(), hr.end(), -1.0);
         if (n > 0)
-          HIPCHK(e, hipMemcpyAsync(d_send.p, hs.data(), hs.size() * 8, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(e, hipMemcpyAsync(d_recv.p, hr.data(), hr.size() * 8, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(e, hipStreamSynchronize(e->stream));
+          H2D_OR_RETURN(h2d_from_host(e, d_send.p, hs.data(), hs.size() * 8, e->stream));
+        H2D_OR_RETURN(h2d_from_host_sync(e, d_recv.p, hr.data(), hr.size() * 8));
         double* recv = reinterpret_cast<double*>(d_recv.p) + kGuard + 1;
         if (e->coll.fn.allgather_f64(me, reinterpret_cast<const double*>(d_send.p), recv, (size_t)n, e->stream) != 0)
           return exchange_failed();
-        HIPCHK(e, hipMemcpyAsync(hr.data(), d_recv.p, hr.size() * 8, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(e, hipStreamSynchronize(e->stream));
+        H2D_OR_RETURN(d2h_to_host(e, hr.data(), d_recv.p, hr.size() * 8, e->stream));
         wt.assign(hr.size(), -1.0);
         for (int r = 0; r < W; ++r)
           for (long long i = 0; i < n; ++i)
@@ -460,12 +457,10 @@ int bpf_shard_local_selftest(bpf_engine* e, int rounds)
         h_recv.assign((size_t)(n + 2 * kGuard + lead), kFill);
         for (long long i = 0; i < n; ++i)
           h_recv[(size_t)(kGuard + lead + i)] = lx_pattern(rank, round, 2 + lead, i);
-        HIPCHK(e, hipMemcpyAsync(d_recv.p, h_recv.data(), h_recv.size() * 8, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(e, hipStreamSynchronize(e->stream));
+        H2D_OR_RETURN(h2d_from_host_sync(e, d_recv.p, h_recv.data(), h_recv.size() * 8));
         if (e->coll.fn.allreduce_sum_i64(me, d_recv.p + kGuard + lead, (size_t)n, e->stream) != 0)
           return exchange_failed();
-        HIPCHK(e, hipMemcpyAsync(h_recv.data(), d_recv.p, h_recv.size() * 8, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(e, hipStreamSynchronize(e->stream));
+        H2D_OR_RETURN(d2h_to_host(e, h_recv.data(), d_recv.p, h_recv.size() * 8, e->stream));
         want.assign(h_recv.size(), kFill);
         for (long long i = 0; i < n; ++i)
         {
@@ -484,13 +479,11 @@ int bpf_shard_local_selftest(bpf_engine* e, int rounds)
         for (long long i = 0; i < n; ++i)
           hb[(size_t)(2 * kGuard + lead + i)] = lx_pattern32(rank, round, i);
         int* d = reinterpret_cast<int*>(d_recv.p);
-        HIPCHK(e, hipMemcpyAsync(d, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(e, hipStreamSynchronize(e->stream));
+        H2D_OR_RETURN(h2d_from_host_sync(e, d, hb.data(), hb.size() * 4));
         if (e->coll.fn.allreduce_sum_i32(me, d + 2 * kGuard + lead, (size_t)n, e->stream) != 0)
           return exchange_failed();
         wt.assign(hb.size(), 0x5A5A5A5A);
-        HIPCHK(e, hipMemcpyAsync(hb.data(), d, hb.size() * 4, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(e, hipStreamSynchronize(e->stream));
+        H2D_OR_RETURN(d2h_to_host(e, hb.data(), d, hb.size() * 4, e->stream));
         for (long long i = 0; i < n; ++i)
         {
           long long acc = 0;

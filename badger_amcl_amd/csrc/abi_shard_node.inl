@@ -26,14 +26,12 @@ int shard_gather_host_words(bpf_engine* e, ShardExchange& X, const long long* mi
   }
   for (int k = 0; k < n_each; ++k)
     e->h_x_words.p[k] = mine[k];
-  HIPCHK(e, hipMemcpyAsync(e->d_x_words.p, e->h_x_words.p, (size_t)n_each * sizeof(long long), hipMemcpyHostToDevice,
-                           e->stream));
+  H2D_OR_RETURN(pinned_up(e, e->d_x_words, 0, e->h_x_words, 0, (size_t)n_each, e->stream));
   const long long* src[1] = { e->d_x_words.p };
   int rc = X.gather(src, 1, counts, e->d_x_words.p + 4, offs, 0);
   if (rc != BPF_OK)
     return rc;
-  HIPCHK(e, hipMemcpyAsync(e->h_x_words.p + 4, e->d_x_words.p + 4, n_all * sizeof(long long), hipMemcpyDeviceToHost,
-                           e->stream));
+  H2D_OR_RETURN(pinned_down(e, e->h_x_words, 4, e->d_x_words, 4, n_all, e->stream));
   rc = X.finish();
   if (rc != BPF_OK)
     return rc;
@@ -88,7 +86,8 @@ int shard_gather_slices_host(bpf_engine* e, ShardExchange& X, const long long* c
   if (rc != BPF_OK)
     return rc;
   soa->resize((size_t)rows * (size_t)n);
-  HIPCHK(e, hipMemcpyAsync(soa->data(), e->d_x_gather.p, soa->size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  // (the pageable way down returns with the stream drained: finish()'s wait finds nothing left to wait for)
+  H2D_OR_RETURN(d2h_to_host(e, soa->data(), e->d_x_gather.p, soa->size() * sizeof(double), e->stream));
   return X.finish();
 }
 

@@ -21,8 +21,7 @@ void install_device_stats(bpf_engine* e, const StatsResult& r)
 int shard_stats_flags(bpf_engine* e)
 {
   HIPCHK(e, e->h_stats_flags.reserve(4));
-  HIPCHK(e, hipMemcpyAsync(e->h_stats_flags.p, e->d_stats_flags.p, 4 * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  H2D_OR_RETURN(pinned_down_sync(e, e->h_stats_flags, 0, e->d_stats_flags, 0, 4, e->stream));
   if (e->h_stats_flags.p[3] != 0)
     return e->fail(BPF_ERR_HIP, "sharded statistics: a bounded table walk ran out (corrupt bin list?)");
   return BPF_OK;
@@ -300,8 +299,7 @@ int bpf_shard_stats_finish_dev(bpf_engine* e, const void* reduced_sums_dev)
   hipLaunchKernelGGL(k_stats_set, dim3(1), dim3(1024), 0, e->stream, A, (const ClusterDev*)clusters,
                      e->d_stats_result.p);
   HIPCHK(e, hipGetLastError());
-  HIPCHK(e, hipMemcpyAsync(e->h_stats_result.p, e->d_stats_result.p, sizeof(StatsResult), hipMemcpyDeviceToHost,
-                           e->stream));
+  H2D_OR_RETURN(pinned_down(e, e->h_stats_result, 0, e->d_stats_result, 0, 1, e->stream));
   int rc = shard_stats_flags(e);
   e->ss_stage = 0;
   if (rc != BPF_OK)

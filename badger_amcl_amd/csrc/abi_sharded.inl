@@ -867,8 +867,7 @@ int bpf_get_cells_walked(bpf_engine* e, unsigned long long* out, int reset)
   if (!e->d_cells_walked.p)
     return BPF_OK;
   HIPCHK(e, hipSetDevice(e->device));
-  HIPCHK(e, hipMemcpyAsync(out, e->d_cells_walked.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  H2D_OR_RETURN(small_down_sync(e, out, (const unsigned long long*)e->d_cells_walked.p, 1, e->stream));
   if (reset)
     HIPCHK(e, hipMemsetAsync(e->d_cells_walked.p, 0, sizeof(unsigned long long), e->stream));
   return BPF_OK;

@@ -128,10 +128,8 @@ int compute_cluster_stats_device(bpf_engine* e, bool* handled)
   hipLaunchKernelGGL(k_stats_set, dim3(1), dim3(1024), 0, e->stream, A, (const ClusterDev*)clusters,
                      e->d_stats_result.p);
   HIPCHK(e, hipGetLastError());
-  HIPCHK(e, hipMemcpyAsync(e->h_stats_result.p, e->d_stats_result.p, sizeof(StatsResult), hipMemcpyDeviceToHost,
-                           e->stream));
-  HIPCHK(e, hipMemcpyAsync(e->h_stats_flags.p, e->d_stats_flags.p, 4 * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  H2D_OR_RETURN(pinned_down(e, e->h_stats_result, 0, e->d_stats_result, 0, 1, e->stream));
+  H2D_OR_RETURN(pinned_down_sync(e, e->h_stats_flags, 0, e->d_stats_flags, 0, 4, e->stream));
   if (e->h_stats_flags.p[0] != 0 || e->h_stats_flags.p[1] != 0)
     return BPF_OK;  // key range / non-finite weights: the host path takes the reference's route through them
   const StatsResult& r = *e->h_stats_result.p;
@@ -159,12 +157,8 @@ int fetch_device_clusters(bpf_engine* e)
     return BPF_OK;
   static_assert(sizeof(ClusterDev) == sizeof(bpf_cluster), "ClusterDev mirrors bpf_cluster");
   e->clusters.assign((size_t)e->stats_cluster_count, bpf_cluster{});
-  if (e->stats_cluster_count > 0)
-  {
-    HIPCHK(e, hipMemcpyAsync(e->clusters.data(), e->d_stats_clusters.p,
-                             (size_t)e->stats_cluster_count * sizeof(bpf_cluster), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-  }
+  H2D_OR_RETURN(d2h_to_host(e, e->clusters.data(), e->d_stats_clusters.p,
+                            (size_t)e->stats_cluster_count * sizeof(bpf_cluster), e->stream));
   e->stats_clusters_fetched = true;
   // The device sums are 32.96 fixed point (kernels_stats.hpp): every term is cut below 2^-96, so a cluster's sums are
   // off by up to count * 2^-96 absolute.  Where that is not below 1e-12 of the cluster's weight (a set scored several

@@ -45,6 +45,7 @@
 using namespace bpf;
 
 #include "engine_state.hpp"
+#include "host_copy.hpp"
 
 namespace
 {

@@ -15,6 +15,8 @@ constexpr int kTableLdsMax = 2048;  // table entries that still go to LDS
 constexpr int kEventPool = 8192;
 constexpr int kSeamMaxChunks = 8;
 constexpr int kSeamMaxBlocks = 4096;
+// the pinned scratch of small_down (host_copy.hpp): its largest caller fetches one weight sum per rank
+constexpr size_t kSmallResultBytes = kMailboxMaxWorld * sizeof(double);
 
 // Device / pinned buffers free themselves with the engine (bpf_destroy selects the device first).
 template <typename T>
@@ -622,9 +624,10 @@ struct bpf_engine
 
   // ---- tile-sorted scoring of a spread cloud (kernels_window.hpp, HOST_MODE 3 of k_score_field)
   bool tile_sort = true;            // BPF_OPT_TILE_SORT
-  // Pageable host memory on its way up (h2d_from_host, host_common.inl): two pinned halves that this thread fills
-  // while the copy engine empties the other one
+  // Pageable host memory on its way up or down (h2d_from_host / d2h_to_host, host_copy.hpp): two pinned halves, one
+  // in this thread's hands while the copy engine has the other
   PinnedBuf<unsigned char> h_bounce;
+  PinnedBuf<unsigned char> h_small;  // [kSmallResultBytes] a few result words on their way into a local (small_down)
   hipEvent_t bounce_ev[2] = { nullptr, nullptr };
   bool bounce_busy[2] = { false, false };
   int bounce_next = 0;
@@ -641,6 +644,8 @@ struct bpf_engine
   unsigned timed_launches = 0;  // scoring launches seen in profile mode 1 / 3 (every timed_stride-th is timed)
   unsigned timed_stride = 8;    // mode 1: kTimedLaunchStride, mode 3: 1
   bool profile_all = false;
+  // the kernel classes the current profile mode times: the scoring kernels, or every class in mode 2
+  bool times_class(int klass) const { return profile_all || klass == BPF_K_SCORE || klass == BPF_K_SCORE_WINDOW; }
   std::vector<hipEvent_t> ev_start, ev_stop;
   std::vector<int> ev_class;
   size_t ev_used = 0;

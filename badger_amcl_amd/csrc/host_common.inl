@@ -1,25 +1,5 @@
-// Host helpers shared by every part of the engine: profiling scopes, drand48 jump tables, LUT encoding.
-// ------------------------------------------------------------------ pageable host memory, host to device
-// hipMemcpy* from PAGEABLE memory of more than a megabyte pins the range on the fly, and the runtime keeps such pins in
-// a small cache keyed by address and size.  A buffer that has been freed and allocated again at the same address -- what
-// an allocator does all day -- then meets a pin of pages that are gone: the copy reads stale data (seen as a weight
-// vector from the previous call in tests/test_gpu_seam_a.py, once in ~20 runs of the suite) or the GPU faults on the
-// host address ("Memory access fault ... Reason: Unknown" at a heap address in tests/test_gpu_soaks.py, one run in
-// five; none in nine runs with the runtime's pinned transfers switched off).  So pageable memory -- the caller's and the
-// engine's own temporaries -- goes up through the engine's own pinned bounce buffer: this thread copies a piece into
-// one half while the copy engine empties the other.  Registered buffers (bpf_host_buffer_register: the owner's
-// promise that the memory stays) and BPF_OPT_HOST_DIRECT_PAGEABLE = 1 (the same promise for every buffer) go to the
-// runtime as they are.  On return the source has been read completely.
-constexpr size_t kBounceHalf = (size_t)2 << 20;
-#define H2D_OR_RETURN(call)   \
-  do                          \
-  {                           \
-    const int _rc = (call);   \
-    if (_rc != BPF_OK)        \
-      return _rc;             \
-  } while (0)
-
-int h2d_from_host(bpf_engine* e, void* dst, const void* src, size_t bytes, hipStream_t st);
+// Host helpers shared by every part of the engine: profiling scopes, drand48 jump tables, LUT encoding.  (Copies
+// between host and device are host_copy.hpp's: pageable memory never goes to the runtime's copy calls from here.)
 
 // The open-addressing table of n keys: the smallest power of two >= 2 n, at least 1024 (at most half full).  Every
 // caller passes an int sample count or a bin total it has held below 2^30, so 2 n < 2^32: the 32-bit product
@@ -33,107 +13,6 @@ unsigned hash_table_size(long long n)
   return table;
 }
 
-// The way down into PAGEABLE memory (a destination of more than a megabyte is pinned and cached by the runtime just
-// the same): piece by piece into the bounce buffer and from there by this thread.  Everything queued on `st` before
-// the call is done when it returns, and so is the copy.
-int d2h_to_host(bpf_engine* e, void* dst, const void* src, size_t bytes, hipStream_t st)
-{
-  if (bytes == 0)
-    return BPF_OK;
-  bool direct = e->host_direct;
-  if (!direct)
-  {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(dst);
-    for (const auto& r : e->host_regs)
-      direct = direct || (a >= r.base && a + bytes <= r.base + r.bytes);
-  }
-  if (direct)
-  {
-    HIPCHK(e, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(e, hipStreamSynchronize(st));
-    return BPF_OK;
-  }
-  HIPCHK(e, e->h_bounce.reserve(2 * kBounceHalf));
-  for (int h = 0; h < 2; ++h)
-  {
-    if (e->bounce_ev[h] == nullptr)
-      HIPCHK(e, hipEventCreateWithFlags(&e->bounce_ev[h], hipEventDisableTiming));
-    if (e->bounce_busy[h])
-      HIPCHK(e, hipEventSynchronize(e->bounce_ev[h]));  // (an upload that may still be reading this half)
-    e->bounce_busy[h] = false;
-  }
-  unsigned char* d = static_cast<unsigned char*>(dst);
-  const unsigned char* s = static_cast<const unsigned char*>(src);
-  // two pieces in flight: the copy engine fills one half while this thread empties the other
-  size_t issued = 0, taken = 0;
-  int h_issue = 0, h_take = 0;
-  while (taken < bytes)
-  {
-    while (issued < bytes && issued - taken < 2 * kBounceHalf)
-    {
-      const size_t piece = std::min(kBounceHalf, bytes - issued);
-      HIPCHK(e, hipMemcpyAsync(e->h_bounce.p + (size_t)h_issue * kBounceHalf, s + issued, piece, hipMemcpyDeviceToHost, st));
-      HIPCHK(e, hipEventRecord(e->bounce_ev[h_issue], st));
-      issued += piece;
-      h_issue ^= 1;
-    }
-    const size_t piece = std::min(kBounceHalf, bytes - taken);
-    HIPCHK(e, hipEventSynchronize(e->bounce_ev[h_take]));
-    std::memcpy(d + taken, e->h_bounce.p + (size_t)h_take * kBounceHalf, piece);
-    taken += piece;
-    h_take ^= 1;
-  }
-  return BPF_OK;
-}
-
-// the same, and the device has it when the call returns (where a plain hipMemcpy stood)
-int h2d_from_host_sync(bpf_engine* e, void* dst, const void* src, size_t bytes)
-{
-  const int rc = h2d_from_host(e, dst, src, bytes, e->stream);
-  if (rc != BPF_OK)
-    return rc;
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return BPF_OK;
-}
-
-int h2d_from_host(bpf_engine* e, void* dst, const void* src, size_t bytes, hipStream_t st)
-{
-  if (bytes == 0)
-    return BPF_OK;
-  bool direct = e->host_direct;
-  if (!direct)
-  {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(src);
-    for (const auto& r : e->host_regs)
-      direct = direct || (a >= r.base && a + bytes <= r.base + r.bytes);
-  }
-  if (direct)
-  {
-    HIPCHK(e, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
-    return BPF_OK;
-  }
-  HIPCHK(e, e->h_bounce.reserve(2 * kBounceHalf));
-  for (int h = 0; h < 2; ++h)
-    if (e->bounce_ev[h] == nullptr)
-      HIPCHK(e, hipEventCreateWithFlags(&e->bounce_ev[h], hipEventDisableTiming));
-  const unsigned char* s = static_cast<const unsigned char*>(src);
-  unsigned char* d = static_cast<unsigned char*>(dst);
-  for (size_t off = 0; off < bytes; off += kBounceHalf)
-  {
-    const size_t piece = std::min(kBounceHalf, bytes - off);
-    const int h = e->bounce_next;
-    e->bounce_next ^= 1;
-    if (e->bounce_busy[h])
-      HIPCHK(e, hipEventSynchronize(e->bounce_ev[h]));  // (the copy that last read this half)
-    unsigned char* half = e->h_bounce.p + (size_t)h * kBounceHalf;
-    std::memcpy(half, s + off, piece);
-    HIPCHK(e, hipMemcpyAsync(d + off, half, piece, hipMemcpyHostToDevice, st));
-    HIPCHK(e, hipEventRecord(e->bounce_ev[h], st));
-    e->bounce_busy[h] = true;
-  }
-  return BPF_OK;
-}
-
 // ------------------------------------------------------------------ profiling helpers
 struct ProfScope
 {
@@ -141,8 +20,7 @@ struct ProfScope
   int idx = -1;
   ProfScope(bpf_engine* eng, int klass) : e(eng)
   {
-    if (!e->profiling || e->ev_used >= e->ev_start.size() ||
-        (klass != BPF_K_SCORE && klass != BPF_K_SCORE_WINDOW && !e->profile_all))
+    if (!e->profiling || e->ev_used >= e->ev_start.size() || !e->times_class(klass))
       return;
     idx = (int)e->ev_used++;
     e->ev_class[idx] = klass;
@@ -167,9 +45,8 @@ constexpr unsigned kTimedLaunchStride = 8;
   do                                                                                                                  \
   {                                                                                                                   \
     bpf_engine* _e = (e);                                                                                             \
-    if (_e->profiling && _e->ev_used < _e->ev_start.size() &&                                                         \
-        ((klass) == BPF_K_SCORE || (klass) == BPF_K_SCORE_WINDOW || _e->profile_all) &&                               \
-        (_e->profile_all || (_e->timed_launches++ % _e->timed_stride) == 0))                                              \
+    if (_e->profiling && _e->ev_used < _e->ev_start.size() && _e->times_class(klass) &&                               \
+        (_e->profile_all || (_e->timed_launches++ % _e->timed_stride) == 0))                                          \
     {                                                                                                                 \
       const int _idx = (int)_e->ev_used++;                                                                            \
       _e->ev_class[_idx] = (klass);                                                                                   \

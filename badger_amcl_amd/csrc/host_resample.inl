@@ -39,9 +39,8 @@ int kld_host_k(const bpf_engine* e)
 
 int fetch_scalars(bpf_engine* e)
 {
-  HIPCHK(e, hipMemcpyAsync(e->h_scalars.p, e->d_scalars.p, sizeof(FilterScalars), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipMemcpyAsync(e->h_flags.p, e->d_flags.p, 8 * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  H2D_OR_RETURN(pinned_down(e, e->h_scalars, 0, e->d_scalars, 0, 1, e->stream));
+  H2D_OR_RETURN(pinned_down_sync(e, e->h_flags, 0, e->d_flags, 0, 8, e->stream));
   if (e->converged_pending)
   {
     // particle_filter.cpp:206-219, float arithmetic for the percentage
@@ -134,7 +133,7 @@ int build_cdf(bpf_engine* e, const double* w, int n, int* zero_word2 = nullptr, 
     if (zero_word2)
       HIPCHK(e, hipMemsetAsync(zero_word2, 0, sizeof(int), e->stream));
     if (sum_out)
-      HIPCHK(e, hipMemcpyAsync(sum_out, e->d_cdf.p + n, sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      HIPCHK(e, copy_d2d(sum_out, (const double*)e->d_cdf.p + n, 1, e->stream));
   }
   else
   {
@@ -337,9 +336,7 @@ struct TrialScores
       if (rc != BPF_OK)
         return rc;
       e->h_cand_scores.resize((size_t)n);
-      HIPCHK(e, hipMemcpyAsync(e->h_cand_scores.data(), e->cand.w.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
-                               e->stream));
-      HIPCHK(e, hipStreamSynchronize(e->stream));
+      H2D_OR_RETURN(d2h_to_host(e, e->h_cand_scores.data(), e->cand.w.p, (size_t)n * sizeof(double), e->stream));
       lo = pos;
       hi = pos + (unsigned)n * stride;
     }
@@ -490,9 +487,7 @@ int ensure_limit_table(bpf_engine* e, int upto)
     for (int k = 0; k <= n; ++k)
       e->kld_limit_host[k] = resample_limit(k, e->min_samples, e->max_samples, e->pop_err, e->pop_z);
     HIPCHK(e, e->d_kld_limit.reserve((size_t)n + 1));
-    HIPCHK(e, hipMemcpyAsync(e->d_kld_limit.p, e->kld_limit_host.data(), ((size_t)n + 1) * sizeof(int),
-                             hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    H2D_OR_RETURN(h2d_from_host_sync(e, e->d_kld_limit.p, e->kld_limit_host.data(), ((size_t)n + 1) * sizeof(int)));
     e->kld_limit_key[0] = e->pop_err;
     e->kld_limit_key[1] = e->pop_z;
     e->kld_limit_key[2] = e->min_samples;
@@ -933,9 +928,7 @@ int kld_tree_levels(bpf_engine* e, const KldArgs& K, bool whole_stream, KldOutco
                          e->d_kld_flags.p + 4 + level);
     }
     HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(e->h_kld.p, e->d_kld_flags.p, (4 + kKldMaxLevels) * sizeof(int), hipMemcpyDeviceToHost,
-                             e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    H2D_OR_RETURN(pinned_down_sync(e, e->h_kld, 0, e->d_kld_flags, 0, 4 + kKldMaxLevels, e->stream));
     if (e->h_kld.p[0] != 0)
       return BPF_OK;  // a key outside the packing range: not handled
     const int waiting = e->h_kld.p[4 + level - 1];  // keys that are not nodes yet
@@ -963,13 +956,11 @@ int kld_tree_levels(bpf_engine* e, const KldArgs& K, bool whole_stream, KldOutco
   hipLaunchKernelGGL(k_kld_scan_final, dim3(tiles), dim3(256), 0, e->stream, K, (const int2*)e->d_kld_tiles.p,
                      e->d_kld_counts.p);
   HIPCHK(e, hipGetLastError());
-  HIPCHK(e, hipMemcpyAsync(e->h_kld.p, e->d_kld_flags.p, 4 * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  H2D_OR_RETURN(pinned_down_sync(e, e->h_kld, 0, e->d_kld_flags, 0, 4, e->stream));
   const int stop = whole_stream ? -1 : e->h_kld.p[2];  // whole_stream: the tree of all n keys, no stop rule
   const int M = (stop >= 1 && stop <= n) ? stop : n;
   int2 c;
-  HIPCHK(e, hipMemcpyAsync(&c, e->d_kld_counts.p + (M - 1), sizeof(int2), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  H2D_OR_RETURN(small_down_sync(e, &c, (const int2*)e->d_kld_counts.p + (M - 1), 1, e->stream));
   out->set((stop >= 1 && stop <= n) ? stop : -1, c.x, c.y);
   return BPF_OK;
 }
@@ -1067,8 +1058,7 @@ struct KeyView
 // the AoS triples the kernel left in e->d_keys, copied
 int copy_key_triples(bpf_engine* e, int n, KeyView* view)
 {
-  HIPCHK(e, hipMemcpyAsync(e->h_keys.p, e->d_keys.p, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  H2D_OR_RETURN(pinned_down_sync(e, e->h_keys, 0, e->d_keys, 0, (size_t)n * 3, e->stream));
   *view = KeyView{ e->h_keys.p, 0 };
   return BPF_OK;
 }
@@ -1103,8 +1093,7 @@ int stream_after_resample(bpf_engine* e, uint64_t state0, const StreamUse& use, 
   if (use.regime == STREAM_MULTINOMIAL_CHAIN)
   {
     HIPCHK(e, e->h_chain_word.reserve(1));
-    HIPCHK(e, hipMemcpyAsync(e->h_chain_word.p, e->d_chain.p + (M - 1), sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    H2D_OR_RETURN(pinned_down_sync(e, e->h_chain_word, 0, e->d_chain, (size_t)(M - 1), 1, e->stream));
     chain_word = e->h_chain_word.p[0];
   }
   *state48_out = lcg_skip_host(state0, stream_consumed(use, M, chain_word), e->jump);
@@ -1405,10 +1394,9 @@ int upload_samples(bpf_engine* e, const double* aos, int n, SampleSet& dst)
 int download_weights(bpf_engine* e, const SampleSet& src, int n, double* aos)
 {
   HIPCHK(e, e->h_aos.reserve((size_t)n));
-  double* hw = reinterpret_cast<double*>(e->h_aos.p);
-  HIPCHK(e, hipMemcpyAsync(hw, src.w.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipMemcpyAsync(e->h_scalars.p, e->d_scalars.p, sizeof(FilterScalars), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  const double* hw = reinterpret_cast<const double*>(e->h_aos.p);  // the staging buffer lent out as n doubles
+  H2D_OR_RETURN(pinned_down(e, e->h_aos, 0, src.w, 0, (size_t)n, e->stream));
+  H2D_OR_RETURN(pinned_down_sync(e, e->h_scalars, 0, e->d_scalars, 0, 1, e->stream));
   for (int i = 0; i < n; ++i)
     aos[4 * (size_t)i + 3] = hw[i];
   return BPF_OK;

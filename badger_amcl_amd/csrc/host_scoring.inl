@@ -418,7 +418,7 @@ int field_prep(bpf_engine* e, int n, ScanSlot* s, const FieldScan& fs, const Fie
     stage.n16 = n16;
   }
   else if (pending)
-    HIPCHK(e, hipMemcpyAsync(s->dev.p, s->host.p, fs.bytes, hipMemcpyHostToDevice, e->stream));
+    H2D_OR_RETURN(pinned_up(e, s->dev, 0, s->host, 0, fs.bytes, e->stream));
   ProfScope pa(e, BPF_K_SCORE_AUX);
   const ParticlesDev& p = A->p;
   if (form == FieldForm::TILE)
@@ -672,9 +672,10 @@ int score_planar_beamskip_finish(bpf_engine* e, ParticlesDev p, int n, long long
   e->skip_pending = false;
   const int nv = std::max(fs.n_staged, 1);
   std::vector<int> counts((size_t)nv, 0);
-  HIPCHK(e, hipMemcpyAsync(counts.data(), e->d_obs_count.p, (size_t)fs.n_staged * sizeof(int), hipMemcpyDeviceToHost,
-                           e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (fs.n_staged > 0)
+    H2D_OR_RETURN(d2h_to_host(e, counts.data(), e->d_obs_count.p, (size_t)fs.n_staged * sizeof(int), e->stream));
+  else
+    HIPCHK(e, hipStreamSynchronize(e->stream));  // (no beam staged: the counting pass is still waited for)
   std::vector<int> obs_count((size_t)pm.max_beams, 0);
   for (int v = 0; v < fs.n_staged; ++v)
     if (fs.slot_of[v] < pm.max_beams)
@@ -763,7 +764,7 @@ int score_beam_model(bpf_engine* e, ParticlesDev p, int n, const double* ranges,
   StagedSlot s;
   H2D_OR_RETURN(acquire_slot(e, bytes, &s));
   std::memcpy(s->host.p, beams.data(), bytes);
-  HIPCHK(e, hipMemcpyAsync(s->dev.p, s->host.p, bytes, hipMemcpyHostToDevice, e->stream));
+  H2D_OR_RETURN(pinned_up(e, s->dev, 0, s->host, 0, bytes, e->stream));
   BeamModelArgs A{};
   A.p = p;
   A.n = n;
