@@ -30,6 +30,13 @@ class PoseHit(C.Structure):
                 ("j", C.c_int), ("heading", C.c_int), ("reserved", C.c_int)]
 
 
+class PoseRefined(C.Structure):
+    _fields_ = [("pose", C.c_double * 3), ("score", C.c_double), ("score_in", C.c_double), ("moved", C.c_int),
+                ("reserved", C.c_int)]
+
+
+assert C.sizeof(PoseRefined) == 48  # bpf_pose_refined
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p
@@ -214,6 +221,11 @@ SIGNATURES = {
     "bpf_cloud_search_poses": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_longlong,
                                          C.c_longlong, C.c_int, C.POINTER(PoseHit), _ip]),
     "bpf_cloud_search_space": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _ip]),
+    "bpf_planar_refine_poses": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, _dp, C.c_int, C.c_int, C.c_double, C.c_int,
+                                          C.c_double, C.c_int, C.POINTER(PoseRefined), _ip]),
+    "bpf_cloud_refine_poses": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, _dp, C.c_int, C.c_int, C.c_double,
+                                         C.c_int, C.c_double, C.c_int, C.POINTER(PoseRefined), _ip]),
+    "bpf_pose_refine_lattice": (C.c_int, [C.c_int, C.c_int, _ip, _ip]),
     "bpf_device_memory_info": (C.c_int, [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "bpf_profile_enable": (C.c_int, [_vp, C.c_int]),
     "bpf_profile_reset": (C.c_int, [_vp]),

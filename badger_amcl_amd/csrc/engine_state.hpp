@@ -487,6 +487,18 @@ struct bpf_engine
   PinnedBuf<bpf_pose_hit> h_search_hits;
   PinnedBuf<int> h_search_count;
 
+  // ---- pose refinement (kernels_pose_refine.hpp, abi_pose_refine.inl): the centres of the descent and what
+  // k_refine_select keeps per pose.  The lattice poses live in `cand`; nothing here describes the particle set
+  DevBuf<double> d_refine_centres;  // [n_poses][3] x, y, theta: the input poses, then every level's choice
+  DevBuf<double> d_refine_score;    // [n_poses] score of the centre, from the last level
+  DevBuf<double> d_refine_score_in; // [n_poses] score of the input pose
+  DevBuf<int> d_refine_moved;       // [n_poses]
+  DevBuf<int> d_refine_trace;       // [n_poses][levels] the m chosen
+  DevBuf<bpf_pose_refined> d_refine_rows;
+  PinnedBuf<double> h_refine_in;    // the input poses on their way up
+  PinnedBuf<bpf_pose_refined> h_refine_rows;
+  PinnedBuf<int> h_refine_trace;
+
   // ---- KLD stop rule on the device (long draw streams)
   int kld_device_min = 8192;  // draws left after the first window from which the device tree takes over
   int kld_count_mode = BPF_KLD_COUNT_LEAVES;  // bpf_pf_set_kld_count: what the stop rule's k counts

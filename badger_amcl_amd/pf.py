@@ -556,11 +556,52 @@ class PlanarScanner:
             int(count), int(k), hits.ctypes.data_as(C.POINTER(_lib.PoseHit)), C.byref(n)))
         return hits[:n.value]
 
+    def refinePoses(self, data, poses, xy_radius, xy_step, theta_radius, theta_step, levels, trace=False):
+        """NOT a reference method: coarse-to-fine lattice descent around every pose of `poses` (an [n, 3] array or a
+        POSE_HIT_DTYPE array) against `data`, on the device.  Returns a POSE_REFINED_DTYPE array in the input order,
+        with trace=True also the [n, levels] int32 array of the lattice points chosen.  See bpf_planar_refine_poses
+        in include/badger_pf.h."""
+        if self.map is not None:
+            self.map.upload()
+        rp, ap = data.pointers()
+        return _refine_poses(self.e, poses, levels, trace, lambda p, n, out, tr: self.e.lib.bpf_planar_refine_poses(
+            self.e.h, rp, ap, data.range_count_, data.range_max_, p, n, int(xy_radius), float(xy_step),
+            int(theta_radius), float(theta_step), int(levels), out, tr))
+
 
 # one row of a pose search: bpf_pose_hit
 POSE_HIT_DTYPE = np.dtype([("pose", "<f8", (3,)), ("score", "<f8"), ("candidate", "<i8"), ("i", "<i4"), ("j", "<i4"),
                            ("heading", "<i4"), ("reserved", "<i4")])
 assert POSE_HIT_DTYPE.itemsize == C.sizeof(_lib.PoseHit)
+
+
+# one row of a pose refinement: bpf_pose_refined
+POSE_REFINED_DTYPE = np.dtype([("pose", "<f8", (3,)), ("score", "<f8"), ("score_in", "<f8"), ("moved", "<i4"),
+                               ("reserved", "<i4")])
+assert POSE_REFINED_DTYPE.itemsize == C.sizeof(_lib.PoseRefined)
+
+
+def _refine_poses(engine, poses, levels, trace, call):
+    """the marshalling both scanners' refinePoses share: call(poses*, n, rows*, trace* or None) -> status"""
+    poses = np.asarray(poses)
+    if poses.dtype == POSE_HIT_DTYPE:
+        poses = poses["pose"]
+    xyt = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    n = xyt.shape[0]
+    rows = np.zeros(max(n, 1), dtype=POSE_REFINED_DTYPE)
+    tr = np.zeros((max(n, 1), max(int(levels), 1)), dtype=np.int32) if trace else None
+    engine.check(call(_dp(xyt), n, rows.ctypes.data_as(C.POINTER(_lib.PoseRefined)),
+                      tr.ctypes.data_as(C.POINTER(C.c_int)) if trace else None))
+    return (rows[:n], tr[:n]) if trace else rows[:n]
+
+
+def pose_refine_lattice(xy_radius, theta_radius):
+    """(M, m_c): the number of points and the centre's index of a refinement lattice (needs no GPU)."""
+    m, c = C.c_int(), C.c_int()
+    rc = _lib.load().bpf_pose_refine_lattice(int(xy_radius), int(theta_radius), C.byref(m), C.byref(c))
+    if rc != 0:
+        raise BpfError(rc, _lib.load().bpf_error_string(rc).decode())
+    return m.value, c.value
 
 
 def pose_search_window():
@@ -703,6 +744,16 @@ class PointCloudScanner:
             self.e.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], int(headings), int(cell_stride),
             int(first), int(count), int(k), hits.ctypes.data_as(C.POINTER(_lib.PoseHit)), C.byref(n)))
         return hits[:n.value]
+
+    def refinePoses(self, data, poses, xy_radius, xy_step, theta_radius, theta_step, levels, trace=False):
+        """NOT a reference method: coarse-to-fine lattice descent around every pose of `poses` (an [n, 3] array or a
+        POSE_HIT_DTYPE array) against the cloud `data`, on the device.  Returns a POSE_REFINED_DTYPE array in the
+        input order, with trace=True also the [n, levels] int32 array of the lattice points chosen.  See
+        bpf_cloud_refine_poses in include/badger_pf.h."""
+        pts = data.points_
+        return _refine_poses(self.e, poses, levels, trace, lambda p, n, out, tr: self.e.lib.bpf_cloud_refine_poses(
+            self.e.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], p, n, int(xy_radius), float(xy_step),
+            int(theta_radius), float(theta_step), int(levels), out, tr))
 
 
 def uniform_pose_retries(threshold, multiplier):

@@ -435,6 +435,41 @@ public:
     hits.resize((size_t)n);
     return hits;
   }
+  // NOT a reference method (bpf_planar_refine_poses): coarse-to-fine lattice descent around every pose of `poses_xyt`
+  // (x, y, theta triples) against `data` on the device; row r refines pose r.  trace_out, when given, receives the
+  // lattice point chosen per (pose, level), poses.size() / 3 * levels ints.
+  std::vector<bpf_pose_refined> refinePoses(std::shared_ptr<PlanarData> data, const std::vector<double>& poses_xyt,
+                                            int xy_radius, double xy_step, int theta_radius, double theta_step,
+                                            int levels, std::vector<int>* trace_out = nullptr)
+  {
+    if (map_)
+      map_->upload();
+    const int n = (int)(poses_xyt.size() / 3);
+    std::vector<bpf_pose_refined> rows((size_t)(n > 0 ? n : 1));
+    if (trace_out)
+      trace_out->assign((size_t)(n > 0 ? n : 1) * (size_t)(levels > 0 ? levels : 1), 0);
+    e_->check(bpf_planar_refine_poses(e_->get(), data->ranges_.data(), data->angles_.data(), data->range_count_,
+                                      data->range_max_, poses_xyt.data(), n, xy_radius, xy_step, theta_radius,
+                                      theta_step, levels, rows.data(), trace_out ? trace_out->data() : nullptr));
+    rows.resize((size_t)n);
+    return rows;
+  }
+  // the same around the poses of a search's hits
+  std::vector<bpf_pose_refined> refinePoses(std::shared_ptr<PlanarData> data, const std::vector<bpf_pose_hit>& hits,
+                                            int xy_radius, double xy_step, int theta_radius, double theta_step,
+                                            int levels, std::vector<int>* trace_out = nullptr)
+  {
+    return refinePoses(data, posesOfHits(hits), xy_radius, xy_step, theta_radius, theta_step, levels, trace_out);
+  }
+  // x, y, theta of every hit, packed
+  static std::vector<double> posesOfHits(const std::vector<bpf_pose_hit>& hits)
+  {
+    std::vector<double> xyt;
+    xyt.reserve(hits.size() * 3);
+    for (const auto& h : hits)
+      xyt.insert(xyt.end(), h.pose, h.pose + 3);
+    return xyt;
+  }
   // candidates (free cells kept by cell_stride x headings) of searchPoses: what a caller splits into ranges
   long long searchSpace(int headings, int cell_stride = 1, int* free_cells_out = nullptr)
   {
@@ -594,6 +629,32 @@ public:
                                      count, k, hits.data(), &n));
     hits.resize((size_t)n);
     return hits;
+  }
+  // NOT a reference method (bpf_cloud_refine_poses): coarse-to-fine lattice descent around every pose of `poses_xyt`
+  // (x, y, theta triples) against the cloud `data` on the device; row r refines pose r.  trace_out, when given,
+  // receives the lattice point chosen per (pose, level), poses.size() / 3 * levels ints.
+  std::vector<bpf_pose_refined> refinePoses(std::shared_ptr<PointCloudData> data, const std::vector<double>& poses_xyt,
+                                            int xy_radius, double xy_step, int theta_radius, double theta_step,
+                                            int levels, std::vector<int>* trace_out = nullptr)
+  {
+    const int n = (int)(poses_xyt.size() / 3);
+    std::vector<bpf_pose_refined> rows((size_t)(n > 0 ? n : 1));
+    if (trace_out)
+      trace_out->assign((size_t)(n > 0 ? n : 1) * (size_t)(levels > 0 ? levels : 1), 0);
+    e_->check(bpf_cloud_refine_poses(e_->get(), data->points_.data(), data->pointCount(), poses_xyt.data(), n,
+                                     xy_radius, xy_step, theta_radius, theta_step, levels, rows.data(),
+                                     trace_out ? trace_out->data() : nullptr));
+    rows.resize((size_t)n);
+    return rows;
+  }
+  // the same around the poses of a search's hits
+  std::vector<bpf_pose_refined> refinePoses(std::shared_ptr<PointCloudData> data,
+                                            const std::vector<bpf_pose_hit>& hits, int xy_radius, double xy_step,
+                                            int theta_radius, double theta_step, int levels,
+                                            std::vector<int>* trace_out = nullptr)
+  {
+    return refinePoses(data, PlanarScanner::posesOfHits(hits), xy_radius, xy_step, theta_radius, theta_step, levels,
+                       trace_out);
   }
   // candidates (columns kept by cell_stride x headings) of searchPoses: what a caller splits into ranges
   long long searchSpace(int headings, int cell_stride = 1, int* columns_out = nullptr)

@@ -1214,6 +1214,54 @@ int bpf_cloud_search_poses(bpf_engine* e, const float* points_xyz, int n_points,
  * itself, also when it is past the limit of a search); *columns_out = |C_s| */
 int bpf_cloud_search_space(bpf_engine* e, int headings, int cell_stride, long long* candidates_out, int* columns_out);
 
+/* ------------------------------------------------------------------ pose refinement
+ * Sub-cell, sub-degree poses from the hits of a search (or from any poses): a coarse-to-fine descent on a lattice
+ * around each pose, all of it on the device.  NOT a reference call (parity unpinned by construction).
+ *
+ * R = xy_radius, A = theta_radius, L = levels.  The lattice has M = (2R+1)^2 (2A+1) points; point m is
+ * (a (2R+1) + b) (2A+1) + t with a, b in [0, 2R] and t in [0, 2A]; the centre m_c has a = b = R, t = A.
+ * At level l in [0, L) the steps are d_l = xy_step * 2^-l and q_l = theta_step * 2^-l (ldexp: exact), and the pose
+ * of point m around the centre (cx, cy, ctheta) is, evaluated in double as written with no contraction,
+ *   x = cx + (double)(a - R) * d_l,  y = cy + (double)(b - R) * d_l,  theta = ctheta + (double)(t - A) * q_l.
+ * A step whose radius is 0 is not read (it counts as 0.0).  The score of a pose is exactly the search's: the weight
+ * of the one-sample set {pose, 1.0} after applyModelToSampleSet with set->converged = 0 (planar form) or what
+ * bpf_cloud_apply_model_to_sample_set returns for it (cloud form), under the model, map factors and scanner pose /
+ * tf configured on the engine; 1.0 with max_beams < 2.
+ *
+ * The new centre is the best point of the lattice: score descending; among equal scores the centre before every
+ * other point, then m ascending; NaN below every number.  A centre chosen again is not rewritten, so a flat or
+ * all-NaN neighbourhood leaves the pose bit for bit where it was.  Level l + 1 starts from level l's centre, level 0
+ * from the input pose.  Row r of `out` refines pose r (the input order is kept; the caller sorts); trace_out, when
+ * not NULL, receives n_poses * levels ints, trace_out[r * L + l] = the m chosen for pose r at level l.
+ *
+ * Limits: 1 <= n_poses <= 1024, R >= 0, A >= 0, 2 <= M <= 2048, 1 <= L <= 16, xy_step finite and > 0 when R > 0,
+ * theta_step finite and > 0 when A > 0, every input pose finite, the scan (cloud), poses_xyt and out non-null,
+ * otherwise BPF_ERR_INVALID_ARGUMENT.  Requirements and the status codes of the scoring path are those of the matching
+ * search call (BPF_ERR_NOT_CONFIGURED, BPF_ERR_BEAM_STEP ...).
+ *
+ * Like the searches the call needs no filter and leaves one as it found it (the same state is saved and put back).
+ * Poses are processed in groups of max(1, bpf_pose_search_window() / M), so that a launch scores at most one window
+ * of candidates; the result does not depend on the grouping.  All levels of all groups are enqueued back to back;
+ * the host waits once for the rows (the cloud form once more before its first launch, for the staging buffers). */
+typedef struct
+{
+  double pose[3];  /* refined x, y, theta (theta as accumulated, NOT normalised) */
+  double score;    /* score of `pose`, from the level that chose it last */
+  double score_in; /* score of the input pose (the centre of level 0) */
+  int moved;       /* number of levels at which the centre changed (the chosen m was not m_c) */
+  int reserved;    /* 0 */
+} bpf_pose_refined; /* 48 bytes in every binding */
+
+int bpf_planar_refine_poses(bpf_engine* e, const double* ranges, const double* angles, int range_count,
+                            double range_max, const double* poses_xyt, int n_poses, int xy_radius, double xy_step,
+                            int theta_radius, double theta_step, int levels, bpf_pose_refined* out, int* trace_out);
+int bpf_cloud_refine_poses(bpf_engine* e, const float* points_xyz, int n_points, const double* poses_xyt, int n_poses,
+                           int xy_radius, double xy_step, int theta_radius, double theta_step, int levels,
+                           bpf_pose_refined* out, int* trace_out);
+/* M and m_c of a lattice (either output may be NULL); BPF_ERR_INVALID_ARGUMENT for a negative radius, M < 2 or
+ * M > 2048.  Plain host code, needs no engine */
+int bpf_pose_refine_lattice(int xy_radius, int theta_radius, int* points_out, int* centre_out);
+
 /* ------------------------------------------------------------------ measurement */
 /* free / total device memory as hipMemGetInfo reports it (diagnostic; used by the leak test) */
 int bpf_device_memory_info(int device_ordinal, size_t* free_bytes, size_t* total_bytes);
