@@ -3,6 +3,8 @@ missing; nothing here computes on the CPU."""
 import ctypes as C
 import os
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.environ.get("BPF_LIB") or os.path.join(HERE, "libbadger_pf_hip.so")  # BPF_LIB: experiment builds
 
@@ -36,6 +38,18 @@ class PoseRefined(C.Structure):
 
 
 assert C.sizeof(PoseRefined) == 48  # bpf_pose_refined
+
+
+class MixtureComponent(C.Structure):
+    _fields_ = [("mean", C.c_double * 3), ("rotation", C.c_double * 9), ("sigma", C.c_double * 3),
+                ("count", C.c_int), ("reserved", C.c_int)]
+
+
+assert C.sizeof(MixtureComponent) == 128  # bpf_mixture_component
+# the same layout for numpy: an array of it is passed to the library as it is
+MIXTURE_COMPONENT_DTYPE = np.dtype([("mean", "<f8", (3,)), ("rotation", "<f8", (3, 3)), ("sigma", "<f8", (3,)),
+                                    ("count", "<i4"), ("reserved", "<i4")])
+assert MIXTURE_COMPONENT_DTYPE.itemsize == 128
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -87,6 +101,7 @@ SIGNATURES = {
     "bpf_pf_get_state": (C.c_int, [_vp, C.POINTER(PFState)]),
     "bpf_pf_init_with_gaussian": (C.c_int, [_vp, _dp, _dp, _dp]),
     "bpf_pf_init_with_random_poses": (C.c_int, [_vp]),
+    "bpf_pf_init_with_mixture": (C.c_int, [_vp, C.POINTER(MixtureComponent), C.c_int]),
     "bpf_odom_set_model": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "bpf_pf_update_action": (C.c_int, [_vp, _dp, _dp, _dp]),
     "bpf_shard_update_action": (C.c_int, [_vp, _dp, _dp, _dp, C.c_longlong, C.c_longlong]),
@@ -142,6 +157,8 @@ SIGNATURES = {
     "bpf_shard_stats_host": (C.c_int, [_vp, _dp, C.c_int]),
     "bpf_shard_init_with_gaussian": (C.c_int, [_vp, _dp, _dp, _dp, C.c_longlong, C.c_int, C.c_longlong]),
     "bpf_shard_init_with_random_poses": (C.c_int, [_vp, C.c_longlong, C.c_int, C.c_longlong]),
+    "bpf_shard_init_with_mixture": (C.c_int, [_vp, C.POINTER(MixtureComponent), C.c_int, C.c_longlong, C.c_int,
+                                              C.c_longlong]),
     "bpf_shard_tree_local_bins_dev": (C.c_int, [_vp, C.c_longlong, C.POINTER(_vp), _ip, _ip]),
     "bpf_shard_tree_merge_dev": (C.c_int, [_vp, _vp, _ip, C.c_int, C.c_int, _ip, _ip]),
     "bpf_shard_tree_local_keys_dev": (C.c_int, [_vp, C.POINTER(_vp), _ip]),
@@ -149,6 +166,7 @@ SIGNATURES = {
     "bpf_shard_tree_last_route": (C.c_int, [_vp, _ip]),
     "bpf_shard_init_with_gaussian_all": (C.c_int, [_vp, _dp, _dp, _dp]),
     "bpf_shard_init_with_random_poses_all": (C.c_int, [_vp]),
+    "bpf_shard_init_with_mixture_all": (C.c_int, [_vp, C.POINTER(MixtureComponent), C.c_int]),
     "bpf_shard_global_leaf_count": (C.c_int, [_vp, _ip, _ip]),
     "bpf_shard_mailbox_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_longlong, _vp]),
     "bpf_shard_mailbox_connect": (C.c_int, [_vp, _vp]),
@@ -226,6 +244,8 @@ SIGNATURES = {
     "bpf_cloud_refine_poses": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, _dp, C.c_int, C.c_int, C.c_double,
                                          C.c_int, C.c_double, C.c_int, C.POINTER(PoseRefined), _ip]),
     "bpf_pose_refine_lattice": (C.c_int, [C.c_int, C.c_int, _ip, _ip]),
+    "bpf_pose_mixture_from_hits": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _dp,
+                                             C.POINTER(MixtureComponent), _ip, _ip, _ip]),
     "bpf_device_memory_info": (C.c_int, [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "bpf_profile_enable": (C.c_int, [_vp, C.c_int]),
     "bpf_profile_reset": (C.c_int, [_vp]),

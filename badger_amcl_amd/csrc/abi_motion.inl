@@ -66,8 +66,10 @@ MotionModelDev motion_constants(const bpf_engine* e, const double pose[3], const
 // `need` Gaussians PDFGaussian::draw(sd[rank % 3]) from the filter's drand48 stream, ranks
 // [first, first + count) materialised in d_gauss; *consumed_out = uniforms the whole update took.
 // `after_gauss` is launched right behind the generation (optimistically: a rare second pass re-runs it).
+// With `mix` the draw's argument is sigma[component of rank / 3][rank % 3] of that table and `sd` is not used.
 int generate_gaussians(bpf_engine* e, long long need, long long first, long long count, const double sd[3],
-                       long long* consumed_out, const std::function<void()>& after_gauss)
+                       long long* consumed_out, const std::function<void()>& after_gauss,
+                       const MixtureDev* mix = nullptr)
 {
   // attempts are accepted with probability pi/4; 6 sigma of slack, doubled on the (never yet seen) shortfall
   long long attempts = (long long)std::ceil((double)need / 0.7853981633974483 + 6.0 * std::sqrt((double)need)) + 64;
@@ -92,14 +94,17 @@ int generate_gaussians(bpf_engine* e, long long need, long long first, long long
     A.gauss = e->d_gauss.p;
     A.result = e->d_motion_result.p;
     for (int k = 0; k < 3; ++k)
-      A.sd[k] = sd[k];
+      A.sd[k] = mix ? 0.0 : sd[k];
     A.jump = e->jump;
     {
       ProfScope ps(e, BPF_K_MOTION);
       HIPCHK(e, hipMemsetAsync(e->d_motion_result.p, 0, 4 * sizeof(long long), e->stream));
       hipLaunchKernelGGL(k_motion_count, dim3(tiles), dim3(256), 0, e->stream, A);
       hipLaunchKernelGGL(k_motion_offsets, dim3(1), dim3(1024), 0, e->stream, A, tiles);
-      hipLaunchKernelGGL(k_motion_gauss, dim3(tiles), dim3(256), 0, e->stream, A);
+      if (mix)
+        hipLaunchKernelGGL(k_mixture_gauss, dim3(tiles), dim3(256), 0, e->stream, A, *mix);
+      else
+        hipLaunchKernelGGL(k_motion_gauss, dim3(tiles), dim3(256), 0, e->stream, A);
       after_gauss();
       HIPCHK(e, hipGetLastError());
     }
@@ -240,6 +245,37 @@ int bpf_pf_init_with_gaussian(bpf_engine* e, const double mean[3], const double 
     return rc;
   e->rng = lcg_skip_host(e->rng, (uint64_t)consumed, e->jump);
   return finish_init(e, n, false);
+}
+
+int bpf_pf_init_with_mixture(bpf_engine* e, const bpf_mixture_component* comps, int n_components)
+{
+  if (!e || !comps)
+    return BPF_ERR_INVALID_ARGUMENT;
+  if (!e->have_pf)
+    return e->fail(BPF_ERR_NOT_CONFIGURED, "bpf_pf_create first");
+  const int n = e->max_samples;
+  MixtureTable T;
+  int rc = mixture_table(e, comps, n_components, n, &T);
+  if (rc != BPF_OK)
+    return rc;
+  HIPCHK(e, hipSetDevice(e->device));
+  MixtureDev X{};
+  rc = mixture_upload(e, T, &X);
+  if (rc != BPF_OK)
+    return rc;
+  SampleSet& dst = e->sets[e->cur];
+  long long consumed = 0;
+  rc = generate_gaussians(
+      e, 3ll * n, 0, 3ll * n, nullptr, &consumed,
+      [&]() {
+        hipLaunchKernelGGL(k_init_mixture, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, dst.dev(), n, 0,
+                           (const double*)e->d_gauss.p, X, 1.0 / (double)n);
+      },
+      &X);
+  if (rc != BPF_OK)
+    return rc;
+  e->rng = lcg_skip_host(e->rng, (uint64_t)consumed, e->jump);
+  return finish_init(e, n, T.spread);
 }
 
 int bpf_pf_init_with_random_poses(bpf_engine* e)

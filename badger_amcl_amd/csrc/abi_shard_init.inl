@@ -36,6 +36,30 @@ int shard_init_gaussian_write(bpf_engine* e, const double mean[3], const double 
   return BPF_OK;
 }
 
+// the mixture initialiser (bpf_pf_init_with_mixture), as above; the table's counts are those of the GLOBAL set
+int shard_init_mixture_write(bpf_engine* e, const MixtureTable& T, long long first, int n, long long global_count,
+                             uint64_t* rng_after)
+{
+  MixtureDev X{};
+  int rc = mixture_upload(e, T, &X);
+  if (rc != BPF_OK)
+    return rc;
+  SampleSet& dst = e->sets[e->cur ^ 1];
+  long long consumed = 0;
+  rc = generate_gaussians(
+      e, 3 * global_count, 3 * first, 3ll * n, nullptr, &consumed,
+      [&]() {
+        if (n > 0)
+          hipLaunchKernelGGL(k_init_mixture, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, dst.dev(), n,
+                             (int)first, (const double*)e->d_gauss.p, X, 1.0 / (double)global_count);
+      },
+      &X);
+  if (rc != BPF_OK)
+    return rc;
+  *rng_after = lcg_skip_host(e->rng, (uint64_t)consumed, e->jump);
+  return BPF_OK;
+}
+
 // ParticleFilter::initWithPoseFn with Node::uniformPoseGenerator, as above
 int shard_init_random_write(bpf_engine* e, long long first, int n, long long global_count, uint64_t* rng_after)
 {
@@ -262,6 +286,29 @@ int bpf_shard_init_with_gaussian(bpf_engine* e, const double mean[3], const doub
   if (rc != BPF_OK)
     return rc;
   rc = shard_init_commit(e, local_count, rng_after, false);
+  e->slice_first = rc == BPF_OK ? global_first : -1;
+  e->slice_global = global_count;
+  return rc;
+}
+
+int bpf_shard_init_with_mixture(bpf_engine* e, const bpf_mixture_component* comps, int n_components,
+                                long long global_first, int local_count, long long global_count)
+{
+  if (!e || !comps)
+    return BPF_ERR_INVALID_ARGUMENT;
+  int rc = shard_init_check(e, global_first, local_count, global_count);
+  if (rc != BPF_OK)
+    return rc;
+  MixtureTable T;
+  rc = mixture_table(e, comps, n_components, global_count, &T);
+  if (rc != BPF_OK)
+    return rc;
+  HIPCHK(e, hipSetDevice(e->device));
+  uint64_t rng_after = 0;
+  rc = shard_init_mixture_write(e, T, global_first, local_count, global_count, &rng_after);
+  if (rc != BPF_OK)
+    return rc;
+  rc = shard_init_commit(e, local_count, rng_after, T.spread);
   e->slice_first = rc == BPF_OK ? global_first : -1;
   e->slice_global = global_count;
   return rc;

@@ -360,6 +360,23 @@ int bpf_shard_init_with_gaussian_all(bpf_engine* e, const double mean[3], const 
   });
 }
 
+int bpf_shard_init_with_mixture_all(bpf_engine* e, const bpf_mixture_component* comps, int n_components)
+{
+  if (!e || !comps)
+    return BPF_ERR_INVALID_ARGUMENT;
+  if (!e->have_pf)
+    return e->fail(BPF_ERR_NOT_CONFIGURED, "bpf_pf_create first");
+  // the table's refusals come first on purpose (every rank holds the same table, so every rank refuses alike, and
+  // before anything is exchanged); they need max_samples, hence the filter check here as well as in shard_init_all
+  MixtureTable T;
+  const int rc = mixture_table(e, comps, n_components, e->max_samples, &T);
+  if (rc != BPF_OK)
+    return rc;
+  return shard_init_all(e, T.spread, [&](long long first, int n, long long G, uint64_t* rng_after) {
+    return shard_init_mixture_write(e, T, first, n, G, rng_after);
+  });
+}
+
 int bpf_shard_init_with_random_poses_all(bpf_engine* e)
 {
   if (!e)

@@ -25,6 +25,7 @@
 #include "kernels_cloud.hpp"
 #include "kernels_lut3d.hpp"
 #include "kernels_motion.hpp"
+#include "kernels_mixture.hpp"
 #include "kernels_kld.hpp"
 #include "kernels_kld2.hpp"
 #include "kernels_kld_bins.hpp"
@@ -68,6 +69,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_map2d.inl"
 #include "abi_planar.inl"
 #include "abi_filter.inl"
+#include "abi_mixture.inl"
 #include "abi_motion.inl"
 #include "abi_statistics.inl"
 #include "abi_lut_reference.inl"

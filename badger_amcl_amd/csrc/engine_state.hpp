@@ -529,6 +529,7 @@ struct bpf_engine
   DevBuf<int> d_motion_counts;
   DevBuf<long long> d_motion_offsets, d_motion_result;
   DevBuf<double> d_gauss, d_init_rot;
+  DevBuf<double> d_mixture;  // the mixture initialiser's component rows, then its count prefix (abi_mixture.inl)
   PinnedBuf<long long> h_motion_result;
 
   // ---- cluster statistics on the device (kernels_stats.hpp)

@@ -12,7 +12,7 @@ import threading
 
 import numpy as np
 
-from .pf import BpfError
+from .pf import BpfError, mixture_components
 from .sharded import RESAMPLE_FORMS, TREE_ROUTES, ShardedState, check_kld_modes, check_settings, even_counts
 
 EXCHANGE_NONE, EXCHANGE_MAILBOX, EXCHANGE_RCCL, EXCHANGE_LOCAL = 0, 1, 2, 3
@@ -184,6 +184,12 @@ class LocalShardedFilter:
         assert m.size == 3 and rot.size == 9 and d.size == 3
         self._collective(lambda r, h, lib: lib.bpf_shard_init_with_gaussian_all(
             h, m.ctypes.data_as(_dp), rot.ctypes.data_as(_dp), d.ctypes.data_as(_dp)))
+        self._after_init()
+
+    def init_with_mixture(self, components):
+        """ParticleFilter.initWithMixture over the local world: the counts sum to max_samples of the global set."""
+        comps, ptr = mixture_components(components)
+        self._collective(lambda r, h, lib: lib.bpf_shard_init_with_mixture_all(h, ptr, comps.shape[0]))
         self._after_init()
 
     def init_with_random_poses(self):

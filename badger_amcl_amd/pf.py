@@ -347,6 +347,13 @@ class ParticleFilter:
         assert m.size == 3 and r.size == 9 and d.size == 3
         self.e.check(self.e.lib.bpf_pf_init_with_gaussian(self.e.h, _dp(m), _dp(r), _dp(d)))
 
+    def initWithMixture(self, components):
+        """The set of K Gaussian components (a MIXTURE_COMPONENT_DTYPE array, e.g. from mixtureFromHits), component k
+        taking count_k consecutive samples from the filter's one drand48 stream.  Not a reference call for K > 1;
+        K = 1 is initWithGaussian.  See bpf_pf_init_with_mixture in include/badger_pf.h."""
+        comps, ptr = mixture_components(components)
+        self.e.check(self.e.lib.bpf_pf_init_with_mixture(self.e.h, ptr, comps.shape[0]))
+
     def initWithRandomPoses(self):
         """ParticleFilter::initWithPoseFn with the generator of setRandomPoseGenerator (global localisation)."""
         self.e.check(self.e.lib.bpf_pf_init_with_random_poses(self.e.h))
@@ -602,6 +609,42 @@ def pose_refine_lattice(xy_radius, theta_radius):
     if rc != 0:
         raise BpfError(rc, _lib.load().bpf_error_string(rc).decode())
     return m.value, c.value
+
+
+# one component of a mixture initialiser: bpf_mixture_component
+MIXTURE_COMPONENT_DTYPE = _lib.MIXTURE_COMPONENT_DTYPE
+
+
+def mixture_components(components):
+    """(array, pointer) of a component table as the library takes it; the array keeps the memory alive."""
+    comps = np.ascontiguousarray(components, dtype=MIXTURE_COMPONENT_DTYPE).reshape(-1)
+    return comps, comps.ctypes.data_as(C.POINTER(_lib.MixtureComponent))
+
+
+def mixtureFromHits(rows, total_count, xy_merge, theta_merge, max_components, sigma):
+    """Mixture components from pose-search hits (POSE_HIT_DTYPE) or refined rows (POSE_REFINED_DTYPE): the best rows by
+    score, rows within the merge distances of a better one suppressed, total_count samples shared out by score
+    (largest remainder).  Returns (components, source_row, merged): a MIXTURE_COMPONENT_DTYPE array for
+    initWithMixture, the row each component came from and the rows each one suppressed.  Plain host code, needs no
+    GPU.  See bpf_pose_mixture_from_hits in include/badger_pf.h."""
+    rows = np.asarray(rows)
+    xyt = np.ascontiguousarray(rows["pose"], dtype=np.float64).reshape(-1, 3)
+    scores = np.ascontiguousarray(rows["score"], dtype=np.float64).reshape(-1)
+    sg = np.ascontiguousarray(sigma, dtype=np.float64).reshape(-1)
+    assert sg.size == 3
+    cap = max(int(max_components), 1)
+    out = np.zeros(cap, dtype=MIXTURE_COMPONENT_DTYPE)
+    src = np.zeros(cap, dtype=np.int32)
+    merged = np.zeros(cap, dtype=np.int32)
+    n = C.c_int()
+    ip = C.POINTER(C.c_int)
+    rc = _lib.load().bpf_pose_mixture_from_hits(_dp(xyt), _dp(scores), xyt.shape[0], int(total_count),
+                                                float(xy_merge), float(theta_merge), int(max_components), _dp(sg),
+                                                out.ctypes.data_as(C.POINTER(_lib.MixtureComponent)),
+                                                src.ctypes.data_as(ip), merged.ctypes.data_as(ip), C.byref(n))
+    if rc != 0:
+        raise BpfError(rc, _lib.load().bpf_error_string(rc).decode())
+    return out[:n.value], src[:n.value], merged[:n.value]
 
 
 def pose_search_window():

@@ -53,6 +53,8 @@ import ctypes as C
 import numpy as np
 import torch
 
+from .pf import mixture_components
+
 
 class _DevArray:
     """Zero-copy view of engine-owned device memory for torch (cuda array interface v2)."""
@@ -527,6 +529,17 @@ class HipShardBackend:
         self.e.check(self.e.lib.bpf_shard_init_with_random_poses(self.e.h, int(global_first), int(local_count),
                                                                  int(global_count)))
 
+    def init_mixture(self, components, global_first, local_count, global_count):
+        """bpf_shard_init_with_mixture: the components' counts are those of the GLOBAL set."""
+        comps, ptr = mixture_components(components)
+        self.e.check(self.e.lib.bpf_shard_init_with_mixture(self.e.h, ptr, comps.shape[0], int(global_first),
+                                                            int(local_count), int(global_count)))
+
+    def init_mixture_all(self, components):
+        comps, ptr = mixture_components(components)
+        self.e.check(self.e.lib.bpf_shard_init_with_mixture_all(self.e.h, ptr, comps.shape[0]))
+        return self.global_leaf_count()
+
     def init_gaussian_all(self, mean, rotation, sigma):
         """The init and the global tree over the engine's own exchange (mailbox): (leaf_count, bin_count)."""
         keep, ptr = self._gauss_args(mean, rotation, sigma)
@@ -899,6 +912,16 @@ class ShardedFilter:
             return self._after_init(*self.b.init_gaussian_all(mean, rotation, sigma))
         lo, n = self._even_share()
         self.b.init_gaussian(mean, rotation, sigma, lo, n, self.max_global)
+        self._after_init(*self._global_tree())
+
+    def init_with_mixture(self, components):
+        """ParticleFilter.initWithMixture over the shards (a MIXTURE_COMPONENT_DTYPE array whose counts sum to
+        max_samples = G): every rank passes the same components and holds the same rng state; rank r ends with
+        samples [G r / W, G (r + 1) / W) of the set one engine would hold."""
+        if self.mailbox and hasattr(self.b, "init_mixture_all"):
+            return self._after_init(*self.b.init_mixture_all(components))
+        lo, n = self._even_share()
+        self.b.init_mixture(components, lo, n, self.max_global)
         self._after_init(*self._global_tree())
 
     def init_with_random_poses(self):

@@ -88,6 +88,47 @@ private:
 };
 static_assert(sizeof(PFSample) == 32, "PFSample must match the reference's 32-byte AoS record");
 
+// One Gaussian component of a mixture initialiser (ParticleFilter::initWithMixture): bpf_mixture_component as it is
+using MixtureComponent = bpf_mixture_component;
+
+// What mixtureFromHits returns: the components, the row each came from and the rows each one suppressed
+struct PoseMixture
+{
+  std::vector<MixtureComponent> components;
+  std::vector<int> source_row;
+  std::vector<int> merged;
+};
+
+// Mixture components from pose-search hits or refined rows (bpf_pose_hit, bpf_pose_refined: anything with .pose and
+// .score): the best rows by score, rows within the merge distances of a better one suppressed, total_count samples
+// shared out by score.  Host code, no engine: bpf_pose_mixture_from_hits.
+template <class Row>
+inline PoseMixture mixtureFromHits(const std::vector<Row>& rows, int total_count, double xy_merge, double theta_merge,
+                                   int max_components, const std::array<double, 3>& sigma)
+{
+  std::vector<double> xyt, scores;
+  for (const Row& r : rows)
+  {
+    xyt.insert(xyt.end(), r.pose, r.pose + 3);
+    scores.push_back(r.score);
+  }
+  const size_t cap = (size_t)(max_components > 0 ? max_components : 1);
+  PoseMixture m;
+  m.components.resize(cap);
+  m.source_row.resize(cap);
+  m.merged.resize(cap);
+  int n = 0;
+  const int rc = bpf_pose_mixture_from_hits(xyt.data(), scores.data(), (int)rows.size(), total_count, xy_merge,
+                                            theta_merge, max_components, sigma.data(), m.components.data(),
+                                            m.source_row.data(), m.merged.data(), &n);
+  if (rc != BPF_OK)
+    throw std::runtime_error(std::string("bpf_pose_mixture_from_hits: ") + bpf_error_string(rc));
+  m.components.resize((size_t)n);
+  m.source_row.resize((size_t)n);
+  m.merged.resize((size_t)n);
+  return m;
+}
+
 struct PFSampleSet
 {
   int sample_count = 0;
@@ -248,6 +289,12 @@ public:
     e_->check(bpf_pf_init_with_gaussian(e_->get(), mean.data(), rotation.data(), sigma.data()));
   }
   void initWithRandomPoses() { e_->check(bpf_pf_init_with_random_poses(e_->get())); }
+  // K Gaussian components, component k taking count_k consecutive samples from the filter's one drand48 stream (the
+  // counts sum to max_samples).  Not a reference call for K > 1; K = 1 is initWithGaussian.
+  void initWithMixture(const std::vector<MixtureComponent>& components)
+  {
+    e_->check(bpf_pf_init_with_mixture(e_->get(), components.data(), (int)components.size()));
+  }
   int maxSamples() const { return max_samples_; }
   void updateResample() { e_->check(bpf_pf_update_resample(e_->get())); }
   std::shared_ptr<PFSampleSet> getCurrentSet()
@@ -716,6 +763,11 @@ public:
     e().check(bpf_shard_init_with_random_poses_all(e().get()));
     afterInit();
   }
+  void initWithMixture(const std::vector<MixtureComponent>& components)
+  {
+    e().check(bpf_shard_init_with_mixture_all(e().get(), components.data(), (int)components.size()));
+    afterInit();
+  }
   // Odom::updateAction on this rank's slice: no exchange, every rank ends on the same rng state
   bool updateAction(std::shared_ptr<OdomData> data)
   {
@@ -932,6 +984,10 @@ public:
   void initWithRandomPoses()
   {
     fanOut([&](int r) { ranks_[(size_t)r]->initWithRandomPoses(); });
+  }
+  void initWithMixture(const std::vector<MixtureComponent>& components)
+  {
+    fanOut([&](int r) { ranks_[(size_t)r]->initWithMixture(components); });
   }
   bool updateAction(std::shared_ptr<OdomData> data)
   {

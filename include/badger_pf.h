@@ -412,6 +412,32 @@ int bpf_shard_update_action(bpf_engine* e, const double pose[3], const double de
 int bpf_pf_init_with_gaussian(bpf_engine* e, const double mean[3], const double rotation[9], const double sigma[3]);
 int bpf_pf_init_with_random_poses(bpf_engine* e);
 
+/* Mixture initialiser: the set of K Gaussian components, e.g. the refined hits of a pose search turned into
+ * components by bpf_pose_mixture_from_hits.  Not a reference call for K > 1; K = 1 is bpf_pf_init_with_gaussian.
+ * The current set becomes what the reference produces by running the body of initWithGaussian's loop
+ * (particle_filter.cpp:112-125, pdf_gaussian.cpp:52-70) over the components in index order: component k takes
+ * count_k consecutive samples, each mean_k + cr_k * (draw(cd_k[0]), draw(cd_k[1]), draw(cd_k[2])), all components
+ * drawing from the ONE drand48 stream of the filter in sample order.  Weight 1 / max_samples; afterwards the
+ * histogram tree of the whole set, w_slow = w_fast = 0, converged cleared and the rng advanced by what the whole set
+ * consumed, as after bpf_pf_init_with_gaussian.  A component with count 0 is skipped and its other fields are not
+ * read.  sigma may be 0 (the draw still consumes its uniforms).
+ * BPF_ERR_INVALID_ARGUMENT, with the set, rng and counts as they were and nothing launched: e or comps NULL,
+ * n_components outside [1, 1024], a negative count, counts that do not sum to max_samples, a non-finite mean,
+ * rotation or sigma of a component that has samples.  BPF_ERR_NOT_CONFIGURED without bpf_pf_create.
+ * On the device: one upload of the component table with the prefix of the counts (at most 128 KB), the Gaussian
+ * generation of the motion update with the draw's argument looked up per sample, one kernel that forms the poses,
+ * one read-back of the generation's result words, then the tree. */
+typedef struct
+{
+  double mean[3];     /* x, y, theta */
+  double rotation[9]; /* cr_, row-major, as bpf_pf_init_with_gaussian takes it */
+  double sigma[3];    /* cd_ */
+  int count;          /* samples drawn from this component, >= 0 */
+  int reserved;       /* 0 */
+} bpf_mixture_component; /* 128 bytes in every binding */
+
+int bpf_pf_init_with_mixture(bpf_engine* e, const bpf_mixture_component* comps, int n_components);
+
 /* ------------------------------------------------------------------ cluster statistics
  * ParticleFilter::computeClusterStatsForSet (particle_filter.cpp:505-636) with PFKDTree::cluster
  * (pf_kdtree.cpp:58-90,169-194), and what Node2D::getMaxWeightPose (node_2d.cpp:588-617) reads.
@@ -604,6 +630,10 @@ int bpf_shard_stats_host(bpf_engine* e, const double* all_samples, int global_co
 int bpf_shard_init_with_gaussian(bpf_engine* e, const double mean[3], const double rotation[9], const double sigma[3],
                                  long long global_first, int local_count, long long global_count);
 int bpf_shard_init_with_random_poses(bpf_engine* e, long long global_first, int local_count, long long global_count);
+/* bpf_pf_init_with_mixture for one shard, in every respect as bpf_shard_init_with_gaussian: the counts are counts of
+ * the GLOBAL set and sum to global_count, and a shard boundary may fall anywhere inside a component. */
+int bpf_shard_init_with_mixture(bpf_engine* e, const bpf_mixture_component* comps, int n_components,
+                                long long global_first, int local_count, long long global_count);
 /* The histogram tree of the GLOBAL set (the PFKDTree initWith* builds, particle_filter.cpp:126-131,157-162, whose
  * leaf count the systematic resampler reads first, :285) without moving a particle: the shape of the tree depends
  * only on the order in which DISTINCT keys first appear (pf_kdtree.cpp:97-150), so the ranks exchange their bins.
@@ -1039,6 +1069,7 @@ int bpf_shard_get_max_weight_pose(bpf_engine* e, double* max_weight, double pose
 int bpf_shard_init_with_gaussian_all(bpf_engine* e, const double mean[3], const double rotation[9],
                                      const double sigma[3]);
 int bpf_shard_init_with_random_poses_all(bpf_engine* e);
+int bpf_shard_init_with_mixture_all(bpf_engine* e, const bpf_mixture_component* comps, int n_components);
 /* Leaf and bin count of the GLOBAL set's tree for slices loaded by hand (bpf_pf_set_samples on every rank, call this
  * before the first motion update): the local sample counts, then the exchanges above.  While counts of the global
  * set are in force (after one of the inits above, this call or a sharded resample) it returns them without an
@@ -1261,6 +1292,30 @@ int bpf_cloud_refine_poses(bpf_engine* e, const float* points_xyz, int n_points,
 /* M and m_c of a lattice (either output may be NULL); BPF_ERR_INVALID_ARGUMENT for a negative radius, M < 2 or
  * M > 2048.  Plain host code, needs no engine */
 int bpf_pose_refine_lattice(int xy_radius, int theta_radius, int* points_out, int* centre_out);
+
+/* ------------------------------------------------------------------ from hit rows to mixture components
+ * The step between the searches / refinements above and bpf_pf_init_with_mixture.  Not a reference call.  Plain host
+ * code, needs no engine.  poses_xyt = n_rows x (x, y, theta), scores = n_rows (search hits and refined rows alike).
+ *  1. Rows with a non-finite pose or a score that is NaN, infinite or <= 0 are dropped; the rest are taken by score
+ *     descending, equal scores by row index ascending.
+ *  2. A row is suppressed by an already kept component c when |x - x_c| <= xy_merge, |y - y_c| <= xy_merge and
+ *     |normalize_angle(theta - theta_c)| <= theta_merge (x_c, y_c, theta_c: the kept ROW's values; normalize_angle in
+ *     the fmod form, no trigonometry); it increments merged_out[c].  Any other row becomes a component until
+ *     max_components are kept; later unsuppressed rows are dropped.
+ *  3. Component k: x, y copied bit for bit, theta = normalize_angle(theta) (refined theta comes accumulated),
+ *     rotation the identity, sigma as given, source_row_out[k] its row.
+ *  4. Counts by largest remainder on the scores: W = sum of the kept scores in component order,
+ *     t_k = ((double)total_count * score_k) / W, c_k = floor(t_k); the samples left over go one each to the components
+ *     by t_k - c_k descending (equal remainders by k ascending), wrapping round; should rounding make the floors
+ *     exceed total_count, one is taken from the components that have any in the reverse of that order until it fits.
+ *     The counts sum to total_count exactly; components with count 0 can appear.
+ * out holds max_components entries, source_row_out / merged_out (either may be NULL) max_components ints.
+ * BPF_ERR_INVALID_ARGUMENT: a NULL array, n_rows or max_components outside [1, 1024], total_count < 1, a negative or
+ * non-finite merge distance or sigma, no usable row. */
+int bpf_pose_mixture_from_hits(const double* poses_xyt, const double* scores, int n_rows, int total_count,
+                               double xy_merge, double theta_merge, int max_components, const double sigma[3],
+                               bpf_mixture_component* out, int* source_row_out, int* merged_out,
+                               int* n_components_out);
 
 /* ------------------------------------------------------------------ measurement */
 /* free / total device memory as hipMemGetInfo reports it (diagnostic; used by the leak test) */
