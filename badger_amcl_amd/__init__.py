@@ -5,4 +5,4 @@ include/badger_pf.h).  Importing this package does not load the library; constru
 `Engine` does, and raises if it is missing -- there is no CPU fallback.
 """
 from .pf import (BpfError, Engine, OccupancyMap, OctoMap, Odom, OdomData, ParticleFilter, PFSampleSet,  # noqa: F401
-                 PlanarData, PlanarScanner, PointCloudData, PointCloudScanner, mixtureFromHits)
+                 PlanarData, PlanarScanner, PointCloudData, PointCloudScanner, mixtureApplyMoments, mixtureFromHits)

@@ -40,6 +40,18 @@ class PoseRefined(C.Structure):
 assert C.sizeof(PoseRefined) == 48  # bpf_pose_refined
 
 
+class PoseMoments(C.Structure):
+    _fields_ = [("mean", C.c_double * 3), ("cov", C.c_double * 6), ("weight_sum", C.c_double),
+                ("score_max", C.c_double), ("support", C.c_int), ("flags", C.c_int)]
+
+
+assert C.sizeof(PoseMoments) == 96  # bpf_pose_moments
+# the same layout for numpy (cov: xx, xy, xt, yy, yt, tt)
+POSE_MOMENTS_DTYPE = np.dtype([("mean", "<f8", (3,)), ("cov", "<f8", (6,)), ("weight_sum", "<f8"),
+                               ("score_max", "<f8"), ("support", "<i4"), ("flags", "<i4")])
+assert POSE_MOMENTS_DTYPE.itemsize == 96
+
+
 class MixtureComponent(C.Structure):
     _fields_ = [("mean", C.c_double * 3), ("rotation", C.c_double * 9), ("sigma", C.c_double * 3),
                 ("count", C.c_int), ("reserved", C.c_int)]
@@ -246,6 +258,12 @@ SIGNATURES = {
     "bpf_pose_refine_lattice": (C.c_int, [C.c_int, C.c_int, _ip, _ip]),
     "bpf_pose_mixture_from_hits": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _dp,
                                              C.POINTER(MixtureComponent), _ip, _ip, _ip]),
+    "bpf_planar_pose_moments": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, _dp, C.c_int, C.c_int, C.c_double, C.c_int,
+                                          C.c_double, C.c_double, C.POINTER(PoseMoments), _dp]),
+    "bpf_cloud_pose_moments": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, _dp, C.c_int, C.c_int, C.c_double,
+                                         C.c_int, C.c_double, C.c_double, C.POINTER(PoseMoments), _dp]),
+    "bpf_pose_mixture_apply_moments": (C.c_int, [C.POINTER(MixtureComponent), C.c_int, _ip, C.POINTER(PoseMoments),
+                                                 C.c_int, _dp, _dp, C.c_int]),
     "bpf_device_memory_info": (C.c_int, [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "bpf_profile_enable": (C.c_int, [_vp, C.c_int]),
     "bpf_profile_reset": (C.c_int, [_vp]),

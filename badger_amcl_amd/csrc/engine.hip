@@ -34,6 +34,7 @@
 #include "kernels_pose_array.hpp"
 #include "kernels_pose_search.hpp"
 #include "kernels_pose_refine.hpp"
+#include "kernels_pose_moments.hpp"
 #include "kernels_fused.hpp"
 #include "kernels_stats.hpp"
 #include "kernels_shard_stats.hpp"
@@ -88,6 +89,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_pose_search.inl"
 #include "abi_pose_search_cloud.inl"
 #include "abi_pose_refine.inl"
+#include "abi_pose_moments.inl"
 #include "abi_bootstrap.inl"
 #include "abi_shard_local.inl"
 #include "abi_measure.inl"

@@ -499,6 +499,12 @@ struct bpf_engine
   PinnedBuf<bpf_pose_refined> h_refine_rows;
   PinnedBuf<int> h_refine_trace;
 
+  // ---- pose moments (kernels_pose_moments.hpp, abi_pose_moments.inl): the poses go up through h_refine_in into
+  // d_refine_centres, as a refinement's do
+  DevBuf<bpf_pose_moments> d_moments_rows;
+  PinnedBuf<bpf_pose_moments> h_moments_rows;
+  PinnedBuf<double> h_moments_scores;  // [n_poses][M], only for a call with scores_out
+
   // ---- KLD stop rule on the device (long draw streams)
   int kld_device_min = 8192;  // draws left after the first window from which the device tree takes over
   int kld_count_mode = BPF_KLD_COUNT_LEAVES;  // bpf_pf_set_kld_count: what the stop rule's k counts

@@ -575,6 +575,19 @@ class PlanarScanner:
             self.e.h, rp, ap, data.range_count_, data.range_max_, p, n, int(xy_radius), float(xy_step),
             int(theta_radius), float(theta_step), int(levels), out, tr))
 
+    def poseMoments(self, data, poses, xy_radius, xy_step, theta_radius, theta_step, baseline, scores=False):
+        """NOT a reference method: the score-weighted first and second moments of one refinement lattice (steps as
+        given) around every pose of `poses` (an [n, 3] array, hit rows or refined rows) against `data`, on the device.
+        Returns a POSE_MOMENTS_DTYPE array in the input order, with scores=True also the [n, M] lattice scores.  See
+        bpf_planar_pose_moments in include/badger_pf.h."""
+        if self.map is not None:
+            self.map.upload()
+        rp, ap = data.pointers()
+        return _pose_moments(self.e, poses, xy_radius, theta_radius, scores,
+                             lambda p, n, out, sp: self.e.lib.bpf_planar_pose_moments(
+                                 self.e.h, rp, ap, data.range_count_, data.range_max_, p, n, int(xy_radius),
+                                 float(xy_step), int(theta_radius), float(theta_step), float(baseline), out, sp))
+
 
 # one row of a pose search: bpf_pose_hit
 POSE_HIT_DTYPE = np.dtype([("pose", "<f8", (3,)), ("score", "<f8"), ("candidate", "<i8"), ("i", "<i4"), ("j", "<i4"),
@@ -600,6 +613,49 @@ def _refine_poses(engine, poses, levels, trace, call):
     engine.check(call(_dp(xyt), n, rows.ctypes.data_as(C.POINTER(_lib.PoseRefined)),
                       tr.ctypes.data_as(C.POINTER(C.c_int)) if trace else None))
     return (rows[:n], tr[:n]) if trace else rows[:n]
+
+
+# one row of pose moments: bpf_pose_moments
+POSE_MOMENTS_DTYPE = _lib.POSE_MOMENTS_DTYPE
+MOMENTS_VALID, MOMENTS_FACE_X, MOMENTS_FACE_Y, MOMENTS_FACE_THETA = 1, 2, 4, 8
+
+
+def _pose_moments(engine, poses, xy_radius, theta_radius, scores, call):
+    """the marshalling both scanners' poseMoments share: call(poses*, n, rows*, scores* or None) -> status"""
+    poses = np.asarray(poses)
+    if poses.dtype.names and "pose" in poses.dtype.names:  # hit rows and refined rows alike
+        poses = poses["pose"]
+    xyt = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    n = xyt.shape[0]
+    rows = np.zeros(max(n, 1), dtype=POSE_MOMENTS_DTYPE)
+    sc = None
+    if scores:
+        side, turns = 2 * max(int(xy_radius), 0) + 1, 2 * max(int(theta_radius), 0) + 1
+        sc = np.zeros((max(n, 1), min(side * side * turns, 2048)), dtype=np.float64)
+    engine.check(call(_dp(xyt), n, rows.ctypes.data_as(C.POINTER(_lib.PoseMoments)), _dp(sc) if scores else None))
+    return (rows[:n], sc[:n]) if scores else rows[:n]
+
+
+def mixtureApplyMoments(mixture, moments, sigma_floor, sigma_cap, take_mean=False):
+    """The rotation and sigma (with take_mean also the mean) of every component of `mixture` -- what mixtureFromHits
+    returned: (components, source_row, merged) -- from the row of `moments` (POSE_MOMENTS_DTYPE, one per hit row) it
+    came from: eigenvectors and clamped eigenvalues of the row's covariance.  A component whose row is invalid keeps
+    what it had.  Returns a new component array.  Plain host code, needs no GPU.  See
+    bpf_pose_mixture_apply_moments in include/badger_pf.h."""
+    comps = np.array(mixture[0], dtype=MIXTURE_COMPONENT_DTYPE).reshape(-1)
+    src = np.ascontiguousarray(mixture[1], dtype=np.int32).reshape(-1)
+    assert src.shape[0] == comps.shape[0]
+    rows = np.ascontiguousarray(moments, dtype=POSE_MOMENTS_DTYPE).reshape(-1)
+    lo = np.ascontiguousarray(sigma_floor, dtype=np.float64).reshape(-1)
+    hi = np.ascontiguousarray(sigma_cap, dtype=np.float64).reshape(-1)
+    assert lo.size == 3 and hi.size == 3
+    rc = _lib.load().bpf_pose_mixture_apply_moments(
+        comps.ctypes.data_as(C.POINTER(_lib.MixtureComponent)), comps.shape[0],
+        src.ctypes.data_as(C.POINTER(C.c_int)), rows.ctypes.data_as(C.POINTER(_lib.PoseMoments)), rows.shape[0],
+        _dp(lo), _dp(hi), 1 if take_mean else 0)
+    if rc != 0:
+        raise BpfError(rc, _lib.load().bpf_error_string(rc).decode())
+    return comps
 
 
 def pose_refine_lattice(xy_radius, theta_radius):
@@ -797,6 +853,18 @@ class PointCloudScanner:
         return _refine_poses(self.e, poses, levels, trace, lambda p, n, out, tr: self.e.lib.bpf_cloud_refine_poses(
             self.e.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], p, n, int(xy_radius), float(xy_step),
             int(theta_radius), float(theta_step), int(levels), out, tr))
+
+    def poseMoments(self, data, poses, xy_radius, xy_step, theta_radius, theta_step, baseline, scores=False):
+        """NOT a reference method: the score-weighted first and second moments of one refinement lattice (steps as
+        given) around every pose of `poses` (an [n, 3] array, hit rows or refined rows) against the cloud `data`, on
+        the device.  Returns a POSE_MOMENTS_DTYPE array in the input order, with scores=True also the [n, M] lattice
+        scores.  See bpf_cloud_pose_moments in include/badger_pf.h."""
+        pts = data.points_
+        return _pose_moments(self.e, poses, xy_radius, theta_radius, scores,
+                             lambda p, n, out, sp: self.e.lib.bpf_cloud_pose_moments(
+                                 self.e.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], p, n,
+                                 int(xy_radius), float(xy_step), int(theta_radius), float(theta_step),
+                                 float(baseline), out, sp))
 
 
 def uniform_pose_retries(threshold, multiplier):

@@ -97,6 +97,19 @@ struct PoseMixture
   std::vector<MixtureComponent> components;
   std::vector<int> source_row;
   std::vector<int> merged;
+
+  // The rotation and sigma (with take_mean also the mean) of every component from the row of `moments` (poseMoments
+  // of the rows the mixture was made from) it came from: eigenvectors and clamped eigenvalues of the row's covariance;
+  // a component whose row is invalid keeps what it had.  Host code, no engine: bpf_pose_mixture_apply_moments.
+  void mixtureApplyMoments(const std::vector<bpf_pose_moments>& moments, const std::array<double, 3>& sigma_floor,
+                           const std::array<double, 3>& sigma_cap, bool take_mean = false)
+  {
+    const int rc = bpf_pose_mixture_apply_moments(components.data(), (int)components.size(), source_row.data(),
+                                                  moments.data(), (int)moments.size(), sigma_floor.data(),
+                                                  sigma_cap.data(), take_mean ? 1 : 0);
+    if (rc != BPF_OK)
+      throw std::runtime_error(std::string("bpf_pose_mixture_apply_moments: ") + bpf_error_string(rc));
+  }
 };
 
 // Mixture components from pose-search hits or refined rows (bpf_pose_hit, bpf_pose_refined: anything with .pose and
@@ -508,6 +521,54 @@ public:
   {
     return refinePoses(data, posesOfHits(hits), xy_radius, xy_step, theta_radius, theta_step, levels, trace_out);
   }
+  // NOT a reference method (bpf_planar_pose_moments): the score-weighted first and second moments of one refinement
+  // lattice (steps as given) around every pose of `poses_xyt` (x, y, theta triples) against `data` on the device; row
+  // r describes pose r.  scores_out, when given, receives the lattice scores, poses.size() / 3 * M doubles.
+  std::vector<bpf_pose_moments> poseMoments(std::shared_ptr<PlanarData> data, const std::vector<double>& poses_xyt,
+                                            int xy_radius, double xy_step, int theta_radius, double theta_step,
+                                            double baseline, std::vector<double>* scores_out = nullptr)
+  {
+    if (map_)
+      map_->upload();
+    const int n = (int)(poses_xyt.size() / 3);
+    std::vector<bpf_pose_moments> rows((size_t)(n > 0 ? n : 1));
+    if (scores_out)
+      scores_out->assign((size_t)(n > 0 ? n : 1) * latticePoints(xy_radius, theta_radius), 0.0);
+    e_->check(bpf_planar_pose_moments(e_->get(), data->ranges_.data(), data->angles_.data(), data->range_count_,
+                                      data->range_max_, poses_xyt.data(), n, xy_radius, xy_step, theta_radius,
+                                      theta_step, baseline, rows.data(), scores_out ? scores_out->data() : nullptr));
+    rows.resize((size_t)n);
+    return rows;
+  }
+  // the same around the poses of a search's hits or of refined rows
+  std::vector<bpf_pose_moments> poseMoments(std::shared_ptr<PlanarData> data, const std::vector<bpf_pose_hit>& hits,
+                                            int xy_radius, double xy_step, int theta_radius, double theta_step,
+                                            double baseline, std::vector<double>* scores_out = nullptr)
+  {
+    return poseMoments(data, posesOfHits(hits), xy_radius, xy_step, theta_radius, theta_step, baseline, scores_out);
+  }
+  std::vector<bpf_pose_moments> poseMoments(std::shared_ptr<PlanarData> data,
+                                            const std::vector<bpf_pose_refined>& refined, int xy_radius,
+                                            double xy_step, int theta_radius, double theta_step, double baseline,
+                                            std::vector<double>* scores_out = nullptr)
+  {
+    return poseMoments(data, posesOfRefined(refined), xy_radius, xy_step, theta_radius, theta_step, baseline,
+                       scores_out);
+  }
+  // M of a lattice for sizing a score buffer (1 where the library would refuse the radii)
+  static size_t latticePoints(int xy_radius, int theta_radius)
+  {
+    int m = 1;
+    return bpf_pose_refine_lattice(xy_radius, theta_radius, &m, nullptr) == BPF_OK ? (size_t)m : 1;
+  }
+  static std::vector<double> posesOfRefined(const std::vector<bpf_pose_refined>& rows)
+  {
+    std::vector<double> xyt;
+    xyt.reserve(rows.size() * 3);
+    for (const auto& r : rows)
+      xyt.insert(xyt.end(), r.pose, r.pose + 3);
+    return xyt;
+  }
   // x, y, theta of every hit, packed
   static std::vector<double> posesOfHits(const std::vector<bpf_pose_hit>& hits)
   {
@@ -702,6 +763,40 @@ public:
   {
     return refinePoses(data, PlanarScanner::posesOfHits(hits), xy_radius, xy_step, theta_radius, theta_step, levels,
                        trace_out);
+  }
+  // NOT a reference method (bpf_cloud_pose_moments): the score-weighted first and second moments of one refinement
+  // lattice (steps as given) around every pose of `poses_xyt` against the cloud `data` on the device; row r describes
+  // pose r.  scores_out, when given, receives the lattice scores, poses.size() / 3 * M doubles.
+  std::vector<bpf_pose_moments> poseMoments(std::shared_ptr<PointCloudData> data, const std::vector<double>& poses_xyt,
+                                            int xy_radius, double xy_step, int theta_radius, double theta_step,
+                                            double baseline, std::vector<double>* scores_out = nullptr)
+  {
+    const int n = (int)(poses_xyt.size() / 3);
+    std::vector<bpf_pose_moments> rows((size_t)(n > 0 ? n : 1));
+    if (scores_out)
+      scores_out->assign((size_t)(n > 0 ? n : 1) * PlanarScanner::latticePoints(xy_radius, theta_radius), 0.0);
+    e_->check(bpf_cloud_pose_moments(e_->get(), data->points_.data(), data->pointCount(), poses_xyt.data(), n,
+                                     xy_radius, xy_step, theta_radius, theta_step, baseline, rows.data(),
+                                     scores_out ? scores_out->data() : nullptr));
+    rows.resize((size_t)n);
+    return rows;
+  }
+  // the same around the poses of a search's hits or of refined rows
+  std::vector<bpf_pose_moments> poseMoments(std::shared_ptr<PointCloudData> data,
+                                            const std::vector<bpf_pose_hit>& hits, int xy_radius, double xy_step,
+                                            int theta_radius, double theta_step, double baseline,
+                                            std::vector<double>* scores_out = nullptr)
+  {
+    return poseMoments(data, PlanarScanner::posesOfHits(hits), xy_radius, xy_step, theta_radius, theta_step, baseline,
+                       scores_out);
+  }
+  std::vector<bpf_pose_moments> poseMoments(std::shared_ptr<PointCloudData> data,
+                                            const std::vector<bpf_pose_refined>& refined, int xy_radius,
+                                            double xy_step, int theta_radius, double theta_step, double baseline,
+                                            std::vector<double>* scores_out = nullptr)
+  {
+    return poseMoments(data, PlanarScanner::posesOfRefined(refined), xy_radius, xy_step, theta_radius, theta_step,
+                       baseline, scores_out);
   }
   // candidates (columns kept by cell_stride x headings) of searchPoses: what a caller splits into ranges
   long long searchSpace(int headings, int cell_stride = 1, int* columns_out = nullptr)

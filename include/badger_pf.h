@@ -1317,6 +1317,76 @@ int bpf_pose_mixture_from_hits(const double* poses_xyt, const double* scores, in
                                bpf_mixture_component* out, int* source_row_out, int* merged_out,
                                int* n_components_out);
 
+/* ------------------------------------------------------------------ pose moments
+ * The shape of the score surface around a pose (a refined hit, usually): score-weighted first and second moments of
+ * ONE lattice per pose, all of it on the device.  NOT a reference call (parity unpinned by construction).
+ *
+ * Lattice, point numbering, pose expressions and scores are those of level 0 of the refinement above, with
+ * d = xy_step and q = theta_step as given (a step whose radius is 0 is not read and counts as 0.0); 1.0 everywhere
+ * with max_beams < 2.  With s_m the score of point m, in double, no contraction, evaluated as written:
+ *   s_max = the largest s_m, NaN below every number (NaN when no s_m is a number); the argmax is the refinement's
+ *           (the centre first among equal scores, then m ascending);
+ *   thr = baseline * s_max;  w_m = s_m - thr when s_m > thr, else 0 (NaN gives 0);
+ *   da = (double)(a - R), db = (double)(b - R), dt = (double)(t - A);
+ *   W = sum w;  Sa = sum w*da (Sb, St alike);  Saa = sum (w*da)*da (Sab, Sat, Sbb, Sbt, Stt alike: (w*du)*dv);
+ *   ma = Sa / W (mb, mt alike);  mean = (cx + ma*d, cy + mb*d, ctheta + mt*q);
+ *   cov_uv = ((Suv / W - mu*mv) * step_u) * step_v   with step_a = step_b = d, step_t = q.
+ * The ten sums are formed in a fixed order: 256 partial sums, partial p adding its points m = p, p + 256, ...
+ * ascending from 0.0; within each 64 consecutive partials the xor butterfly v = v + v[lane ^ off] with off = 32, 16,
+ * ..., 1; then the four results added in the order 0, 1, 2, 3.
+ * A row is valid iff s_max is a number and > 0 (then W >= (1 - baseline) * s_max > 0).  An invalid row has flags = 0,
+ * support = 0, weight_sum and cov 0.0 and the mean equal to the input pose bit for bit; score_max stays s_max (the
+ * canonical quiet NaN 0x7ff8000000000000 when no score is a number).
+ *
+ * scores_out, when not NULL, receives the n_poses * M lattice scores, scores_out[r * M + m].
+ * Limits and refusals are the refinement's (1..1024 poses, 2 <= M <= 2048, finite poses, the step rules, the
+ * BPF_ERR_NOT_CONFIGURED cases of the matching refine call) and 0 <= baseline < 1, finite; every refusal happens before
+ * anything is launched.  Read-only for a filter, like the refinement; poses are processed in groups of
+ * max(1, bpf_pose_search_window() / M), the result does not depend on the grouping, and the host waits once for the
+ * rows (the cloud form once more before its first launch, for the staging buffers). */
+typedef struct
+{
+  double mean[3];    /* x, y, theta (theta accumulated, not normalised) */
+  double cov[6];     /* xx, xy, xt, yy, yt, tt */
+  double weight_sum; /* W */
+  double score_max;  /* s_max; NaN when no lattice score is a number */
+  int support;       /* lattice points with w > 0 */
+  int flags;         /* bit 0: valid; bits 1..3: argmax on the lattice's outer face in x / y / theta (radius > 0 only) */
+} bpf_pose_moments;  /* 96 bytes in every binding */
+enum
+{
+  BPF_MOMENTS_VALID = 1,
+  BPF_MOMENTS_FACE_X = 2,
+  BPF_MOMENTS_FACE_Y = 4,
+  BPF_MOMENTS_FACE_THETA = 8
+};
+
+int bpf_planar_pose_moments(bpf_engine* e, const double* ranges, const double* angles, int range_count,
+                            double range_max, const double* poses_xyt, int n_poses, int xy_radius, double xy_step,
+                            int theta_radius, double theta_step, double baseline, bpf_pose_moments* out,
+                            double* scores_out);
+int bpf_cloud_pose_moments(bpf_engine* e, const float* points_xyz, int n_points, const double* poses_xyt, int n_poses,
+                           int xy_radius, double xy_step, int theta_radius, double theta_step, double baseline,
+                           bpf_pose_moments* out, double* scores_out);
+
+/* Moments to the rotation / sigma of mixture components.  Plain host code, needs no engine.  Component k takes row
+ * r = source_row[k]; a component whose row is invalid keeps what it had.  For a valid row:
+ *  - the symmetric 3 x 3 cov goes through cyclic Jacobi: pairs (0,1), (0,2), (1,2) per sweep, a rotation skipped when
+ *    the off-diagonal entry is exactly 0, at most 8 sweeps, stopping early when all three off-diagonal entries are 0;
+ *    tau = (a_qq - a_pp) / (2 a_pq), t = sign(tau) / (|tau| + sqrt(tau^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c; only
+ *    + - * / and sqrt, no contraction; eigenvalues stay in diagonal order (not sorted);
+ *  - rotation = the eigenvectors as columns, row-major (the cr_ of bpf_pf_init_with_gaussian);
+ *  - sigma[i] = sqrt(lambda_i clamped to [floor_j^2, cap_j^2]) with j the axis (x, y, theta) on which eigenvector i
+ *    has its largest absolute entry, the lowest axis winning ties;
+ *  - take_mean != 0: mean = the moments' mean, theta normalised (fmod form); otherwise the mean is untouched;
+ *  - count is untouched.
+ * BPF_ERR_INVALID_ARGUMENT: a NULL array, n_components or n_rows outside [1, 1024], a source_row entry outside
+ * [0, n_rows), a negative or non-finite floor or cap, cap < floor, a non-finite cov in a valid row (used by a
+ * component or not); nothing is written then. */
+int bpf_pose_mixture_apply_moments(bpf_mixture_component* comps, int n_components, const int* source_row,
+                                   const bpf_pose_moments* rows, int n_rows, const double sigma_floor[3],
+                                   const double sigma_cap[3], int take_mean);
+
 /* ------------------------------------------------------------------ measurement */
 /* free / total device memory as hipMemGetInfo reports it (diagnostic; used by the leak test) */
 int bpf_device_memory_info(int device_ordinal, size_t* free_bytes, size_t* total_bytes);
