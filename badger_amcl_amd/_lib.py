@@ -32,6 +32,16 @@ class PoseHit(C.Structure):
                 ("j", C.c_int), ("heading", C.c_int), ("reserved", C.c_int)]
 
 
+class PoseSearchStats(C.Structure):
+    _fields_ = [(name, C.c_longlong) for name in (
+        "candidates", "block_candidates", "seed_candidates", "pruned_block_candidates", "expanded_block_candidates",
+        "scored_candidates", "windows")]
+
+
+assert C.sizeof(PoseSearchStats) == 56  # bpf_pose_search_stats
+POSE_SEARCH_BLOCKS = (2, 4, 8, 16, 32, 64)  # the block sizes bpf_planar_search_poses_pruned takes
+
+
 class PoseRefined(C.Structure):
     _fields_ = [("pose", C.c_double * 3), ("score", C.c_double), ("score_in", C.c_double), ("moved", C.c_int),
                 ("reserved", C.c_int)]
@@ -248,6 +258,14 @@ SIGNATURES = {
     "bpf_planar_search_space": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _ip]),
     "bpf_pose_search_merge": (C.c_int, [C.POINTER(PoseHit), _ip, C.c_int, C.c_int, C.POINTER(PoseHit), _ip]),
     "bpf_pose_search_window": (C.c_int, []),
+    "bpf_planar_search_poses_pruned": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                 C.c_int, C.c_int, C.c_int, C.POINTER(PoseHit), _ip,
+                                                 C.POINTER(PoseSearchStats)]),
+    "bpf_planar_search_blocks": (C.c_int, [_vp, C.c_int, C.c_int, _ip]),
+    "bpf_planar_search_pooled_lut": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_ushort), C.c_longlong,
+                                               C.POINTER(C.c_longlong), _ip, _ip]),
+    "bpf_planar_search_bounds": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                           C.c_longlong, C.c_longlong, _dp]),
     "bpf_cloud_search_poses": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_longlong,
                                          C.c_longlong, C.c_int, C.POINTER(PoseHit), _ip]),
     "bpf_cloud_search_space": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _ip]),

@@ -44,6 +44,7 @@
 #include "kernels_shard_rebalance.hpp"
 #include "kernels_score.hpp"
 #include "kernels_window.hpp"
+#include "kernels_pose_search_pruned.hpp"
 
 using namespace bpf;
 
@@ -88,6 +89,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_pose_array.inl"
 #include "abi_pose_search.inl"
 #include "abi_pose_search_cloud.inl"
+#include "abi_pose_search_pruned.inl"
 #include "abi_pose_refine.inl"
 #include "abi_pose_moments.inl"
 #include "abi_bootstrap.inl"

@@ -168,6 +168,8 @@ struct FieldRequest
   const double4* aos = nullptr;  // non-null: the n particles are still 32-byte records there (device-visible memory);
                                  // the prep launch unpacks them into `p` as it goes (k_field_prep_aos)
   const FieldHostOut* host_out = nullptr;  // non-null: a host-out form of the scoring kernel
+  const uint16_t* bound_tiles = nullptr;   // non-null: the bound pass of the pruned pose search -- the kernel gathers
+                                           // from this image (the layout of lut_tiles) under neutral map factors
 };
 
 // What the last weight pass left behind for the passes that follow it.  Invariant: a field that is set describes the
@@ -486,6 +488,39 @@ struct bpf_engine
   DevBuf<bpf_pose_hit> d_search_hits;  // [kSearchMaxK] the rows on their way to the host
   PinnedBuf<bpf_pose_hit> h_search_hits;
   PinnedBuf<int> h_search_count;
+
+  // ---- pruned pose search (kernels_pose_search_pruned.hpp, abi_pose_search_pruned.inl): one pooled image per
+  // (map version, B) and one block list per (map version, radius, stride, B), a slot per allowed B (log2 B - 1), so
+  // that calls with different B do not evict each other; then the working arrays of a call
+  struct PrunePool
+  {
+    DevBuf<uint16_t> tiles;  // P_B in the layout of d_lut_tiles
+    int map_version = -1;
+  } prune_pool[6];
+  DevBuf<uint16_t> d_prune_rows;  // the row pass of a pooled image under construction, padded row-major
+  struct PruneList
+  {
+    DevBuf<int> start, member;  // CSR over F_s
+    DevBuf<int2> anchor;
+    std::vector<int> h_start;
+    int n_blocks = 0, max_members = 0;
+    int map_version = -1, stride = 0;
+    double radius = -1.0;
+  } prune_list[6];
+  DevBuf<double> d_prune_bounds;        // [block candidates of the call]
+  DevBuf<uint8_t> d_prune_in_seed;      // [block candidates of the call]
+  DevBuf<SearchEntry> d_prune_best;     // [kSearchMaxK] the best bounds, ids = block candidates of the call
+  DevBuf<int> d_prune_best_count;       // [1]
+  DevBuf<int> d_prune_seed;             // [1024] seed_q, [1025] seed_off behind it
+  DevBuf<long long> d_prune_ids;        // [window] candidate of every slot, -1 for an empty one
+  DevBuf<int> d_prune_surv;             // [chunks * 1024] surv_q, then as many surv_off
+  DevBuf<uint8_t> d_prune_state;        // [chunks * 1024] per survivor: 0 undecided, 1 dropped, 2 expanded
+  DevBuf<int2> d_prune_chunks;          // [chunks] (survivors, their members)
+  DevBuf<long long> d_prune_chunk_off;  // [chunks + 1] members before a chunk, from the host
+  DevBuf<unsigned long long> d_prune_words;  // [kPruneWords]
+  PinnedBuf<int2> h_prune_chunks;
+  PinnedBuf<long long> h_prune_chunk_off;
+  PinnedBuf<unsigned long long> h_prune_words;
 
   // ---- pose refinement (kernels_pose_refine.hpp, abi_pose_refine.inl): the centres of the descent and what
   // k_refine_select keeps per pose.  The lattice poses live in `cand`; nothing here describes the particle set

@@ -372,6 +372,12 @@ FieldScoreArgs field_args(const bpf_engine* e, ParticlesDev p, int n, const Scan
     A.w_host = req.host_out->w_host;
     A.rec = req.host_out->rec;
   }
+  if (req.bound_tiles != nullptr)
+  {
+    A.map.lut_tiles = req.bound_tiles;
+    A.off_map_factor = 1.0;
+    A.non_free_factor = 1.0;
+  }
   return A;
 }
 
@@ -821,7 +827,7 @@ int score_beam_model(bpf_engine* e, ParticlesDev p, int n, const double* ranges,
 
 // The likelihood-field family without beam skipping: one pass over every valid beam.
 int score_field_plain(bpf_engine* e, ParticlesDev p, int n, const double* ranges, const double* angles, int rc,
-                      double range_max, bool want_partials, const double4* aos)
+                      double range_max, bool want_partials, const double4* aos, const uint16_t* bound_tiles)
 {
   StagedSlot s;
   FieldScan fs;
@@ -830,6 +836,7 @@ int score_field_plain(bpf_engine* e, ParticlesDev p, int n, const double* ranges
   FieldRequest req;
   req.want_partials = want_partials;
   req.aos = aos;
+  req.bound_tiles = bound_tiles;
   H2D_OR_RETURN(launch_field(e, p, n, s.get(), fs, req));
   return s.commit();
 }
@@ -870,7 +877,8 @@ int score_field_beamskip_count(bpf_engine* e, ParticlesDev p, int n, const doubl
 // for the other forms).
 int score_planar(bpf_engine* e, ParticlesDev p, int n, int set_converged, const double* ranges,
                  const double* angles, int rc, double range_max, bool* forced_zero, bool want_partials = false,
-                 bool defer_beamskip_pass2 = false, const double4* aos = nullptr)
+                 bool defer_beamskip_pass2 = false, const double4* aos = nullptr,
+                 const uint16_t* bound_tiles = nullptr)
 {
   *forced_zero = false;
   e->weights_overwritten();
@@ -883,6 +891,10 @@ int score_planar(bpf_engine* e, ParticlesDev p, int n, int set_converged, const 
   if (rc <= 0 || ranges == nullptr || angles == nullptr || n <= 0)
     return e->fail(BPF_ERR_INVALID_ARGUMENT, "empty scan or sample set");
   const bool beam = e->pm.model == BPF_MODEL_BEAM, beamskip = e->pm.beamskip_armed(set_converged != 0);
+  // a bound pass (bound_tiles, FieldRequest) exists for the plain likelihood-field launch only: the window route and
+  // the tile form, which want_partials opens, read the engine's own LUT image
+  if (bound_tiles != nullptr && (beam || beamskip || want_partials || aos != nullptr))
+    return e->fail(BPF_ERR_UNSUPPORTED, "bound pass: plain likelihood-field scoring without partials only");
   e->evals_last = 0;
   if (aos != nullptr && (beam || beamskip))
   {
@@ -893,7 +905,7 @@ int score_planar(bpf_engine* e, ParticlesDev p, int n, int set_converged, const 
   if (beam)
     return score_beam_model(e, p, n, ranges, angles, rc, range_max);
   if (!beamskip)
-    return score_field_plain(e, p, n, ranges, angles, rc, range_max, want_partials, aos);
+    return score_field_plain(e, p, n, ranges, angles, rc, range_max, want_partials, aos, bound_tiles);
   H2D_OR_RETURN(score_field_beamskip_count(e, p, n, ranges, angles, rc, range_max));
   if (defer_beamskip_pass2)
     return BPF_OK;  // sharded: the per-beam counts are summed over the shards first

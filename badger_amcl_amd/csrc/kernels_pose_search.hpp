@@ -149,12 +149,14 @@ __device__ __forceinline__ void search_sort_lds(SearchEntry* s, int P)
 // Block b takes scores[b * kSearchTile ...) of the window's n (candidates c0 + index).  best / best_count: the running
 // list of the windows before this one (sorted, best first); with K entries in it, a candidate strictly below the
 // K-th is dropped.  Output: tile_out[b * K ...) = the tile's best min(K, kept), best first; tile_count[b] = how many.
-__global__ __launch_bounds__(kSearchThreads) void k_search_select(const double* __restrict__ scores, int n,
-                                                                  long long c0, int K,
-                                                                  const SearchEntry* __restrict__ best,
-                                                                  const int* __restrict__ best_count,
-                                                                  SearchEntry* __restrict__ tile_out,
-                                                                  int* __restrict__ tile_count)
+// The body serves two kernels: the candidate of slot idx is c0 + idx (IDS false: k_search_select) or ids[idx], a
+// negative id marking an empty slot (IDS true: k_prune_select, kernels_pose_search_pruned.hpp).
+template <bool IDS>
+__device__ __forceinline__ void search_select_tile(const double* __restrict__ scores, int n, long long c0,
+                                                   const long long* __restrict__ ids, int K,
+                                                   const SearchEntry* __restrict__ best,
+                                                   const int* __restrict__ best_count,
+                                                   SearchEntry* __restrict__ tile_out, int* __restrict__ tile_count)
 {
   __shared__ SearchEntry s[kSearchTile];
   __shared__ int kept;
@@ -173,9 +175,13 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_select(const double* 
     bool keep = false;
     if (idx < n)
     {
-      en.key = search_key_of(scores[idx]);
-      en.inv = ~(unsigned long long)(c0 + (long long)idx);
-      keep = en.key >= floor_key;
+      const long long c = IDS ? ids[idx] : c0 + (long long)idx;
+      if (!IDS || c >= 0)
+      {
+        en.key = search_key_of(scores[idx]);
+        en.inv = ~(unsigned long long)c;
+        keep = en.key >= floor_key;
+      }
     }
     const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
     int at = 0;
@@ -205,6 +211,16 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_select(const double* 
     tile_out[(size_t)blockIdx.x * K + t] = s[t];
   if (tid == 0)
     tile_count[blockIdx.x] = out_n;
+}
+
+__global__ __launch_bounds__(kSearchThreads) void k_search_select(const double* __restrict__ scores, int n,
+                                                                  long long c0, int K,
+                                                                  const SearchEntry* __restrict__ best,
+                                                                  const int* __restrict__ best_count,
+                                                                  SearchEntry* __restrict__ tile_out,
+                                                                  int* __restrict__ tile_count)
+{
+  search_select_tile<false>(scores, n, c0, nullptr, K, best, best_count, tile_out, tile_count);
 }
 
 // One block: best[0 .. *best_count) (sorted) and every tile's sorted list -> the best K of them all, sorted, back in

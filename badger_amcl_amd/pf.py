@@ -41,6 +41,10 @@ OPT_HOST_DIRECT_PAGEABLE = 15  # pageable buffers straight to the HIP runtime (t
 OPT_FUSED_LDS_TREE = 16  # the LDS form of the single-block resample's histogram tree (tests)
 OPT_STAGE_ON_HOST = 17  # the host forms the scan's end points always (A/B switch of the device staging)
 CELL_FREE, CELL_UNKNOWN, CELL_OCCUPIED = -1, 0, 1
+# pruned pose search: the block sizes it takes and the default (profiles/pose_search_pruned.md)
+POSE_SEARCH_BLOCKS = _lib.POSE_SEARCH_BLOCKS
+POSE_SEARCH_BLOCK = 8
+POSE_SEARCH_STATS_FIELDS = tuple(name for name, _ in _lib.PoseSearchStats._fields_)
 
 
 class BpfError(RuntimeError):
@@ -562,6 +566,63 @@ class PlanarScanner:
             self.e.h, rp, ap, data.range_count_, data.range_max_, int(headings), int(cell_stride), int(first),
             int(count), int(k), hits.ctypes.data_as(C.POINTER(_lib.PoseHit)), C.byref(n)))
         return hits[:n.value]
+
+    def searchBlocks(self, cell_stride=1, block=POSE_SEARCH_BLOCK):
+        """Blocks of block x block cells that hold an entry of the strided free list: what a caller of
+        searchPosesPruned splits into ranges."""
+        if self.map is not None:
+            self.map.upload()
+        n = C.c_int()
+        self.e.check(self.e.lib.bpf_planar_search_blocks(self.e.h, int(cell_stride), int(block), C.byref(n)))
+        return n.value
+
+    def searchPosesPruned(self, data, headings, cell_stride, k, block=POSE_SEARCH_BLOCK, first_block=0,
+                          block_count=-1, stats=False):
+        """NOT a reference method: the rows of searchPoses over the candidates whose cells lie in blocks first_block
+        .. first_block + block_count - 1 of the block list, bit for bit, from fewer exact evaluations (likelihood
+        field and Gompertz only).  stats=True: (hits, dict of the bpf_pose_search_stats fields).  See
+        bpf_planar_search_poses_pruned in include/badger_pf.h."""
+        if self.map is not None:
+            self.map.upload()
+        hits = np.zeros(max(int(k), 1), dtype=POSE_HIT_DTYPE)
+        n = C.c_int()
+        st = _lib.PoseSearchStats()
+        rp, ap = data.pointers()
+        self.e.check(self.e.lib.bpf_planar_search_poses_pruned(
+            self.e.h, rp, ap, data.range_count_, data.range_max_, int(headings), int(cell_stride), int(block),
+            int(first_block), int(block_count), int(k), hits.ctypes.data_as(C.POINTER(_lib.PoseHit)), C.byref(n),
+            C.byref(st)))
+        if stats:
+            return hits[:n.value], {name: getattr(st, name) for name, _ in _lib.PoseSearchStats._fields_}
+        return hits[:n.value]
+
+    def searchPooledLUT(self, block=POSE_SEARCH_BLOCK):
+        """(tiles, ltx, lty): the min-pooled LUT image searchPosesPruned bounds with, uint16 codes (level * 8) in the
+        engine's 8x8-tiled layout.  For diagnosis and tests."""
+        if self.map is not None:
+            self.map.upload()
+        n, ltx, lty = C.c_longlong(), C.c_int(), C.c_int()
+        self.e.check(self.e.lib.bpf_planar_search_pooled_lut(self.e.h, int(block), None, 0, C.byref(n),
+                                                             C.byref(ltx), C.byref(lty)))
+        out = np.zeros(n.value, dtype=np.uint16)
+        self.e.check(self.e.lib.bpf_planar_search_pooled_lut(
+            self.e.h, int(block), out.ctypes.data_as(C.POINTER(C.c_ushort)), n.value, C.byref(n), C.byref(ltx),
+            C.byref(lty)))
+        return out, ltx.value, lty.value
+
+    def searchBounds(self, data, headings, cell_stride, block=POSE_SEARCH_BLOCK, first_q=0, count=-1):
+        """The upper bounds searchPosesPruned prunes with, as a float64 array: block candidate q = block_index *
+        headings + h, first_q .. first_q + count - 1.  For diagnosis and tests."""
+        if self.map is not None:
+            self.map.upload()
+        if count < 0:
+            count = self.searchBlocks(cell_stride, block) * int(headings) - int(first_q)
+        out = np.zeros(max(int(count), 1), dtype=np.float64)
+        rp, ap = data.pointers()
+        self.e.check(self.e.lib.bpf_planar_search_bounds(
+            self.e.h, rp, ap, data.range_count_, data.range_max_, int(headings), int(cell_stride), int(block),
+            int(first_q), int(count), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out[:max(int(count), 0)]
 
     def refinePoses(self, data, poses, xy_radius, xy_step, theta_radius, theta_step, levels, trace=False):
         """NOT a reference method: coarse-to-fine lattice descent around every pose of `poses` (an [n, 3] array or a

@@ -495,6 +495,32 @@ public:
     hits.resize((size_t)n);
     return hits;
   }
+  // NOT a reference method (bpf_planar_search_poses_pruned): the rows of searchPoses over the candidates whose cells
+  // lie in blocks first_block .. first_block + block_count - 1 (block_count = -1: to the end) of the list of
+  // block x block cell blocks, bit for bit, from fewer exact evaluations.  Likelihood field and Gompertz only.
+  std::vector<bpf_pose_hit> searchPosesPruned(std::shared_ptr<PlanarData> data, int headings, int cell_stride, int k,
+                                              int block = 8, int first_block = 0, int block_count = -1,
+                                              bpf_pose_search_stats* stats_out = nullptr)
+  {
+    if (map_)
+      map_->upload();
+    std::vector<bpf_pose_hit> hits((size_t)(k > 0 ? k : 1));
+    int n = 0;
+    e_->check(bpf_planar_search_poses_pruned(e_->get(), data->ranges_.data(), data->angles_.data(),
+                                             data->range_count_, data->range_max_, headings, cell_stride, block,
+                                             first_block, block_count, k, hits.data(), &n, stats_out));
+    hits.resize((size_t)n);
+    return hits;
+  }
+  // blocks in that list: what a caller of searchPosesPruned splits into ranges
+  int searchBlocks(int cell_stride = 1, int block = 8)
+  {
+    if (map_)
+      map_->upload();
+    int n = 0;
+    e_->check(bpf_planar_search_blocks(e_->get(), cell_stride, block, &n));
+    return n;
+  }
   // NOT a reference method (bpf_planar_refine_poses): coarse-to-fine lattice descent around every pose of `poses_xyt`
   // (x, y, theta triples) against `data` on the device; row r refines pose r.  trace_out, when given, receives the
   // lattice point chosen per (pose, level), poses.size() / 3 * levels ints.

@@ -1207,6 +1207,63 @@ int bpf_pose_search_merge(const bpf_pose_hit* lists, const int* list_lengths, in
 /* candidates scored per window, an internal constant the tests size their cases from; needs no engine */
 int bpf_pose_search_window(void);
 
+/* The same search, pruned: the rows of bpf_planar_search_poses, bit for bit, from fewer exact evaluations.  NOT a
+ * reference call.  Likelihood field and likelihood-field Gompertz only.
+ *
+ * block B (one of 2, 4, 8, 16, 32, 64) cuts the map into B x B blocks of cells: block (bi, bj) holds the cells with
+ * i / B == bi and j / B == bj.  The block list holds the blocks with at least one entry of F_s, bi outer, bj inner.
+ * Block candidate q = block_index * headings + h stands for the candidates c = f * headings + h of the exhaustive
+ * search whose cell F_s[f] lies in the block (its members); numbering, poses and scores of the candidates are those
+ * of bpf_planar_search_poses.  The bound of q is the block's anchor pose -- the cell (bi * B, bj * B), free or not,
+ * at heading h -- scored by the same scoring path against a min-pooled copy of the LUT image, with neutral map
+ * factors, times max(1, off_map_factor, non_free_factor); for Gompertz a small margin is added.  bound(q) >=
+ * score(c), as doubles, for every member c ("Pose search, pruned form").
+ *
+ * The call scores every bound, then the members of the min(1024, count) block candidates of the best bounds exactly
+ * (the seed, as large as the bound list whatever k is); tau is the k-th best exact score once k are known.  A block
+ * candidate with bound < tau is never expanded; the others are, in windows of at most bpf_pose_search_window()
+ * members, each checked once more against the tau of that moment.  A NaN bound is never pruned; equal scores keep
+ * their order by candidate.  The host waits twice: once for the number of surviving block candidates, once for the
+ * rows.
+ *
+ * first_block / block_count select a range of the block list (block_count = -1: to its end), so that a sharded
+ * caller can split the space; lists of disjoint ranges merge with bpf_pose_search_merge.
+ *
+ * Status: BPF_ERR_UNSUPPORTED, before anything is launched, for the prob and beam models, for a Gompertz whose a, b,
+ * c or input_scale is not > 0, for map factors that are negative or NaN, and for a per-level term table that is not
+ * non-increasing over levels 0 .. K.  BPF_ERR_INVALID_ARGUMENT for a block that is not in the list, a range outside
+ * the block list, and what bpf_planar_search_poses refuses.  BPF_ERR_CAPACITY for |F_s| * headings > 2^31 - 1 and
+ * for more than 2^24 block candidates in one call (18 bytes of device memory each, about 300 MB at the limit; split
+ * the range, or raise block).  With max_beams < 2 every score is 1.0, as in the exhaustive call.  Read-only for the
+ * filter, exactly as bpf_planar_search_poses is. */
+typedef struct
+{
+  long long candidates;               /* what bpf_planar_search_poses would score for the same range */
+  long long block_candidates;         /* = seed_candidates + pruned_block_candidates + expanded_block_candidates */
+  long long seed_candidates;          /* block candidates expanded as the seed */
+  long long pruned_block_candidates;  /* never expanded: below tau behind the seed, or at their window */
+  long long expanded_block_candidates;
+  long long scored_candidates;        /* exact evaluations: members of the seed and of the expanded */
+  long long windows;                  /* scoring launches of the call: bound, seed and expansion windows */
+} bpf_pose_search_stats;
+
+int bpf_planar_search_poses_pruned(bpf_engine* e, const double* ranges, const double* angles, int range_count,
+                                   double range_max, int headings, int cell_stride, int block, int first_block,
+                                   int block_count, int k, bpf_pose_hit* hits_out, int* n_hits_out,
+                                   bpf_pose_search_stats* stats_out /* nullable */);
+/* number of blocks in the block list of (cell_stride, block) for the current map and radius */
+int bpf_planar_search_blocks(bpf_engine* e, int cell_stride, int block, int* n_blocks_out);
+/* the pooled image P_B of the current map as the bound pass reads it: ltx * lty tiles of 64 u16 codes (level * 8),
+ * the layout of the engine's LUT image.  *n_out = entries of the image; tiles_out may be null to ask for the size
+ * alone, otherwise capacity >= *n_out entries.  For diagnosis and for the tests. */
+int bpf_planar_search_pooled_lut(bpf_engine* e, int block, unsigned short* tiles_out, long long capacity,
+                                 long long* n_out, int* ltx_out, int* lty_out);
+/* the bounds the pruning uses, as doubles, of the block candidates first_q .. first_q + count - 1 (q over the whole
+ * block list; count = -1: to the end).  For diagnosis and for the tests; refusals as above. */
+int bpf_planar_search_bounds(bpf_engine* e, const double* ranges, const double* angles, int range_count,
+                             double range_max, int headings, int cell_stride, int block, long long first_q,
+                             long long count, double* bounds_out);
+
 /* The same search with the 3-D map and the cloud scanner: Node3D's global localisation without the lottery over the
  * columns of the map's bounding rectangle.  NOT a reference call (parity unpinned by construction).
  *
