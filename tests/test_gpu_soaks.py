@@ -22,7 +22,7 @@ def engine():
 @pytest.mark.parametrize("tool,cases", [("soak_score", 500), ("soak_resample", 300), ("soak_cycle", 100),
                                         ("soak_cloud", 30), ("soak_motion", 600), ("soak_stats", 100),
                                         ("soak_lut", 300), ("soak_rays", 80), ("soak_recovery", 60),
-                                        ("soak_sequences", 36)])
+                                        ("soak_sequences", 36), ("soak_long_rays", 6)])
 def test_randomised_soak_against_the_oracle(engine, tool, cases):
     mod = importlib.import_module(tool)
     assert mod.run(cases, seed=977, e=engine) == 0
