@@ -176,6 +176,7 @@ SIGNATURES = {
     "bpf_shard_stats_label_dev": (C.c_int, [_vp, _vp, _ip, C.c_int, C.c_int, _ip]),
     "bpf_shard_stats_local_sums_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "bpf_shard_stats_finish_dev": (C.c_int, [_vp, _vp]),
+    "bpf_shard_stats_finish_installed": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "bpf_shard_stats_host": (C.c_int, [_vp, _dp, C.c_int]),
     "bpf_shard_init_with_gaussian": (C.c_int, [_vp, _dp, _dp, _dp, C.c_longlong, C.c_int, C.c_longlong]),
     "bpf_shard_init_with_random_poses": (C.c_int, [_vp, C.c_longlong, C.c_int, C.c_longlong]),

@@ -171,13 +171,13 @@ int inplace_xy_sums(bpf_engine* e, SampleSet& s, int n)
     return rc;
   long long* p = e->d_ip_words.p;
   HIPCHK(e, hipMemsetAsync(p, 0, 32 * sizeof(long long), e->stream));
-  long long* acc_hi = p + 24;
+  long long *acc_hi = p + 24, *acc_top = p + 26;
   unsigned long long* acc_lo = reinterpret_cast<unsigned long long*>(p + 28);
   if (n > 0)
     hipLaunchKernelGGL(k_inplace_xy_sums, dim3(std::min(blocks_for(n, 256), 1024)), dim3(256), 0, e->stream,
-                       (const double*)s.x.p, (const double*)s.y.p, n, acc_hi, acc_lo, p);
-  hipLaunchKernelGGL(k_sstat_export, dim3(1), dim3(64), 0, e->stream, (const long long*)acc_hi,
-                     (const unsigned long long*)acc_lo, 2, p);
+                       (const double*)s.x.p, (const double*)s.y.p, n, acc_top, acc_hi, acc_lo, p);
+  hipLaunchKernelGGL(k_inplace_export, dim3(1), dim3(64), 0, e->stream, (const long long*)acc_top,
+                     (const long long*)acc_hi, (const unsigned long long*)acc_lo, p);
   HIPCHK(e, hipGetLastError());
   return BPF_OK;
 }

@@ -204,7 +204,8 @@ int shard_ensure_stats(bpf_engine* e)
       rc = bpf_shard_stats_finish_dev(e, sums);
       if (rc != BPF_OK)
         return rc;
-      route = BPF_SHARD_STATS_ROUTE_DISTRIBUTED;
+      // sums beyond the fixed-point format: every rank read the same reduced words and decides alike
+      route = e->ss_finish_installed ? BPF_SHARD_STATS_ROUTE_DISTRIBUTED : BPF_SHARD_STATS_ROUTE_HOST;
     }
   }
   if (route == BPF_SHARD_STATS_ROUTE_HOST)

@@ -265,7 +265,7 @@ int bpf_shard_stats_local_sums_dev(bpf_engine* e, void** sums_dev, size_t* n_wor
   }
   hipLaunchKernelGGL(k_sstat_export, dim3(blocks_for(n_sums, 256)), dim3(256), 0, e->stream,
                      (const long long*)e->d_stats_hi.p, (const unsigned long long*)e->d_stats_lo.p, n_sums,
-                     e->d_ss_limbs.p);
+                     e->d_ss_limbs.p, (const int*)e->d_stats_flags.p);
   HIPCHK(e, hipGetLastError());
   *sums_dev = e->d_ss_limbs.p;
   *n_words_out = (size_t)kStatLimbs * n_sums;
@@ -302,11 +302,21 @@ int bpf_shard_stats_finish_dev(bpf_engine* e, const void* reduced_sums_dev)
   H2D_OR_RETURN(pinned_down(e, e->h_stats_result, 0, e->d_stats_result, 0, 1, e->stream));
   int rc = shard_stats_flags(e);
   e->ss_stage = 0;
+  e->ss_finish_installed = false;
   if (rc != BPF_OK)
     return rc;
   if (e->h_stats_flags.p[1] != 0)
-    return e->fail(BPF_ERR_HIP, "sharded statistics: a non-finite term the first stage did not report");
+    return BPF_OK;  // a sum beyond the fixed-point format, on every rank alike (kernels_shard_stats.hpp): the host route
   install_device_stats(e, *e->h_stats_result.p);
+  e->ss_finish_installed = true;
+  return BPF_OK;
+}
+
+int bpf_shard_stats_finish_installed(bpf_engine* e, int* installed_out)
+{
+  if (!e || !installed_out)
+    return BPF_ERR_INVALID_ARGUMENT;
+  *installed_out = e->ss_finish_installed ? 1 : 0;
   return BPF_OK;
 }
 

@@ -592,6 +592,7 @@ struct bpf_engine
 
   // ---- cluster statistics of a sharded set (kernels_shard_stats.hpp, abi_shard_stats.inl)
   int ss_stage = 0;                 // 0 none, 1 local bins listed, 2 bins merged and labelled, 3 local sums exported
+  bool ss_finish_installed = false; // the last bpf_shard_stats_finish_dev installed its result (the sums fitted)
   long long ss_epoch = -1;          // set_epoch the stages in progress belong to
   int ss_clusters = 0;              // global cluster count (stage 2)
   unsigned ss_gmask = 0;            // global bin table size - 1 (stage 2)
@@ -614,7 +615,7 @@ struct bpf_engine
   long long slice_global = 0;       //   (-1: nobody has told the engine) and the samples of the whole set
   int ip_stage = 0;                 // 0 none, 1 selected, 2 sums exported, 3 counted
   long long ip_epoch = -1;          // set_epoch the stages in progress belong to
-  DevBuf<long long> d_ip_words;     // [kInplaceSumWords] limbs + flag, [16] the count, [24 .. 25] / [28 .. 29] acc hi / lo
+  DevBuf<long long> d_ip_words;     // [kInplaceSumWords] limbs + flag, [16] the count, [24 .. 25] / [26 .. 27] / [28 .. 29] acc hi / top / lo
   int ip_counts[kMailboxMaxWorld] = { 0 };  // every rank's new count of the last one-call in-place resample
 
   // ---- the multinomial resample of a sharded set in place (kernels_shard_inplace_mn.hpp, abi_shard_inplace_mn.inl)

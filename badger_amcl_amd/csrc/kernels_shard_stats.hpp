@@ -20,6 +20,12 @@
 //   finish       carries propagated back into (hi, lo) (k_sstat_import), then k_stats_clusters / k_stats_set of the
 //                single engine on the reduced sums: the same integers, the same finishing code, the same doubles.
 //
+// The range of the fixed-point sums (|sum| < 2^31, kernels_stats.hpp) is only known once they are formed, after the
+// last exchange.  A rank whose own additions leave the format (k_sstat_accumulate) marks every sum it exports with a
+// top limb no sum in range can reach (kStatPoison); k_sstat_import finds a top limb that does not fit its 32 bits --
+// a marked one, or a total that passed 2^31 although every rank's share fitted -- on EVERY rank alike, since all of
+// them read the same reduced words, and raises flags[1]: nothing is installed and every rank takes the host route.
+//
 // Every probe loop and every union-find walk is bounded by the table size; a bound that is hit sets flags[3] (it
 // cannot be with a table of at least twice the bins, and is reported as an error, not waited out).
 #pragma once
@@ -430,8 +436,6 @@ __global__ __launch_bounds__(256) void k_sstat_accumulate(const ShardSumsArgs A)
       t[k].lo = 0;
     }
   }
-  if (bad)
-    atomicExch(&A.flags[1], 1);
   const int first = __builtin_amdgcn_readfirstlane(cidx);
   const bool uniform = __builtin_amdgcn_ballot_w64(live && cidx != first) == 0 && first >= 0;
   if (lane == 0)
@@ -450,14 +454,14 @@ __global__ __launch_bounds__(256) void k_sstat_accumulate(const ShardSumsArgs A)
         Fx u;
         u.hi = __shfl_xor(v.hi, o, 64);
         u.lo = __shfl_xor(v.lo, o, 64);
-        v = fx_add(v, u);
+        v = fx_add(v, u, &bad);
       }
       if (lane == 0)
       {
         if (block_uniform)
-          fx_atomic_add(&s_hi[k], &s_lo[k], v);
+          bad |= fx_atomic_add(&s_hi[k], &s_lo[k], v);
         else
-          fx_atomic_add(&A.acc_hi[(size_t)k * A.clusters + first], &A.acc_lo[(size_t)k * A.clusters + first], v);
+          bad |= fx_atomic_add(&A.acc_hi[(size_t)k * A.clusters + first], &A.acc_lo[(size_t)k * A.clusters + first], v);
       }
     }
   }
@@ -465,7 +469,7 @@ __global__ __launch_bounds__(256) void k_sstat_accumulate(const ShardSumsArgs A)
   {
 #pragma unroll
     for (int k = 0; k < kStatTerms; ++k)
-      fx_atomic_add(&A.acc_hi[(size_t)k * A.clusters + cidx], &A.acc_lo[(size_t)k * A.clusters + cidx], t[k]);
+      bad |= fx_atomic_add(&A.acc_hi[(size_t)k * A.clusters + cidx], &A.acc_lo[(size_t)k * A.clusters + cidx], t[k]);
   }
   if (block_uniform)
   {
@@ -476,18 +480,31 @@ __global__ __launch_bounds__(256) void k_sstat_accumulate(const ShardSumsArgs A)
       v.hi = s_hi[threadIdx.x];
       v.lo = s_lo[threadIdx.x];
       const size_t at = (size_t)threadIdx.x * A.clusters + s_c[0];
-      fx_atomic_add(&A.acc_hi[at], &A.acc_lo[at], v);
+      bad |= fx_atomic_add(&A.acc_hi[at], &A.acc_lo[at], v);
     }
   }
+  if (bad)  // a term or a sum outside the format
+    atomicExch(&A.flags[1], 1);
 }
 
-// (hi, lo) -> four 32-bit limbs, least significant first, each in an int64; the top one keeps the sign
+// A top limb in range is below 2^31 in magnitude, sixteen of them below 2^35: a poisoned one stays out of the 32 bits
+// k_sstat_import has for it whatever the other ranks add, and sixteen of them are far from the end of the int64.
+constexpr long long kStatPoison = 1ll << 45;
+
+// (hi, lo) -> four 32-bit limbs, least significant first, each in an int64; the top one keeps the sign.  flags[1] up
+// (this rank's sums left the format): every top limb is poisoned.
 __global__ void k_sstat_export(const long long* __restrict__ acc_hi, const unsigned long long* __restrict__ acc_lo,
-                               int n_sums, long long* __restrict__ limbs)
+                               int n_sums, long long* __restrict__ limbs, const int* __restrict__ flags)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_sums)
     return;
+  if (flags[1] != 0)
+  {
+    limbs[(size_t)kStatLimbs * i + 0] = limbs[(size_t)kStatLimbs * i + 1] = limbs[(size_t)kStatLimbs * i + 2] = 0;
+    limbs[(size_t)kStatLimbs * i + 3] = kStatPoison;
+    return;
+  }
   const long long hi = acc_hi[i];
   const unsigned long long lo = acc_lo[i];
   limbs[(size_t)kStatLimbs * i + 0] = (long long)(lo & 0xFFFFFFFFull);
@@ -496,7 +513,8 @@ __global__ void k_sstat_export(const long long* __restrict__ acc_hi, const unsig
   limbs[(size_t)kStatLimbs * i + 3] = hi >> 32;
 }
 
-// limbs summed over the ranks (each below 2^36 in magnitude) -> (hi, lo) with the carries propagated
+// limbs summed over the ranks (each below 2^36 in magnitude) -> (hi, lo) with the carries propagated; a total whose top
+// limb does not fit the 32 bits left for it in `hi` raises flags[1]
 __global__ void k_sstat_import(const long long* __restrict__ limbs, int n_sums, long long* __restrict__ acc_hi,
                                unsigned long long* __restrict__ acc_lo, int* __restrict__ flags, int clusters)
 {
@@ -511,6 +529,8 @@ __global__ void k_sstat_import(const long long* __restrict__ limbs, int n_sums, 
   const long long l3 = limbs[(size_t)kStatLimbs * i + 3] + (long long)(l2 >> 32);
   acc_lo[i] = (l0 & 0xFFFFFFFFull) | (l1 << 32);
   acc_hi[i] = (long long)((l2 & 0xFFFFFFFFull) | ((unsigned long long)l3 << 32));
+  if (l3 != (long long)(int)l3)
+    atomicExch(&flags[1], 1);
 }
 
 __global__ void k_sstat_fill(double* __restrict__ w, int n, double v)

@@ -216,10 +216,20 @@ __global__ __launch_bounds__(256) void k_stats_labels(const StatsArgs A, const i
     }
 }
 
-// 32.96 fixed point: the 128-bit integer round-down of t * 2^96, as (hi, lo).  |t| < 2^31 (the largest term is
-// w x y with a weight <= 1 and coordinates of a few km); the 96 fractional bits keep every bit of a term down to
-// 2^-43 (a particle whose weight is 1e-8 still contributes 69 significant bits -- with 64 fractional bits a cluster of
-// such stragglers came out only 1e-11 accurate).
+// 32.96 fixed point: the 128-bit integer round-down of t * 2^96, as (hi, lo); the 96 fractional bits keep every bit of
+// a term down to 2^-43 (a particle whose weight is 1e-8 still contributes 69 significant bits -- with 64 fractional bits
+// a cluster of such stragglers came out only 1e-11 accurate).
+//
+// Range.  `hi` is an int64 that holds floor(t * 2^32), so the format ends at |value| < 2^31 = 2 147 483 648 -- for a
+// TERM and for every SUM of terms alike:
+//   per term   fx_from refuses |t| >= 2e9 (and NaN / inf): `bad`.  With w = 1/n that is |x| or |y| beyond ~4.4e4 sqrt(n) m.
+//   per sum    sum w x^2 ~ mean(x)^2 for normalised weights: a cluster further than sqrt(2^31) = 46 341 m from the frame's
+//              origin on one axis, or with |mean(x) mean(y)| >= 2^31, does not fit -- nor do 100 000 samples of weight 1
+//              at 150 m.  Every addition of two `hi` words (fx_add in registers, the atomics' return values, the set's
+//              sums over the clusters) is checked for signed overflow and reports it the same way: `bad`.
+// `bad` raises the flag that sends the evaluation to the host, which follows the reference's doubles; nothing that
+// wrapped is ever turned into a moment.  The check is conservative: a sum of mixed signs whose partial sums leave the
+// range is refused although its total fits.
 struct Fx
 {
   long long hi;
@@ -249,11 +259,16 @@ __device__ __forceinline__ Fx fx_from(double t, bool* bad)
   return r;
 }
 
-__device__ __forceinline__ Fx fx_add(Fx a, Fx b)
+// *ovf: the sum left the format (signed overflow of the hi word); the wrapped bits are returned all the same
+__device__ __forceinline__ Fx fx_add(Fx a, Fx b, bool* ovf)
 {
   Fx r;
   r.lo = a.lo + b.lo;
-  r.hi = a.hi + b.hi + (r.lo < a.lo ? 1 : 0);
+  long long h;
+  bool o = __builtin_add_overflow(a.hi, b.hi, &h);
+  o |= __builtin_add_overflow(h, (long long)(r.lo < a.lo ? 1 : 0), &r.hi);
+  if (o)
+    *ovf = true;
   return r;
 }
 
@@ -262,11 +277,16 @@ __device__ __forceinline__ double fx_to_double(long long hi, unsigned long long 
   return (double)hi * 2.3283064365386963e-10 + (double)lo * 1.2621774483536189e-29;  // 2^-32, 2^-96
 }
 
-__device__ __forceinline__ void fx_atomic_add(long long* hi, unsigned long long* lo, Fx v)
+// true: the accumulator left the format with this add.  The adds to one hi word happen in SOME order, and a total that
+// wrapped has wrapped at one of them, whatever the order: the thread whose add it was sees it in the value it got back.
+__device__ __forceinline__ bool fx_atomic_add(long long* hi, unsigned long long* lo, Fx v)
 {
   const unsigned long long old = atomicAdd(lo, v.lo);
-  const unsigned long long carry = (old + v.lo < old) ? 1ull : 0ull;
-  atomicAdd(reinterpret_cast<unsigned long long*>(hi), (unsigned long long)v.hi + carry);
+  long long add, sum;
+  bool o = __builtin_add_overflow(v.hi, (long long)((old + v.lo < old) ? 1 : 0), &add);
+  const unsigned long long was = atomicAdd(reinterpret_cast<unsigned long long*>(hi), (unsigned long long)add);
+  o |= __builtin_add_overflow((long long)was, add, &sum);
+  return o;
 }
 
 // every sample adds its terms to its cluster's accumulators; a wave whose samples all belong to one cluster (the
@@ -306,8 +326,6 @@ __global__ __launch_bounds__(256) void k_stats_accumulate(const StatsArgs A, con
       t[k].lo = 0;
     }
   }
-  if (bad)
-    atomicExch(&A.flags[1], 1);
   const int first = __builtin_amdgcn_readfirstlane(cidx);
   const bool uniform = __builtin_amdgcn_ballot_w64(live && cidx != first) == 0 && first >= 0;
   if (uniform)
@@ -322,18 +340,20 @@ __global__ __launch_bounds__(256) void k_stats_accumulate(const StatsArgs A, con
         Fx u;
         u.hi = __shfl_xor(v.hi, o, 64);
         u.lo = __shfl_xor(v.lo, o, 64);
-        v = fx_add(v, u);
+        v = fx_add(v, u, &bad);
       }
       if ((threadIdx.x & 63) == 0)
-        fx_atomic_add(&A.acc_hi[(size_t)k * A.n + first], &A.acc_lo[(size_t)k * A.n + first], v);
+        bad |= fx_atomic_add(&A.acc_hi[(size_t)k * A.n + first], &A.acc_lo[(size_t)k * A.n + first], v);
     }
   }
   else if (live && cidx >= 0)
   {
 #pragma unroll
     for (int k = 0; k < kStatTerms; ++k)
-      fx_atomic_add(&A.acc_hi[(size_t)k * A.n + cidx], &A.acc_lo[(size_t)k * A.n + cidx], t[k]);
+      bad |= fx_atomic_add(&A.acc_hi[(size_t)k * A.n + cidx], &A.acc_lo[(size_t)k * A.n + cidx], t[k]);
   }
+  if (bad)  // a term or a sum outside the format, seen by whichever lane formed it
+    atomicExch(&A.flags[1], 1);
 }
 
 struct ClusterDev  // = bpf_cluster (include/badger_pf.h)
@@ -410,6 +430,7 @@ __global__ __launch_bounds__(1024) void k_stats_set(const StatsArgs A, const Clu
   }
   double bw = 0.0;
   int bi = INT_MAX;
+  bool ovf = false;
   for (int c = tid; c < C; c += 1024)
   {
 #pragma unroll
@@ -418,7 +439,7 @@ __global__ __launch_bounds__(1024) void k_stats_set(const StatsArgs A, const Clu
       Fx v;
       v.hi = A.acc_hi[(size_t)k * A.n + c];
       v.lo = A.acc_lo[(size_t)k * A.n + c];
-      t[k] = fx_add(t[k], v);
+      t[k] = fx_add(t[k], v, &ovf);
     }
     const double w = clusters[c].weight;
     if (w > bw)  // ascending c within a thread: the first of equals stays
@@ -437,11 +458,13 @@ __global__ __launch_bounds__(1024) void k_stats_set(const StatsArgs A, const Clu
       Fx u;
       u.hi = __shfl_xor(v.hi, o, 64);
       u.lo = __shfl_xor(v.lo, o, 64);
-      v = fx_add(v, u);
+      v = fx_add(v, u, &ovf);
     }
     if ((tid & 63) == 0)
-      fx_atomic_add(&s_hi[k], &s_lo[k], v);
+      ovf |= fx_atomic_add(&s_hi[k], &s_lo[k], v);
   }
+  if (ovf)  // the clusters' sums fit, the set's do not: the host evaluation (the flags are read after this launch)
+    atomicExch(&A.flags[1], 1);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1)
   {
@@ -758,20 +781,20 @@ __global__ __launch_bounds__(1024) void k_stats_block(const StatsBlockArgs A)
             Fx u;
             u.hi = __shfl_xor(v.hi, o, 64);
             u.lo = __shfl_xor(v.lo, o, 64);
-            v = fx_add(v, u);
+            v = fx_add(v, u, &bad);
           }
           if (lane == 0)
-            fx_atomic_add(&s_hi[first][k], &s_lo[first][k], v);
+            bad |= fx_atomic_add(&s_hi[first][k], &s_lo[first][k], v);
         }
       }
       else if (live && cidx >= 0)
       {
 #pragma unroll
         for (int k = 0; k < kStatTerms; ++k)
-          fx_atomic_add(&s_hi[cidx][k], &s_lo[cidx][k], t[k]);
+          bad |= fx_atomic_add(&s_hi[cidx][k], &s_lo[cidx][k], t[k]);
       }
     }
-    if (bad)
+    if (bad)  // a term or a sum outside the fixed-point format
       s_bad = 2;
   }
   __syncthreads();
@@ -782,6 +805,7 @@ __global__ __launch_bounds__(1024) void k_stats_block(const StatsBlockArgs A)
     double bw = 0.0;
     int bi = INT_MAX;
     double mean0 = 0.0, mean1 = 0.0, mean2 = 0.0;
+    bool ovf = false;
     Fx tot[kStatTerms];
 #pragma unroll
     for (int k = 0; k < kStatTerms; ++k)
@@ -821,7 +845,7 @@ __global__ __launch_bounds__(1024) void k_stats_block(const StatsBlockArgs A)
         Fx u;
         u.hi = __shfl_xor(tot[k].hi, o, 64);
         u.lo = __shfl_xor(tot[k].lo, o, 64);
-        tot[k] = fx_add(tot[k], u);
+        tot[k] = fx_add(tot[k], u, &ovf);
       }
     }
 #pragma unroll
@@ -835,6 +859,8 @@ __global__ __launch_bounds__(1024) void k_stats_block(const StatsBlockArgs A)
         bi = oi;
       }
     }
+    // the clusters' sums fit and the set's do not: status 12, as for a term outside the format
+    const bool set_fits = __builtin_amdgcn_ballot_w64(ovf) == 0;
     const int best = (good && bw > 0.0 && bi != INT_MAX) ? bi : -1;
     const int src_lane = best >= 0 ? best : 0;
     const double bp0 = __shfl(mean0, src_lane, 64), bp1 = __shfl(mean1, src_lane, 64), bp2 = __shfl(mean2, src_lane, 64);
@@ -866,7 +892,7 @@ __global__ __launch_bounds__(1024) void k_stats_block(const StatsBlockArgs A)
     if (lane < kWords)
       out[4 + lane] = reinterpret_cast<const int*>(&s_res)[lane];
     if (lane == 63)
-      out[1] = good ? 0 : (s_bad ? 10 + s_bad : (fits ? 2 : 1));
+      out[1] = good ? (set_fits ? 0 : 12) : (s_bad ? 10 + s_bad : (fits ? 2 : 1));
     __threadfence_system();
     if (lane == 0)
       __hip_atomic_store(const_cast<int*>(out), A.generation, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -463,7 +463,12 @@ class HipShardBackend:
         return self._view(p.value, (n.value,))
 
     def stats_finish(self, reduced):
+        """False: the reduced sums do not fit the fixed-point format (a frame far from the origin) and nothing was
+        installed -- on every rank alike; the host route takes over."""
         self.e.check(self.e.lib.bpf_shard_stats_finish_dev(self.e.h, C.c_void_p(reduced.data_ptr())))
+        ok = C.c_int()
+        self.e.check(self.e.lib.bpf_shard_stats_finish_installed(self.e.h, C.byref(ok)))
+        return bool(ok.value)
 
     def stats_local_samples_host(self):
         """numpy [n_local, 4] copy of the slice (the host route only)."""
@@ -1319,8 +1324,8 @@ class ShardedFilter:
                 b.stats_label(all_bins, bin_counts, pad)
                 sums = b.stats_local_sums()
                 self._all_reduce_sum(sums)  # limb form: the lane-wise int64 sum is exact
-                b.stats_finish(sums)
-                route = "distributed"
+                # (a backend without a range to leave returns None)
+                route = "host" if b.stats_finish(sums) is False else "distributed"
         if route == "host":
             local = torch.from_numpy(np.ascontiguousarray(b.stats_local_samples_host()[:, :4].T))
             allv, _ = self._gather_ragged(local.to(self.device), self.counts)

@@ -609,8 +609,13 @@ int bpf_shard_stats_label_dev(bpf_engine* e, const void* all_bins_dev, const int
 int bpf_shard_stats_local_sums_dev(bpf_engine* e, void** sums_dev, size_t* n_words_out);
 /* Stage 4 (particle_filter.cpp:541-567,607-635, node_2d.cpp:608-612), redundant on every rank: carries propagated,
  * the single engine's finishing kernels on the reduced sums, the result installed as this engine's statistics.
- * reduced_sums_dev may be the buffer stage 3 returned, reduced in place.  Waits for the stream. */
+ * reduced_sums_dev may be the buffer stage 3 returned, reduced in place.  Waits for the stream.
+ * The sums are 32.96 fixed point and end at |sum| < 2^31 (normalised weights: a cluster beyond ~46 km from the frame's
+ * origin on one axis does not fit).  A rank whose own sums leave that range marks what it exports, and a total that
+ * leaves it shows in the reduced words, so every rank finds out here, alike: nothing is installed then, the call
+ * returns BPF_OK, bpf_shard_stats_finish_installed reports 0 and every rank takes bpf_shard_stats_host instead. */
 int bpf_shard_stats_finish_dev(bpf_engine* e, const void* reduced_sums_dev);
+int bpf_shard_stats_finish_installed(bpf_engine* e, int* installed_out);
 /* The host route, redundant on every rank: particle_filter.cpp:505-636 in index order over the gathered set,
  * all_samples = global_count x (x, y, theta, w) in host memory; bit for bit the BPF_OPT_STATS_HOST = 1 evaluation of
  * one engine holding the set.  Crosses between ranks: the all-gather of the slices (32 B per particle), the caller's. */

@@ -135,9 +135,9 @@ def run_stages(bs, samples, cuts, force_distributed=False):
             sums = [b.stats_local_sums() for b in bs]
             reduced = torch.stack(sums).sum(dim=0)  # exchange 2: lane-wise int64 sum of the limb words
             assert reduced.dtype == torch.int64 and reduced.numel() == 40 * cs[0]
-            for b in bs:
-                b.stats_finish(reduced)
-            route = "distributed"
+            done = [b.stats_finish(reduced) for b in bs]
+            assert len(set(done)) == 1  # sums beyond the fixed-point format: every rank finds out alike
+            route = "host" if done[0] is False else "distributed"
     if route == "host":
         for b in bs:
             b.stats_host(samples)
