@@ -45,6 +45,7 @@ int bpf_map3d_set(bpf_engine* e, const uint32_t* pose_indices, size_t n_pose_ind
   e->n_pose_indices = n_pose_indices;
   e->n_ratios = n_distance_ratios;
   e->have_map3d = true;
+  e->map3_version++;
   // the dense tiled copy for the scoring kernel's gathers, when a plane fits the 24-bit multiply and the volume 1 GiB
   M.dense = nullptr;
   M.dense_k = 0;
@@ -503,10 +504,24 @@ int stage_cloud(bpf_engine* e, const float* points_xyz, int n_points)
   return BPF_OK;
 }
 
+// whether launch_cloud takes the BORDER form of k_cloud_score (its own conditions, restated for the callers that
+// must know before they launch)
+bool cloud_border_form(const bpf_engine* e)
+{
+  const bool planar = e->cm.tf_quat[0] == 0.0 && e->cm.tf_quat[1] == 0.0 && (e->map3.max_c[2] - e->map3.min_c[2]) < 65534;
+  const bool dense = e->map3.dense != nullptr && e->cloud_dense;
+  return BPF_CLOUD_BORDER != 0 && planar && dense && e->map3.border_code >= 0;
+}
+
 // The launches, against what stage_cloud left on the device: k_cloud_affine, the k_cloud_score instance,
 // k_cloud_finish.  Enqueues only (the scratch grows here when n is larger than any before).
-int launch_cloud(bpf_engine* e, ParticlesDev p, int n, int n_points)
+// bound_volume (the bound pass of the pruned search, abi_pose_search_cloud_pruned.inl): a volume in the layout of
+// Map3dDev::dense that the kernel gathers from in its place, with off_map_factor taken as 1 in the epilogue.  Only the
+// BORDER form reads the volume for a sample that is off the map, so every other form is refused here.
+int launch_cloud(bpf_engine* e, ParticlesDev p, int n, int n_points, const uint8_t* bound_volume = nullptr)
 {
+  if (bound_volume != nullptr && !cloud_border_form(e))
+    return e->fail(BPF_ERR_UNSUPPORTED, "cloud bound pass: needs the planar dense kernel with the border codes");
   const int n_chunks = blocks_for(n_points, kCloudChunk);
   HIPCHK(e, e->d_affine.reserve((size_t)n * 12));
   HIPCHK(e, e->d_cloud_partials.reserve((size_t)n_chunks * n));
@@ -517,6 +532,8 @@ int launch_cloud(bpf_engine* e, ParticlesDev p, int n, int n_points)
   A.points = e->d_points.p;
   A.n_points = n_points;
   A.map = e->map3;
+  if (bound_volume != nullptr)
+    A.map.dense = bound_volume;
   A.table = e->d_cloud_table.p;
   A.partials = e->d_cloud_partials.p;
   A.slabs = std::max(1, std::min(blocks_for(n, 4), std::max(1, (e->n_cu * 6) / n_chunks)));
@@ -589,6 +606,8 @@ int launch_cloud(bpf_engine* e, ParticlesDev p, int n, int n_points)
   F.n_points = n_points;
   F.map = e->map3;
   F.model = e->cm;
+  if (bound_volume != nullptr)
+    F.model.off_map_factor = 1.0;
   hipLaunchKernelGGL(k_cloud_finish, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, F);
   HIPCHK(e, hipGetLastError());
   e->evals_last = (long long)n * n_points;

@@ -166,17 +166,9 @@ PruneBlocks prune_blocks_of(const PruneCall& call, int first_block)
   return PruneBlocks{ call.list->start.p, call.list->member.p, call.list->anchor.p, first_block, call.headings };
 }
 
-// one exact window as it stands in e->cand (poses) and e->d_prune_ids: scored, folded into the exact list
-int prune_score_fold(bpf_engine* e, int n, int k, const double* ranges, const double* angles, int range_count,
-                     double range_max)
+// one exact window as it stands in e->cand (poses, scored) and e->d_prune_ids, folded into the exact list
+int prune_fold(bpf_engine* e, int n, int k)
 {
-  if (e->pm.max_beams >= 2)
-  {
-    bool forced_zero = false;
-    const int rc = score_planar(e, e->cand.dev(), n, 0, ranges, angles, range_count, range_max, &forced_zero);
-    if (rc != BPF_OK)
-      return rc;
-  }
   int kp = 2;
   while (kp < k)
     kp <<= 1;
@@ -190,6 +182,20 @@ int prune_score_fold(bpf_engine* e, int n, int k, const double* ranges, const do
   if (hipGetLastError() != hipSuccess)
     return e->fail(BPF_ERR_HIP, "pruned pose search selection launch");
   return BPF_OK;
+}
+
+// one exact window as it stands in e->cand (poses) and e->d_prune_ids: scored, folded into the exact list
+int prune_score_fold(bpf_engine* e, int n, int k, const double* ranges, const double* angles, int range_count,
+                     double range_max)
+{
+  if (e->pm.max_beams >= 2)
+  {
+    bool forced_zero = false;
+    const int rc = score_planar(e, e->cand.dev(), n, 0, ranges, angles, range_count, range_max, &forced_zero);
+    if (rc != BPF_OK)
+      return rc;
+  }
+  return prune_fold(e, n, k);
 }
 
 // bounds of the global block candidates q0 .. q0 + nq - 1 into e->d_prune_bounds[0 .. nq), window by window; k > 0:

@@ -45,6 +45,7 @@
 #include "kernels_score.hpp"
 #include "kernels_window.hpp"
 #include "kernels_pose_search_pruned.hpp"
+#include "kernels_pose_search_cloud_pruned.hpp"
 
 using namespace bpf;
 
@@ -90,6 +91,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_pose_search.inl"
 #include "abi_pose_search_cloud.inl"
 #include "abi_pose_search_pruned.inl"
+#include "abi_pose_search_cloud_pruned.inl"
 #include "abi_pose_refine.inl"
 #include "abi_pose_moments.inl"
 #include "abi_bootstrap.inl"

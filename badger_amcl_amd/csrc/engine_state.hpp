@@ -301,6 +301,7 @@ struct bpf_engine
   bool have_map3d = false;
   Map3dDev map3{};
   double map3_max_dist = 0.0;
+  int map3_version = 0;  // bumped by bpf_map3d_set: what is cached per 3-D map compares it
   DevBuf<uint32_t> d_pose_indices;
   DevBuf<uint8_t> d_ratios, d_dense3d;
   bool lut_host = false;      // BPF_OPT_LUT_HOST: the 3-D LUT builder on the host
@@ -521,6 +522,23 @@ struct bpf_engine
   PinnedBuf<int2> h_prune_chunks;
   PinnedBuf<long long> h_prune_chunk_off;
   PinnedBuf<unsigned long long> h_prune_words;
+  // the 3-D form (kernels_pose_search_cloud_pruned.hpp, abi_pose_search_cloud_pruned.inl): one pooled volume per
+  // (3-D map version, B), as large as Map3dDev::dense and reserved on first use, and one block list per (3-D map
+  // version, stride, B) -- per-axis arrays and per-block starts and anchors, never per column
+  struct PrunePool3
+  {
+    DevBuf<uint8_t> vol;  // P_B in the layout of d_dense3d
+    int map3_version = -1;
+  } prune_pool3[6];
+  DevBuf<uint8_t> d_prune_rows3;  // the row pass of some planes of a pooled volume under construction
+  struct PruneRect
+  {
+    DevBuf<int> start, axis_i, axis_j;
+    DevBuf<int2> anchor;
+    std::vector<int> h_start;
+    int n_blocks = 0, nbj = 0, max_members = 0;
+    int map3_version = -1, stride = 0;
+  } prune_rect[6];
 
   // ---- pose refinement (kernels_pose_refine.hpp, abi_pose_refine.inl): the centres of the descent and what
   // k_refine_select keeps per pose.  The lattice poses live in `cand`; nothing here describes the particle set

@@ -19,6 +19,9 @@
 // tau lives in device memory (the K-th row of the running exact list) and only changes between kernels of the one
 // stream.  No block waits for another.  A dropped or empty slot of a window carries a NaN pose, which the scoring path
 // sends off the map without a gather that misses (field_prep_of), and id -1, which the selection skips.
+//
+// The 3-D cloud search (bpf_cloud_search_poses_pruned, kernels_pose_search_cloud_pruned.hpp) runs the same kernels over
+// the rectangle form of SearchSpace and PruneBlocks: anchors and members by arithmetic instead of from lists.
 #pragma once
 #include "kernels_pose_search.hpp"
 #include "kernels_score.hpp"
@@ -41,6 +44,12 @@ struct PruneBlocks
   const int2* anchor;   // [n_blocks] the cell (bi * B, bj * B)
   int first_block;      // block candidate q of the call is block first_block + q / H at heading q % H
   int headings;
+  // rectangle form (member == nullptr: the 3-D cloud search, kernels_pose_search_cloud_pruned.hpp).  The block list is
+  // the product of two per-axis lists, block b = ib * nbj + jb; a block's members are the columns a in [axis_i[ib],
+  // axis_i[ib + 1]) x b in [axis_j[jb], axis_j[jb + 1]) of the rectangle C_s, f = a * n_j + b, a outer (f ascending)
+  const int* axis_i;    // [nbi + 1]
+  const int* axis_j;    // [nbj + 1]
+  int nbj, n_j;
 };
 
 // what a bound is made of behind the scoring launch
@@ -127,7 +136,7 @@ __global__ __launch_bounds__(256) void k_pool_cols(MapDev M, int B, unsigned kof
 
 // ------------------------------------------------------------------ bounds
 // anchor poses of the global block candidates q0 .. q0 + n - 1 (q = block * H + h over the whole block list): the
-// cell expression and the heading expression of search_pose_of
+// cell expression (of either form of the space) and the heading expression of search_pose_of
 __global__ void k_prune_anchors(ParticlesDev dst, int n, long long q0, const int2* __restrict__ anchor, SearchSpace S)
 {
 #pragma clang fp contract(off)
@@ -137,8 +146,16 @@ __global__ void k_prune_anchors(ParticlesDev dst, int n, long long q0, const int
   const unsigned q = (unsigned)(q0 + (long long)t), H = (unsigned)S.headings;
   const unsigned b = q / H, hh = q - b * H;
   const int2 cell = anchor[b];
-  dst.x[t] = S.origin_x + (cell.x - S.size_x / 2) * S.resolution;
-  dst.y[t] = S.origin_y + (cell.y - S.size_y / 2) * S.resolution;
+  if (S.cells != nullptr)
+  {
+    dst.x[t] = S.origin_x + (cell.x - S.size_x / 2) * S.resolution;
+    dst.y[t] = S.origin_y + (cell.y - S.size_y / 2) * S.resolution;
+  }
+  else  // the rectangle form's cell expression (3-D: i * res, j * res)
+  {
+    dst.x[t] = cell.x * S.resolution;
+    dst.y[t] = cell.y * S.resolution;
+  }
   dst.th[t] = (2.0 * 3.14159265358979323846 * (double)hh) / (double)S.headings - 3.14159265358979323846;
   dst.w[t] = 1.0;
 }
@@ -228,7 +245,18 @@ __device__ __forceinline__ void prune_write_slot(ParticlesDev dst, long long* id
   {
     const int bq = q / L.headings;
     const int h = q - bq * L.headings;
-    const long long c = (long long)L.member[L.start[L.first_block + bq] + r] * (long long)L.headings + (long long)h;
+    const int b = L.first_block + bq;
+    long long f;
+    if (L.member != nullptr)
+      f = (long long)L.member[L.start[b] + r];
+    else
+    {
+      const int ib = b / L.nbj, jb = b - ib * L.nbj;
+      const int b0 = L.axis_j[jb], nb = L.axis_j[jb + 1] - b0;
+      const int ra = r / nb;
+      f = (long long)(L.axis_i[ib] + ra) * (long long)L.n_j + (long long)(b0 + (r - ra * nb));
+    }
+    const long long c = f * (long long)L.headings + (long long)h;
     int i, j, hh;
     double x, y, th;
     search_pose_of(S, c, &i, &j, &hh, &x, &y, &th);

@@ -44,6 +44,7 @@ CELL_FREE, CELL_UNKNOWN, CELL_OCCUPIED = -1, 0, 1
 # pruned pose search: the block sizes it takes and the default (profiles/pose_search_pruned.md)
 POSE_SEARCH_BLOCKS = _lib.POSE_SEARCH_BLOCKS
 POSE_SEARCH_BLOCK = 8
+POSE_SEARCH_CLOUD_BLOCK = 16  # the cloud scanner's default (profiles/pose_search_cloud_pruned.md)
 POSE_SEARCH_STATS_FIELDS = tuple(name for name, _ in _lib.PoseSearchStats._fields_)
 
 
@@ -904,6 +905,55 @@ class PointCloudScanner:
             self.e.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], int(headings), int(cell_stride),
             int(first), int(count), int(k), hits.ctypes.data_as(C.POINTER(_lib.PoseHit)), C.byref(n)))
         return hits[:n.value]
+
+    def searchBlocks(self, cell_stride=1, block=POSE_SEARCH_CLOUD_BLOCK):
+        """Blocks of block x block columns that hold a column of the strided rectangle: what a caller of
+        searchPosesPruned splits into ranges."""
+        n = C.c_int()
+        self.e.check(self.e.lib.bpf_cloud_search_blocks(self.e.h, int(cell_stride), int(block), C.byref(n)))
+        return n.value
+
+    def searchPosesPruned(self, data, headings, cell_stride, k, block=POSE_SEARCH_CLOUD_BLOCK, first_block=0,
+                          block_count=-1, stats=False):
+        """NOT a reference method: the rows of searchPoses over the candidates whose columns lie in blocks first_block
+        .. first_block + block_count - 1 of the block list, bit for bit, from fewer exact evaluations (a mounting
+        without roll or pitch and a map with the dense volume only).  stats=True: (hits, dict of the
+        bpf_pose_search_stats fields).  See bpf_cloud_search_poses_pruned in include/badger_pf.h."""
+        hits = np.zeros(max(int(k), 1), dtype=POSE_HIT_DTYPE)
+        n = C.c_int()
+        st = _lib.PoseSearchStats()
+        pts = data.points_
+        self.e.check(self.e.lib.bpf_cloud_search_poses_pruned(
+            self.e.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], int(headings), int(cell_stride),
+            int(block), int(first_block), int(block_count), int(k), hits.ctypes.data_as(C.POINTER(_lib.PoseHit)),
+            C.byref(n), C.byref(st)))
+        if stats:
+            return hits[:n.value], {name: getattr(st, name) for name, _ in _lib.PoseSearchStats._fields_}
+        return hits[:n.value]
+
+    def searchPooledLut(self, block=POSE_SEARCH_CLOUD_BLOCK):
+        """(bytes, ntx, nty, planes): the min-pooled volume searchPosesPruned bounds with, uint8 distance ratios in the
+        engine's dense layout (planes of ntx x nty tiles of 8 x 8, the zero plane last).  For diagnosis and tests."""
+        n, ntx, nty, planes = C.c_longlong(), C.c_int(), C.c_int(), C.c_int()
+        self.e.check(self.e.lib.bpf_cloud_search_pooled_lut(self.e.h, int(block), None, 0, C.byref(n), C.byref(ntx),
+                                                            C.byref(nty), C.byref(planes)))
+        out = np.zeros(n.value, dtype=np.uint8)
+        self.e.check(self.e.lib.bpf_cloud_search_pooled_lut(
+            self.e.h, int(block), out.ctypes.data_as(C.POINTER(C.c_ubyte)), n.value, C.byref(n), C.byref(ntx),
+            C.byref(nty), C.byref(planes)))
+        return out, ntx.value, nty.value, planes.value
+
+    def searchBounds(self, data, headings, cell_stride, block=POSE_SEARCH_CLOUD_BLOCK, first_q=0, count=-1):
+        """The upper bounds searchPosesPruned prunes with, as a float64 array: block candidate q = block_index *
+        headings + h, first_q .. first_q + count - 1.  For diagnosis and tests."""
+        if count < 0:
+            count = self.searchBlocks(cell_stride, block) * int(headings) - int(first_q)
+        out = np.zeros(max(int(count), 1), dtype=np.float64)
+        pts = data.points_
+        self.e.check(self.e.lib.bpf_cloud_search_bounds(
+            self.e.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], int(headings), int(cell_stride),
+            int(block), int(first_q), int(count), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out[:max(int(count), 0)]
 
     def refinePoses(self, data, poses, xy_radius, xy_step, theta_radius, theta_step, levels, trace=False):
         """NOT a reference method: coarse-to-fine lattice descent around every pose of `poses` (an [n, 3] array or a

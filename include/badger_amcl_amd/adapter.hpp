@@ -764,6 +764,52 @@ public:
     hits.resize((size_t)n);
     return hits;
   }
+  // NOT a reference method (bpf_cloud_search_poses_pruned): the rows of searchPoses over the candidates whose columns
+  // lie in blocks first_block .. first_block + block_count - 1 (block_count = -1: to the end) of the list of
+  // block x block column blocks, bit for bit, from fewer exact evaluations.  A mounting without roll or pitch and a
+  // map with the dense volume only.
+  std::vector<bpf_pose_hit> searchPosesPruned(std::shared_ptr<PointCloudData> data, int headings, int cell_stride,
+                                              int k, int block = 16, int first_block = 0, int block_count = -1,
+                                              bpf_pose_search_stats* stats_out = nullptr)
+  {
+    std::vector<bpf_pose_hit> hits((size_t)(k > 0 ? k : 1));
+    int n = 0;
+    e_->check(bpf_cloud_search_poses_pruned(e_->get(), data->points_.data(), data->pointCount(), headings, cell_stride,
+                                            block, first_block, block_count, k, hits.data(), &n, stats_out));
+    hits.resize((size_t)n);
+    return hits;
+  }
+  // blocks in that list: what a caller of searchPosesPruned splits into ranges
+  int searchBlocks(int cell_stride = 1, int block = 16)
+  {
+    int n = 0;
+    e_->check(bpf_cloud_search_blocks(e_->get(), cell_stride, block, &n));
+    return n;
+  }
+  // the bounds searchPosesPruned prunes with, of block candidates first_q .. first_q + count - 1 (count = -1: to the
+  // end of the block list x headings).  For diagnosis and tests.
+  std::vector<double> searchBounds(std::shared_ptr<PointCloudData> data, int headings, int cell_stride, int block = 16,
+                                   long long first_q = 0, long long count = -1)
+  {
+    if (count < 0)
+      count = (long long)searchBlocks(cell_stride, block) * headings - first_q;
+    std::vector<double> bounds((size_t)(count > 0 ? count : 1));
+    e_->check(bpf_cloud_search_bounds(e_->get(), data->points_.data(), data->pointCount(), headings, cell_stride, block,
+                                      first_q, count, bounds.data()));
+    bounds.resize((size_t)(count > 0 ? count : 0));
+    return bounds;
+  }
+  // the pooled volume searchPosesPruned bounds with, in the engine's dense layout: planes of ntx x nty tiles of 64
+  // bytes, the zero plane last.  For diagnosis and tests.
+  std::vector<unsigned char> searchPooledLut(int block = 16, int* ntx_out = nullptr, int* nty_out = nullptr,
+                                             int* planes_out = nullptr)
+  {
+    long long n = 0;
+    e_->check(bpf_cloud_search_pooled_lut(e_->get(), block, nullptr, 0, &n, ntx_out, nty_out, planes_out));
+    std::vector<unsigned char> bytes((size_t)n);
+    e_->check(bpf_cloud_search_pooled_lut(e_->get(), block, bytes.data(), n, &n, ntx_out, nty_out, planes_out));
+    return bytes;
+  }
   // NOT a reference method (bpf_cloud_refine_poses): coarse-to-fine lattice descent around every pose of `poses_xyt`
   // (x, y, theta triples) against the cloud `data` on the device; row r refines pose r.  trace_out, when given,
   // receives the lattice point chosen per (pose, level), poses.size() / 3 * levels ints.

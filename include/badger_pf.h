@@ -1307,6 +1307,54 @@ int bpf_cloud_search_poses(bpf_engine* e, const float* points_xyz, int n_points,
  * itself, also when it is past the limit of a search); *columns_out = |C_s| */
 int bpf_cloud_search_space(bpf_engine* e, int headings, int cell_stride, long long* candidates_out, int* columns_out);
 
+/* The cloud search, pruned: the rows of bpf_cloud_search_poses, bit for bit, from fewer exact evaluations.  NOT a
+ * reference call.  The structure, the stats and their invariants are those of bpf_planar_search_poses_pruned.
+ *
+ * block B (one of 2, 4, 8, 16, 32, 64): block (bi, bj) holds the columns of C_s with floor(i / B) == bi and
+ * floor(j / B) == bj (floor division: the cell bounds may be negative).  The block list holds the blocks with at
+ * least one column of C_s, bi outer, bj inner; it is the product of two per-axis lists, never a per-column list.
+ * Block candidate q = block_index * headings + h stands for the candidates c = f * headings + h of
+ * bpf_cloud_search_poses whose column lies in the block; numbering, poses and scores are unchanged.  The bound of q
+ * is the anchor pose -- the column (bi * B, bj * B), inside the rectangle or not, x = i * resolution, y = j *
+ * resolution, at heading h -- scored by the same scoring launches against the pooled volume P_B with off_map_factor
+ * taken as 1, times max(1, off_map_factor) (min(1, ...) under a negative value); for Gompertz a small margin is
+ * added first.  P_B has the layout of the engine's dense volume; its entry at grid position (x, y) of plane k is the
+ * smallest distance ratio of the on-map cells of the window [x - 1, x + B] x [y - 1, y + B] of that plane (the far
+ * border entry: of the cells within B + 1 of either edge), the border code when there is none.  bound(q) >=
+ * score(c), as doubles, for every member c ("Pose search, pruned 3-D form").
+ *
+ * Seed, tau, survivors, expansion and the two waits behind the staging are as in the planar call; first_block /
+ * block_count select a range of the block list (block_count = -1: to its end), and lists of disjoint ranges merge
+ * with bpf_pose_search_merge.
+ *
+ * Status: BPF_ERR_NOT_CONFIGURED without the 3-D map or a cloud model.  BPF_ERR_UNSUPPORTED, before any scoring
+ * launch: a scanner mounting with roll or pitch; a 3-D map without the dense volume or with fewer than two distance
+ * ratios free for the border codes (or BPF_OPT_CLOUD_DENSE off); a Gompertz whose a, b, c or input_scale is not > 0;
+ * an off_map_factor that is negative or NaN; a term table that is not non-increasing over the ratios 0 .. 255 and
+ * the off-map term; a cloud too large for the resolution -- with L = the largest |x| + |y| over the points whose
+ * coordinates are all finite, + |tf_x| + |tf_y| + (the largest |cell bound| in x, y + B) * resolution, the call needs
+ * L * 2^-21 < resolution (points with a non-finite coordinate are off the map at every pose and do not count).
+ * BPF_ERR_INVALID_ARGUMENT for a block that is not in the list, a range outside the block list and what
+ * bpf_cloud_search_poses refuses.  BPF_ERR_CAPACITY for |C_s| * headings > 2^31 - 1, more than 2^24 block candidates
+ * in one call and more than 2^26 blocks.  P_B takes as much device memory as the dense volume (up to 1 GiB) per block
+ * size used, reserved on first use; when that fails the call returns the allocation's error.  With cloud max_beams < 2
+ * every score is 1.0.  Read-only for the filter, exactly as bpf_cloud_search_poses is. */
+int bpf_cloud_search_poses_pruned(bpf_engine* e, const float* points_xyz, int n_points, int headings, int cell_stride,
+                                  int block, int first_block, int block_count, int k, bpf_pose_hit* hits_out,
+                                  int* n_hits_out, bpf_pose_search_stats* stats_out /* nullable */);
+/* number of blocks in the block list of (cell_stride, block) for the current 3-D map (needs the map only) */
+int bpf_cloud_search_blocks(bpf_engine* e, int cell_stride, int block, int* n_blocks_out);
+/* the pooled volume P_B of the current 3-D map as the bound pass reads it: *planes_out planes (the map's z cells and
+ * the zero plane behind them) of *ntx_out x *nty_out tiles of 64 bytes, the layout of the engine's dense volume.
+ * *n_out = bytes of the volume; bytes_out may be null to ask for the size and the geometry alone, otherwise capacity
+ * >= *n_out.  BPF_ERR_UNSUPPORTED without the dense volume or the border codes.  For diagnosis and for the tests. */
+int bpf_cloud_search_pooled_lut(bpf_engine* e, int block, unsigned char* bytes_out, long long capacity,
+                                long long* n_out, int* ntx_out, int* nty_out, int* planes_out);
+/* the bounds the pruning uses, as doubles, of the block candidates first_q .. first_q + count - 1 (q over the whole
+ * block list; count = -1: to the end).  For diagnosis and for the tests; refusals as above. */
+int bpf_cloud_search_bounds(bpf_engine* e, const float* points_xyz, int n_points, int headings, int cell_stride,
+                            int block, long long first_q, long long count, double* bounds_out);
+
 /* ------------------------------------------------------------------ pose refinement
  * Sub-cell, sub-degree poses from the hits of a search (or from any poses): a coarse-to-fine descent on a lattice
  * around each pose, all of it on the device.  NOT a reference call (parity unpinned by construction).
