@@ -278,6 +278,16 @@ SIGNATURES = {
                                               C.POINTER(C.c_longlong), _ip, _ip, _ip]),
     "bpf_cloud_search_bounds": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_longlong, C.c_longlong, _dp]),
+    "bpf_shard_search_poses": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_longlong,
+                                         C.c_longlong, C.c_int, C.POINTER(PoseHit), _ip]),
+    "bpf_shard_search_poses_pruned": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                C.c_int, C.c_int, C.c_int, C.POINTER(PoseHit), _ip,
+                                                C.POINTER(PoseSearchStats)]),
+    "bpf_shard_cloud_search_poses": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_longlong,
+                                               C.c_longlong, C.c_int, C.POINTER(PoseHit), _ip]),
+    "bpf_shard_cloud_search_poses_pruned": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.c_int, C.c_int, C.c_int, C.POINTER(PoseHit), _ip,
+                                                      C.POINTER(PoseSearchStats)]),
     "bpf_planar_refine_poses": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, _dp, C.c_int, C.c_int, C.c_double, C.c_int,
                                           C.c_double, C.c_int, C.POINTER(PoseRefined), _ip]),
     "bpf_cloud_refine_poses": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, _dp, C.c_int, C.c_int, C.c_double,

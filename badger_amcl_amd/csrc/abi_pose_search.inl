@@ -16,6 +16,30 @@ constexpr int kSearchWindow = 65536;  // candidates per window (bpf_pose_search_
 static_assert(sizeof(bpf_pose_hit) == 56, "bpf_pose_hit is 56 bytes in every binding");
 static_assert(kSearchWindow % kSearchTile == 0, "whole tiles per full window");
 
+// ---- what a sharded search (abi_shard_search.inl) hands the four internal searches on its rank.  With it a search
+// checks the whole range given, takes this rank's share of it, and hands its list -- left in d_search_best with its
+// count -- to shard_search_finish instead of search_finish; the pruned forms share their tau behind the seed.  The
+// single-engine entry points pass nullptr: finish, no hook.
+struct SearchShard
+{
+  int rank = 0, world = 1;
+  const unsigned long long* floor_key = nullptr;  // device word for prune_tau, set by shard_search_share_floor
+};
+// units [first + T r / W, first + T (r + 1) / W) of the T given: the convention of even_counts
+void shard_search_share(int rank, int world, long long first, long long T, long long* my_first, long long* my_count)
+{
+  const long long lo = (T * rank) / world, hi = (T * (rank + 1)) / world;
+  *my_first = first + lo;
+  *my_count = hi - lo;
+}
+// abi_shard_search.inl: the ranks' K-th keys behind the seed into a floor on the device (enqueued, no wait) ...
+int shard_search_share_floor(bpf_engine* e, SearchShard* sh, int k);
+// ... whose exchange the host checks behind the wait for the survivor counts; and the ranks' lists gathered, folded
+// on the device and fetched as rows
+int shard_search_floor_arrived(bpf_engine* e, SearchShard* sh);
+int shard_search_finish(bpf_engine* e, SearchShard* sh, const SearchSpace& S, int k, bpf_pose_hit* hits_out,
+                        int* n_hits_out);
+
 // arguments every entry point checks alike
 int search_space_of(bpf_engine* e, int headings, int cell_stride, SearchSpace* S, long long* total)
 {
@@ -88,7 +112,7 @@ int search_finish(bpf_engine* e, const SearchSpace& S, int k, bpf_pose_hit* hits
 
 int search_poses(bpf_engine* e, const double* ranges, const double* angles, int range_count, double range_max,
                  int headings, int cell_stride, long long first, long long count, int k, bpf_pose_hit* hits_out,
-                 int* n_hits_out)
+                 int* n_hits_out, SearchShard* sh = nullptr)
 {
   if (!hits_out || !n_hits_out || !ranges || !angles || range_count <= 0)
     return e->fail(BPF_ERR_INVALID_ARGUMENT, "pose search: a scan and an output are needed");
@@ -110,10 +134,12 @@ int search_poses(bpf_engine* e, const double* ranges, const double* angles, int 
   if (count < 0)
     count = total - first;
   *n_hits_out = 0;
-  if (count == 0)
+  if (sh)  // (an empty share scores nothing and contributes an empty list)
+    shard_search_share(sh->rank, sh->world, first, count, &first, &count);
+  else if (count == 0)
     return BPF_OK;
 
-  HIPCHK(e, e->cand.reserve((size_t)std::min<long long>(count, kSearchWindow)));
+  HIPCHK(e, e->cand.reserve((size_t)std::max<long long>(1, std::min<long long>(count, kSearchWindow))));
   rc = search_begin(e);
   if (rc != BPF_OK)
     return rc;
@@ -140,7 +166,7 @@ int search_poses(bpf_engine* e, const double* ranges, const double* angles, int 
     if (rc != BPF_OK)
       return drained(rc);
   }
-  rc = search_finish(e, S, k, hits_out, n_hits_out);
+  rc = sh ? shard_search_finish(e, sh, S, k, hits_out, n_hits_out) : search_finish(e, S, k, hits_out, n_hits_out);
   return rc == BPF_OK ? rc : drained(rc);
 }
 

@@ -44,7 +44,8 @@ int cloud_search_space_of(bpf_engine* e, int headings, int cell_stride, SearchSp
 }
 
 int cloud_search_poses(bpf_engine* e, const float* points_xyz, int n_points, int headings, int cell_stride,
-                       long long first, long long count, int k, bpf_pose_hit* hits_out, int* n_hits_out)
+                       long long first, long long count, int k, bpf_pose_hit* hits_out, int* n_hits_out,
+                       SearchShard* sh = nullptr)
 {
   if (!hits_out || !n_hits_out || !points_xyz || n_points <= 0)
     return e->fail(BPF_ERR_INVALID_ARGUMENT, "pose search: a cloud and an output are needed");
@@ -64,12 +65,14 @@ int cloud_search_poses(bpf_engine* e, const float* points_xyz, int n_points, int
   if (count < 0)
     count = total - first;
   *n_hits_out = 0;
-  if (count == 0)
+  if (sh)  // (an empty share scores nothing and contributes an empty list)
+    shard_search_share(sh->rank, sh->world, first, count, &first, &count);
+  else if (count == 0)
     return BPF_OK;
   HIPCHK(e, hipSetDevice(e->device));
 
   const bool scored = e->cloud_max_beams >= 2;  // (below that applyModelToSampleSet leaves the weight 1.0, :109-110)
-  const int n_max = (int)std::min<long long>(count, kSearchWindow);
+  const int n_max = (int)std::max<long long>(1, std::min<long long>(count, kSearchWindow));
   if (scored)
   {
     rc = stage_cloud(e, points_xyz, n_points);  // (waits for the stream: nothing below frees a buffer in use)
@@ -104,7 +107,7 @@ int cloud_search_poses(bpf_engine* e, const float* points_xyz, int n_points, int
     if (rc != BPF_OK)
       return drained(rc);
   }
-  rc = search_finish(e, S, k, hits_out, n_hits_out);
+  rc = sh ? shard_search_finish(e, sh, S, k, hits_out, n_hits_out) : search_finish(e, S, k, hits_out, n_hits_out);
   return rc == BPF_OK ? rc : drained(rc);
 }
 }  // namespace

@@ -306,7 +306,7 @@ int prune3_bound_pass(bpf_engine* e, const Prune3Call& call, long long q0, long 
 
 int cloud_search_poses_pruned(bpf_engine* e, const float* points_xyz, int n_points, int headings, int cell_stride,
                               int block, int first_block, int block_count, int k, bpf_pose_hit* hits_out,
-                              int* n_hits_out, bpf_pose_search_stats* stats_out)
+                              int* n_hits_out, bpf_pose_search_stats* stats_out, SearchShard* sh = nullptr)
 {
   if (!hits_out || !n_hits_out)
     return e->fail(BPF_ERR_INVALID_ARGUMENT, "pose search: an output is needed");
@@ -322,6 +322,22 @@ int cloud_search_poses_pruned(bpf_engine* e, const float* points_xyz, int n_poin
     return e->fail(BPF_ERR_INVALID_ARGUMENT, "pruned pose search: first_block / block_count outside the block list");
   if (block_count < 0)
     block_count = L.n_blocks - first_block;
+  if (sh)
+  {
+    // the capacity limit holds for every rank's share, checked on every rank alike; then this rank's share
+    long long mine_first = first_block, mine = block_count;
+    for (int r = 0; r < sh->world; ++r)
+    {
+      long long f, c;
+      shard_search_share(r, sh->world, first_block, block_count, &f, &c);
+      if (c * headings > kPruneMaxBlockCandidates)
+        return e->fail(BPF_ERR_CAPACITY, "pruned pose search: more than 2^24 block candidates in a rank's share");
+      if (r == sh->rank)
+        mine_first = f, mine = c;
+    }
+    first_block = (int)mine_first;
+    block_count = (int)mine;
+  }
   const long long nq = (long long)block_count * headings;
   if (nq > kPruneMaxBlockCandidates)
     return e->fail(BPF_ERR_CAPACITY, "pruned pose search: more than 2^24 block candidates (split the range or raise block)");
@@ -331,11 +347,25 @@ int cloud_search_poses_pruned(bpf_engine* e, const float* points_xyz, int n_poin
   *n_hits_out = 0;
   if (stats_out)
     *stats_out = st;
-  if (nq == 0)
+  if (nq == 0 && !sh)
     return BPF_OK;
-  rc = prune3_stage(e, points_xyz, block, &call);
+  rc = prune3_stage(e, points_xyz, block, &call);  // (the table's refusal: before any exchange, on every rank alike)
   if (rc != BPF_OK)
     return rc;
+  if (nq == 0)
+  {
+    // an empty share: nothing is scored, the list stays empty, and the rank takes part in every exchange
+    rc = search_begin(e);
+    if (rc == BPF_OK)
+      rc = shard_search_share_floor(e, sh, k);
+    if (rc == BPF_OK)
+      rc = shard_search_floor_arrived(e, sh);
+    if (rc == BPF_OK)
+      rc = shard_search_finish(e, sh, call.S, k, hits_out, n_hits_out);
+    if (rc != BPF_OK)
+      (void)hipStreamSynchronize(e->stream);
+    return rc;
+  }
 
   const int n_chunks = blocks_for((int)nq, kPruneChunk);
   HIPCHK(e, e->d_prune_bounds.reserve((size_t)nq));
@@ -397,14 +427,25 @@ int cloud_search_poses_pruned(bpf_engine* e, const float* points_xyz, int n_poin
     ++st.windows;
   }
 
-  // 4. the survivors; the host sums the chunks' totals
+  // 4. the survivors; the host sums the chunks' totals.  A sharded search first shares tau: from here on the ranks
+  // prune against the largest K-th score any of them holds behind its seed
+  const unsigned long long* floor_key = nullptr;
+  if (sh)
+  {
+    rc = shard_search_share_floor(e, sh, k);
+    if (rc != BPF_OK)
+      return drained(rc);
+    floor_key = sh->floor_key;
+  }
   hipLaunchKernelGGL(k_prune_survivors, dim3(n_chunks), dim3(kPruneChunk), 0, e->stream,
                      (const double*)e->d_prune_bounds.p, (int)nq, (const uint8_t*)e->d_prune_in_seed.p,
-                     (const SearchEntry*)e->d_search_best.p, (const int*)e->d_search_counts.p, k, blocks, surv_q,
-                     surv_off, e->d_prune_chunks.p);
+                     (const SearchEntry*)e->d_search_best.p, (const int*)e->d_search_counts.p, k, floor_key, blocks,
+                     surv_q, surv_off, e->d_prune_chunks.p);
   if (hipGetLastError() != hipSuccess)
     return drained(e->fail(BPF_ERR_HIP, "k_prune_survivors launch"));
   rc = pinned_down_sync(e, e->h_prune_chunks, 0, e->d_prune_chunks, 0, (size_t)n_chunks, e->stream);
+  if (rc == BPF_OK && sh)
+    rc = shard_search_floor_arrived(e, sh);  // (the floor's exchange rides on this wait)
   if (rc != BPF_OK)
     return drained(rc);
   long long survivors = 0, members = 0;
@@ -425,7 +466,7 @@ int cloud_search_poses_pruned(bpf_engine* e, const float* points_xyz, int n_poin
     const int n = (int)std::min<long long>(members - done, kSearchWindow);
     hipLaunchKernelGGL(k_prune_expand, dim3(blocks_for(n, 256)), dim3(256), 0, e->stream, e->cand.dev(),
                        e->d_prune_ids.p, n, done, (const double*)e->d_prune_bounds.p,
-                       (const SearchEntry*)e->d_search_best.p, (const int*)e->d_search_counts.p, k,
+                       (const SearchEntry*)e->d_search_best.p, (const int*)e->d_search_counts.p, k, floor_key,
                        (const int*)surv_q, (const int*)surv_off, (const int2*)e->d_prune_chunks.p,
                        (const long long*)e->d_prune_chunk_off.p, n_chunks, e->d_prune_state.p, e->d_prune_words.p,
                        blocks, call.S);
@@ -441,7 +482,8 @@ int cloud_search_poses_pruned(bpf_engine* e, const float* points_xyz, int n_poin
   rc = pinned_down(e, e->h_prune_words, 0, e->d_prune_words, 0, kPruneWords, e->stream);
   if (rc != BPF_OK)
     return drained(rc);
-  rc = search_finish(e, call.S, k, hits_out, n_hits_out);
+  rc = sh ? shard_search_finish(e, sh, call.S, k, hits_out, n_hits_out)
+          : search_finish(e, call.S, k, hits_out, n_hits_out);
   if (rc != BPF_OK)
     return drained(rc);
   const unsigned long long* w = e->h_prune_words.p;

@@ -92,6 +92,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_pose_search_cloud.inl"
 #include "abi_pose_search_pruned.inl"
 #include "abi_pose_search_cloud_pruned.inl"
+#include "abi_shard_search.inl"
 #include "abi_pose_refine.inl"
 #include "abi_pose_moments.inl"
 #include "abi_bootstrap.inl"

@@ -489,6 +489,9 @@ struct bpf_engine
   DevBuf<bpf_pose_hit> d_search_hits;  // [kSearchMaxK] the rows on their way to the host
   PinnedBuf<bpf_pose_hit> h_search_hits;
   PinnedBuf<int> h_search_count;
+  // the sharded search (abi_shard_search.inl): a list travels as K + 1 entries, a header (count, 0) and K rows
+  DevBuf<SearchEntry> d_shard_lists;         // [K + 1] this rank's packed list, then [world][K + 1] the gathered ones
+  DevBuf<unsigned long long> d_shard_floor;  // [0] this rank's K-th key, [1] the floor, [2 ...] the W gathered keys
 
   // ---- pruned pose search (kernels_pose_search_pruned.hpp, abi_pose_search_pruned.inl): one pooled image per
   // (map version, B) and one block list per (map version, radius, stride, B), a slot per allowed B (log2 B - 1), so

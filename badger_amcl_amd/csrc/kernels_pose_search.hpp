@@ -10,6 +10,7 @@
 //   k_search_merge        ONE block folds the tiles' lists into the running best-K list (bitonic merge of two sorted
 //                         halves in LDS, one round per tile that kept something)
 //   k_search_hits         the final list as bpf_pose_hit rows
+// and two for the sharded search (abi_shard_search.inl): k_search_pack_list, k_search_merge_lists
 //
 // Order: score descending, equal scores by candidate ascending, NaN below every number.  An entry is 16 bytes: `key`,
 // the score's bits mapped so that unsigned order is numeric order (NaN -> 0, -0.0 -> +0.0; a non-negative double
@@ -226,10 +227,12 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_select(const double* 
 // One block: best[0 .. *best_count) (sorted) and every tile's sorted list -> the best K of them all, sorted, back in
 // `best`.  Kp = the power of two >= max(K, 2): the list sits in s[0 .. Kp), a tile's list reversed in s[Kp .. 2 Kp),
 // empties between them -- a bitonic sequence, which log2(2 Kp) compare-exchange stages sort.
-__global__ __launch_bounds__(kSearchThreads) void k_search_merge(SearchEntry* __restrict__ best,
-                                                                 int* __restrict__ best_count, int K, int Kp,
-                                                                 const SearchEntry* __restrict__ tile_out,
-                                                                 const int* __restrict__ tile_count, int n_tiles)
+// The body serves two kernels: list b starts at lists[b * list_stride] and holds counts[b * count_stride] entries --
+// the tiles of a window (k_search_merge: stride K, int counts) or the ranks' gathered lists (k_search_merge_lists).
+template <typename CountT>
+__device__ __forceinline__ void search_merge_body(SearchEntry* __restrict__ best, int* __restrict__ best_count, int K,
+                                                  int Kp, const SearchEntry* __restrict__ lists, size_t list_stride,
+                                                  const CountT* __restrict__ counts, size_t count_stride, int n_lists)
 {
   __shared__ SearchEntry s[2 * kSearchMaxK];
   const int tid = threadIdx.x;
@@ -237,16 +240,16 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_merge(SearchEntry* __
   for (int t = tid; t < Kp; t += kSearchThreads)
     s[t] = t < have ? best[t] : SearchEntry{ 0ull, 0ull };
   int total = have;
-  for (int b = 0; b < n_tiles; ++b)
+  for (int b = 0; b < n_lists; ++b)
   {
-    const int cnt = tile_count[b];  // (the same for every thread: the loop stays uniform)
+    const int cnt = (int)counts[(size_t)b * count_stride];  // (the same for every thread: the loop stays uniform)
     if (cnt == 0)
       continue;
     total += cnt;
     for (int t = tid; t < Kp; t += kSearchThreads)
     {
       const int src = Kp - 1 - t;
-      s[Kp + t] = src < cnt ? tile_out[(size_t)b * K + src] : SearchEntry{ 0ull, 0ull };
+      s[Kp + t] = src < cnt ? lists[(size_t)b * list_stride + src] : SearchEntry{ 0ull, 0ull };
     }
     __syncthreads();
     for (int j = Kp; j > 0; j >>= 1)
@@ -270,6 +273,39 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_merge(SearchEntry* __
     best[t] = s[t];
   if (tid == 0)
     *best_count = keep;
+}
+
+__global__ __launch_bounds__(kSearchThreads) void k_search_merge(SearchEntry* __restrict__ best,
+                                                                 int* __restrict__ best_count, int K, int Kp,
+                                                                 const SearchEntry* __restrict__ tile_out,
+                                                                 const int* __restrict__ tile_count, int n_tiles)
+{
+  search_merge_body<int>(best, best_count, K, Kp, tile_out, (size_t)K, tile_count, 1, n_tiles);
+}
+
+// ---- the ranks' lists of a sharded search (abi_shard_search.inl).  A rank's list travels as K + 1 entries of two
+// int64 words each: a header (count, 0), then K rows, the ones behind the count empty.
+// this rank's list in that form
+__global__ __launch_bounds__(kSearchThreads) void k_search_pack_list(const SearchEntry* __restrict__ best,
+                                                                     const int* __restrict__ best_count, int K,
+                                                                     SearchEntry* __restrict__ out)
+{
+  const int have = min(*best_count, K);
+  for (int t = threadIdx.x; t < K; t += kSearchThreads)
+    out[1 + t] = t < have ? best[t] : SearchEntry{ 0ull, 0ull };
+  if (threadIdx.x == 0)
+    out[0] = SearchEntry{ (unsigned long long)have, 0ull };
+}
+
+// ONE block: the W gathered lists (rank r's header at gathered[r * (K + 1)]) folded into the best K of them all, in
+// `best` / `best_count` (which the caller emptied)
+__global__ __launch_bounds__(kSearchThreads) void k_search_merge_lists(SearchEntry* __restrict__ best,
+                                                                       int* __restrict__ best_count, int K, int Kp,
+                                                                       const SearchEntry* __restrict__ gathered,
+                                                                       int n_lists)
+{
+  search_merge_body<unsigned long long>(best, best_count, K, Kp, gathered + 1, (size_t)K + 1, &gathered[0].key,
+                                        2 * ((size_t)K + 1), n_lists);
 }
 
 // the list as rows for the caller

@@ -15,6 +15,8 @@
 //                               1024 in index order; the host sums the chunk totals (the call's one intermediate wait)
 //   k_prune_expand              one window of the survivors' members; every block candidate is checked once more
 //                               against the tau of that moment and dropped whole if its bound is below it
+//   k_prune_floor_word / k_prune_floor   a sharded search only: the ranks' K-th keys behind the seed, their maximum as
+//                               a floor under tau for the two kernels above
 //
 // tau lives in device memory (the K-th row of the running exact list) and only changes between kernels of the one
 // stream.  No block waits for another.  A dropped or empty slot of a window carries a NaN pose, which the scoring path
@@ -314,11 +316,49 @@ __global__ __launch_bounds__(kSearchThreads) void k_prune_select(const double* _
   search_select_tile<true>(scores, n, 0ll, ids, K, best, best_count, tile_out, tile_count);
 }
 
-// tau of this moment: the K-th score of the exact list once it holds K rows (*full), as a double
-__device__ __forceinline__ double prune_tau(const SearchEntry* best, const int* best_count, int K, bool* full)
+// tau of this moment: the K-th score of the exact list once it holds K rows (*full), as a double.  floor_key (null in
+// the single-engine calls): the largest K-th key any rank of a sharded search published behind its seed
+// (k_prune_floor); non-zero, it is a tau of its own -- *full is true and tau the larger of the two.  A zero floor (no
+// rank's list was full, or its K-th score was a NaN) changes nothing.
+__device__ __forceinline__ double prune_tau(const SearchEntry* best, const int* best_count, int K,
+                                            const unsigned long long* floor_key, bool* full)
 {
-  *full = *best_count >= K;
-  return *full ? search_score_of(best[K - 1].key) : 0.0;
+  const bool own = *best_count >= K;
+  unsigned long long key = own ? best[K - 1].key : 0ull;
+  const unsigned long long fl = floor_key != nullptr ? *floor_key : 0ull;
+  if (fl != 0ull)
+  {
+    // key order is score order, and a NaN K-th score (key 0) is below every floor
+    key = (own && key > fl) ? key : fl;
+    *full = true;
+    return search_score_of(key);
+  }
+  *full = own;
+  return own ? search_score_of(key) : 0.0;
+}
+
+// ---- the shared floor of a sharded search (abi_shard_search.inl)
+// the word this rank publishes behind its seed: the key of the K-th row of its exact list if it holds K rows, else 0
+__global__ void k_prune_floor_word(const SearchEntry* __restrict__ best, const int* __restrict__ best_count, int K,
+                                   unsigned long long* __restrict__ word)
+{
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    *word = *best_count >= K ? best[K - 1].key : 0ull;
+}
+
+// one wave: *floor_key = the largest of the W gathered words
+__global__ __launch_bounds__(64) void k_prune_floor(const unsigned long long* __restrict__ words, int W,
+                                                    unsigned long long* __restrict__ floor_key)
+{
+  unsigned long long m = (int)threadIdx.x < W ? words[threadIdx.x] : 0ull;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+  {
+    const unsigned long long o = __shfl_xor(m, off, 64);
+    m = o > m ? o : m;
+  }
+  if (threadIdx.x == 0)
+    *floor_key = m;
 }
 
 // Chunk c = blockIdx.x takes block candidates c * 1024 ...: those outside the seed for which `bound < tau` is not
@@ -328,13 +368,14 @@ __global__ __launch_bounds__(kPruneChunk) void k_prune_survivors(const double* _
                                                                  const uint8_t* __restrict__ in_seed,
                                                                  const SearchEntry* __restrict__ best,
                                                                  const int* __restrict__ best_count, int K,
+                                                                 const unsigned long long* __restrict__ floor_key,
                                                                  PruneBlocks L, int* __restrict__ surv_q,
                                                                  int* __restrict__ surv_off,
                                                                  int2* __restrict__ chunk_info)
 {
   __shared__ int s_w[16];
   bool full;
-  const double tau = prune_tau(best, best_count, K, &full);
+  const double tau = prune_tau(best, best_count, K, floor_key, &full);
   const int q = blockIdx.x * kPruneChunk + (int)threadIdx.x;
   bool keep = false;
   int cnt = 0;
@@ -363,7 +404,8 @@ __global__ __launch_bounds__(kPruneChunk) void k_prune_survivors(const double* _
 // reach.  words[2 .. 4] count the decisions.
 __global__ void k_prune_expand(ParticlesDev dst, long long* __restrict__ ids, int n, long long base,
                                const double* __restrict__ bounds, const SearchEntry* __restrict__ best,
-                               const int* __restrict__ best_count, int K, const int* __restrict__ surv_q,
+                               const int* __restrict__ best_count, int K,
+                               const unsigned long long* __restrict__ floor_key, const int* __restrict__ surv_q,
                                const int* __restrict__ surv_off, const int2* __restrict__ chunk_info,
                                const long long* __restrict__ chunk_moff, int n_chunks, uint8_t* __restrict__ state,
                                unsigned long long* __restrict__ words, PruneBlocks L, SearchSpace S)
@@ -406,7 +448,7 @@ __global__ void k_prune_expand(ParticlesDev dst, long long* __restrict__ ids, in
   if (start >= base)
   {
     bool full;
-    const double tau = prune_tau(best, best_count, K, &full);
+    const double tau = prune_tau(best, best_count, K, floor_key, &full);
     drop = full && bounds[q] < tau;
     if (m == start)
     {

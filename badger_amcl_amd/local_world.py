@@ -12,8 +12,10 @@ import threading
 
 import numpy as np
 
-from .pf import BpfError, mixture_components
-from .sharded import RESAMPLE_FORMS, TREE_ROUTES, ShardedState, check_kld_modes, check_settings, even_counts
+from . import _lib
+from .pf import POSE_HIT_DTYPE, BpfError, mixture_components
+from .sharded import (RESAMPLE_FORMS, TREE_ROUTES, ShardedState, check_kld_modes, check_settings, even_counts,
+                      mixture_of_hits)
 
 EXCHANGE_NONE, EXCHANGE_MAILBOX, EXCHANGE_RCCL, EXCHANGE_LOCAL = 0, 1, 2, 3
 STATS_ROUTES = {1: "gathered", 2: "distributed", 3: "host"}
@@ -394,6 +396,80 @@ class LocalShardedFilter:
             if g.tobytes() != got[0].tobytes():
                 raise RuntimeError("LocalShardedFilter: the ranks' pose arrays differ")
         return got[0]
+
+    # ---- global localisation: pose search over the ranks
+    def _search(self, k, call, want_stats):
+        """call(rank, handle, lib, hits*, n*, stats*) -> status on every rank's thread; the rows (rank 0's, after all
+        ranks' rows were compared as bytes) and, for the pruned forms, every rank's stats."""
+        W = self.world
+        hits = [np.zeros(max(int(k), 1), dtype=POSE_HIT_DTYPE) for _ in range(W)]
+        ns = [C.c_int(0) for _ in range(W)]
+        sts = [_lib.PoseSearchStats() for _ in range(W)]
+        self._collective(lambda r, h, lib: call(r, h, lib, hits[r].ctypes.data_as(C.POINTER(_lib.PoseHit)),
+                                                C.byref(ns[r]), C.byref(sts[r])))
+        rows = [hits[r][:ns[r].value] for r in range(W)]
+        for r in range(1, W):
+            if rows[r].tobytes() != rows[0].tobytes():
+                raise RuntimeError("LocalShardedFilter: the ranks' search rows differ (rank %d)" % r)
+        if want_stats:
+            return rows[0], [{name: getattr(st, name) for name, _ in _lib.PoseSearchStats._fields_} for st in sts]
+        return rows[0]
+
+    def search_poses(self, data, headings, cell_stride, k, first=0, count=-1):
+        """PlanarScanner.searchPoses over the ranks (bpf_shard_search_poses): rank r scores candidates
+        [first + T r / W, first + T (r + 1) / W) of the T given, the lists are merged on the device, and the rows are
+        the single engine's, byte for byte.  Every engine carries the map and the scanner's model already, as for
+        update_sensor."""
+        rp, ap = data.pointers()
+        return self._search(k, lambda r, h, lib, hits, n, st: lib.bpf_shard_search_poses(
+            h, rp, ap, data.range_count_, data.range_max_, int(headings), int(cell_stride), int(first), int(count),
+            int(k), hits, n), False)
+
+    def search_poses_pruned(self, data, headings, cell_stride, k, block=8, first_block=0, block_count=-1):
+        """PlanarScanner.searchPosesPruned over the ranks (bpf_shard_search_poses_pruned): the block range is split,
+        and behind their seeds the ranks prune against the largest k-th score any of them holds.  Returns
+        (rows, per-rank stats); a rank's stats count its own share."""
+        rp, ap = data.pointers()
+        return self._search(k, lambda r, h, lib, hits, n, st: lib.bpf_shard_search_poses_pruned(
+            h, rp, ap, data.range_count_, data.range_max_, int(headings), int(cell_stride), int(block),
+            int(first_block), int(block_count), int(k), hits, n, st), True)
+
+    def cloud_search_poses(self, data, headings, cell_stride, k, first=0, count=-1):
+        """PointCloudScanner.searchPoses over the ranks (bpf_shard_cloud_search_poses)."""
+        pts = data.points_
+        ptr = pts.ctypes.data_as(C.POINTER(C.c_float))
+        return self._search(k, lambda r, h, lib, hits, n, st: lib.bpf_shard_cloud_search_poses(
+            h, ptr, pts.shape[0], int(headings), int(cell_stride), int(first), int(count), int(k), hits, n), False)
+
+    def cloud_search_poses_pruned(self, data, headings, cell_stride, k, block=8, first_block=0, block_count=-1):
+        """PointCloudScanner.searchPosesPruned over the ranks (bpf_shard_cloud_search_poses_pruned): (rows, per-rank
+        stats)."""
+        pts = data.points_
+        ptr = pts.ctypes.data_as(C.POINTER(C.c_float))
+        return self._search(k, lambda r, h, lib, hits, n, st: lib.bpf_shard_cloud_search_poses_pruned(
+            h, ptr, pts.shape[0], int(headings), int(cell_stride), int(block), int(first_block), int(block_count),
+            int(k), hits, n, st), True)
+
+    def localize(self, scanners, data, headings, cell_stride, k, refine, moments, mixture, pruned=True, block=8):
+        """Global localisation in one call, host composition only: the sharded search; refinePoses and poseMoments on
+        every rank (replicated: at most 1024 lattices, identical inputs on identical devices); mixtureFromHits and
+        mixtureApplyMoments; init_with_mixture.  scanners[r]: rank r's PlanarScanner or PointCloudScanner.
+        refine = (xy_radius, xy_step, theta_radius, theta_step, levels); moments = (xy_radius, xy_step, theta_radius,
+        theta_step, baseline, sigma_floor, sigma_cap); mixture = (xy_merge, theta_merge, max_components, sigma).
+        Returns the components."""
+        cloud = hasattr(data, "points_")
+        if pruned:
+            hits, _ = (self.cloud_search_poses_pruned if cloud else self.search_poses_pruned)(
+                data, headings, cell_stride, k, block)
+        else:
+            hits = (self.cloud_search_poses if cloud else self.search_poses)(data, headings, cell_stride, k)
+        comps = self.for_each_rank(lambda r, pf: mixture_of_hits(scanners[r], data, hits, self.max_global, refine,
+                                                                 moments, mixture))
+        for c in comps[1:]:
+            if c.tobytes() != comps[0].tobytes():
+                raise RuntimeError("LocalShardedFilter: the ranks' mixtures differ")
+        self.init_with_mixture(comps[0])
+        return comps[0]
 
     def selftest(self, rounds=1):
         """bpf_shard_local_selftest on every rank."""

@@ -53,7 +53,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .pf import mixture_components
+from . import _lib
+from .pf import POSE_HIT_DTYPE, merge_pose_hits, mixture_components, mixtureApplyMoments, mixtureFromHits
 
 
 class _DevArray:
@@ -555,6 +556,43 @@ class HipShardBackend:
         self.e.check(self.e.lib.bpf_shard_init_with_random_poses_all(self.e.h))
         return self.global_leaf_count()
 
+    # ---- pose search over the ranks (include/badger_pf.h, bpf_shard_search_poses and its three siblings)
+    def exchange_mode(self):
+        """bpf_shard_exchange_mode: 0 while the engine has no exchange of its own (mailbox, RCCL or a local world)"""
+        m = C.c_int(-1)
+        self.e.check(self.e.lib.bpf_shard_exchange_mode(self.e.h, C.byref(m)))
+        return m.value
+
+    def _search_all(self, k, call):
+        hits = np.zeros(max(int(k), 1), dtype=POSE_HIT_DTYPE)
+        n, st = C.c_int(), _lib.PoseSearchStats()
+        self.e.check(call(hits.ctypes.data_as(C.POINTER(_lib.PoseHit)), C.byref(n), C.byref(st)))
+        return hits[:n.value], {name: getattr(st, name) for name, _ in _lib.PoseSearchStats._fields_}
+
+    def search_poses_all(self, data, headings, cell_stride, k, first, count):
+        """The whole sharded search over the engine's own exchange: the rows (planar scan or cloud by the data)."""
+        if hasattr(data, "points_"):
+            pts = data.points_
+            return self._search_all(k, lambda hits, n, st: self.e.lib.bpf_shard_cloud_search_poses(
+                self.e.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], int(headings), int(cell_stride),
+                int(first), int(count), int(k), hits, n))[0]
+        rp, ap = data.pointers()
+        return self._search_all(k, lambda hits, n, st: self.e.lib.bpf_shard_search_poses(
+            self.e.h, rp, ap, data.range_count_, data.range_max_, int(headings), int(cell_stride), int(first),
+            int(count), int(k), hits, n))[0]
+
+    def search_poses_pruned_all(self, data, headings, cell_stride, k, block, first_block, block_count):
+        """The pruned sharded search over the engine's own exchange: (rows, this rank's stats)."""
+        if hasattr(data, "points_"):
+            pts = data.points_
+            return self._search_all(k, lambda hits, n, st: self.e.lib.bpf_shard_cloud_search_poses_pruned(
+                self.e.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], int(headings), int(cell_stride),
+                int(block), int(first_block), int(block_count), int(k), hits, n, st))
+        rp, ap = data.pointers()
+        return self._search_all(k, lambda hits, n, st: self.e.lib.bpf_shard_search_poses_pruned(
+            self.e.h, rp, ap, data.range_count_, data.range_max_, int(headings), int(cell_stride), int(block),
+            int(first_block), int(block_count), int(k), hits, n, st))
+
     def global_leaf_count(self):
         a, b = C.c_int(), C.c_int()
         self.e.check(self.e.lib.bpf_shard_global_leaf_count(self.e.h, C.byref(a), C.byref(b)))
@@ -657,6 +695,15 @@ def check_kld_modes(who, modes):
     if len(set(int(m) for m in modes)) != 1:
         raise ValueError("%s: the ranks use different KLD count modes %s" % (who, modes))
     return int(modes[0])
+
+
+def mixture_of_hits(scanner, data, hits, total_count, refine, moments, mixture):
+    """What localize() runs on a rank between the search and the init: refinePoses, poseMoments, mixtureFromHits and
+    mixtureApplyMoments, as one engine would run them; the components."""
+    refined = scanner.refinePoses(data, hits, *refine)
+    xy_radius, xy_step, theta_radius, theta_step, baseline, sigma_floor, sigma_cap = moments
+    rows = scanner.poseMoments(data, refined, xy_radius, xy_step, theta_radius, theta_step, baseline)
+    return mixtureApplyMoments(mixtureFromHits(refined, total_count, *mixture), rows, sigma_floor, sigma_cap)
 
 
 def even_counts(n, W):
@@ -1371,6 +1418,78 @@ class ShardedFilter:
             return None
         rows = self._concat_ragged(allr, sel_counts).contiguous()
         return self.b.pose_array_from_rows(rows, count)
+
+    # ---- global localisation: pose search over the ranks
+    def _engine_exchange(self):
+        """The engine's own transport carries the one-call searches: the mailbox, or a world the engines were
+        connected to outside this class (bpf_shard_bootstrap, bpf_shard_connect_local)."""
+        return self.mailbox or (hasattr(self.b, "exchange_mode") and self.b.exchange_mode() != 0)
+
+    def _share(self, first, total):
+        lo, hi = (total * self.rank) // self.world, (total * (self.rank + 1)) // self.world
+        return first + lo, hi - lo
+
+    def _merge_rows(self, rows, k):
+        """The ranks' hit rows (at most k each) gathered as int64 words and merged on the host."""
+        words = np.zeros(7 * int(k) + 1, dtype=np.int64)
+        words[0] = rows.shape[0]
+        words[1:1 + 7 * rows.shape[0]] = np.ascontiguousarray(rows).view(np.int64)
+        allw = self._all_gather(torch.from_numpy(words).to(self.device)).cpu().numpy().reshape(self.world, -1)
+        lists = [np.ascontiguousarray(w[1:1 + 7 * int(w[0])]).view(POSE_HIT_DTYPE) for w in allw]
+        return merge_pose_hits(lists, k)
+
+    def search_poses(self, data, headings, cell_stride, k, first=0, count=-1):
+        """The scanner's searchPoses (planar scan or cloud, by the data) over the ranks: collective, the same
+        arguments on every rank, the single engine's rows for the range on every rank.  Rank r scores candidates
+        [first + T r / W, first + T (r + 1) / W) of the T given.  On the engine's own transport the lists are merged
+        on the device (bpf_shard_search_poses); on collectives the rows are gathered as int64 words and merged on the
+        host."""
+        sc = self.b.sc
+        total = sc.searchSpace(headings, cell_stride)[0]
+        if not (1 <= int(k) <= 1024) or first < 0 or first > total or count < -1 or count > total - first:
+            raise ValueError("search_poses: 1 <= k <= 1024 and first / count inside the candidate space")
+        if hasattr(self.b, "search_poses_all") and self._engine_exchange():
+            return self.b.search_poses_all(data, headings, cell_stride, k, first, count)
+        lo, n = self._share(first, total - first if count < 0 else count)
+        mine = sc.searchPoses(data, headings, cell_stride, k, lo, n)
+        return self._merge_rows(mine, k)
+
+    def search_poses_pruned(self, data, headings, cell_stride, k, block=None, first_block=0, block_count=-1):
+        """The scanner's searchPosesPruned over the ranks: (rows, this rank's stats); the block range is split like
+        the candidates of search_poses.  On the engine's own transport the ranks share their tau behind the seed
+        (bpf_shard_search_poses_pruned).  On collectives there is NO shared tau: every rank prunes against the k-th
+        score of its own share, and the stats are those of the stand-alone range call."""
+        sc = self.b.sc
+        opt = {} if block is None else {"block": int(block)}
+        if block is None:
+            block = sc.searchPosesPruned.__defaults__[0]
+        total = sc.searchBlocks(cell_stride, block)
+        if (not (1 <= int(k) <= 1024) or first_block < 0 or first_block > total or block_count < -1
+                or block_count > total - first_block):
+            raise ValueError("search_poses_pruned: 1 <= k <= 1024 and first_block / block_count inside the block list")
+        if hasattr(self.b, "search_poses_pruned_all") and self._engine_exchange():
+            return self.b.search_poses_pruned_all(data, headings, cell_stride, k, block, first_block, block_count)
+        lo, n = self._share(first_block, total - first_block if block_count < 0 else block_count)
+        mine, stats = sc.searchPosesPruned(data, headings, cell_stride, k, first_block=lo, block_count=n, stats=True,
+                                           **opt)
+        return self._merge_rows(mine, k), stats
+
+    cloud_search_poses = search_poses
+    cloud_search_poses_pruned = search_poses_pruned
+
+    def localize(self, data, headings, cell_stride, k, refine, moments, mixture, pruned=True, block=None):
+        """Global localisation in one call, host composition only: the sharded search; refinePoses and poseMoments on
+        every rank (replicated: at most 1024 lattices, identical inputs on identical devices); mixtureFromHits and
+        mixtureApplyMoments; init_with_mixture.  refine = (xy_radius, xy_step, theta_radius, theta_step, levels);
+        moments = (xy_radius, xy_step, theta_radius, theta_step, baseline, sigma_floor, sigma_cap); mixture =
+        (xy_merge, theta_merge, max_components, sigma).  Returns the components."""
+        if pruned:
+            hits, _ = self.search_poses_pruned(data, headings, cell_stride, k, block)
+        else:
+            hits = self.search_poses(data, headings, cell_stride, k)
+        comps = mixture_of_hits(self.b.sc, data, hits, self.max_global, refine, moments, mixture)
+        self.init_with_mixture(comps)
+        return comps
 
     def set_random_pose_generator(self, mode):
         """random_pose_fn of this rank's engine (pf.RANDOM_POSE_*); every rank sets the same mode.  Every rank

@@ -21,6 +21,7 @@
 #include <condition_variable>
 #include <cstdint>
 #include <cmath>
+#include <cstring>
 #include <exception>
 #include <functional>
 #include <memory>
@@ -955,6 +956,85 @@ public:
     e().check(bpf_shard_update_sensor_cloud(e().get(), xyz, n, global_count_));
     return true;
   }
+  // NOT reference methods (badger_pf.h, "pose search over a sharded filter"): PlanarScanner::searchPoses /
+  // searchPosesPruned and PointCloudScanner's over the ranks.  The range given is split over the ranks, the ranks'
+  // lists are merged on the device, and every rank returns the single engine's rows for the range, byte for byte.
+  // The pruned forms share their tau behind the seed; stats_out counts this rank's share.
+  std::vector<bpf_pose_hit> searchPoses(std::shared_ptr<PlanarData> data, int headings, int cell_stride, int k,
+                                        long long first = 0, long long count = -1)
+  {
+    std::vector<bpf_pose_hit> hits((size_t)(k > 0 ? k : 1));
+    int n = 0;
+    e().check(bpf_shard_search_poses(e().get(), data->ranges_.data(), data->angles_.data(), data->range_count_,
+                                     data->range_max_, headings, cell_stride, first, count, k, hits.data(), &n));
+    hits.resize((size_t)n);
+    return hits;
+  }
+  std::vector<bpf_pose_hit> searchPosesPruned(std::shared_ptr<PlanarData> data, int headings, int cell_stride, int k,
+                                              int block = 8, int first_block = 0, int block_count = -1,
+                                              bpf_pose_search_stats* stats_out = nullptr)
+  {
+    std::vector<bpf_pose_hit> hits((size_t)(k > 0 ? k : 1));
+    int n = 0;
+    e().check(bpf_shard_search_poses_pruned(e().get(), data->ranges_.data(), data->angles_.data(), data->range_count_,
+                                            data->range_max_, headings, cell_stride, block, first_block, block_count,
+                                            k, hits.data(), &n, stats_out));
+    hits.resize((size_t)n);
+    return hits;
+  }
+  std::vector<bpf_pose_hit> searchPosesCloud(const float* xyz, int n_points, int headings, int cell_stride, int k,
+                                             long long first = 0, long long count = -1)
+  {
+    std::vector<bpf_pose_hit> hits((size_t)(k > 0 ? k : 1));
+    int n = 0;
+    e().check(bpf_shard_cloud_search_poses(e().get(), xyz, n_points, headings, cell_stride, first, count, k,
+                                           hits.data(), &n));
+    hits.resize((size_t)n);
+    return hits;
+  }
+  std::vector<bpf_pose_hit> searchPosesCloudPruned(const float* xyz, int n_points, int headings, int cell_stride,
+                                                   int k, int block = 8, int first_block = 0, int block_count = -1,
+                                                   bpf_pose_search_stats* stats_out = nullptr)
+  {
+    std::vector<bpf_pose_hit> hits((size_t)(k > 0 ? k : 1));
+    int n = 0;
+    e().check(bpf_shard_cloud_search_poses_pruned(e().get(), xyz, n_points, headings, cell_stride, block, first_block,
+                                                  block_count, k, hits.data(), &n, stats_out));
+    hits.resize((size_t)n);
+    return hits;
+  }
+  // What localize() takes besides the search's arguments: the lattices of refinePoses and poseMoments, the clamps of
+  // mixtureApplyMoments and the arguments of mixtureFromHits
+  struct LocalizeSettings
+  {
+    int refine_xy_radius = 2, refine_theta_radius = 2, refine_levels = 2;
+    double refine_xy_step = 0.025, refine_theta_step = 0.02;
+    int moments_xy_radius = 2, moments_theta_radius = 2;
+    double moments_xy_step = 0.025, moments_theta_step = 0.02, baseline = 0.5;
+    std::array<double, 3> sigma_floor{ { 0.01, 0.01, 0.01 } }, sigma_cap{ { 1.0, 1.0, 1.0 } };
+    double xy_merge = 0.5, theta_merge = 0.5;
+    int max_components = 8;
+    std::array<double, 3> sigma{ { 0.1, 0.1, 0.05 } };
+    bool pruned = true;
+    int block = 8;
+  };
+  // Global localisation in one call, host composition only: the sharded search; refinePoses and poseMoments with this
+  // rank's scanner (replicated on every rank: at most 1024 lattices, identical inputs on identical devices);
+  // mixtureFromHits and mixtureApplyMoments; initWithMixture.  Returns the components.
+  std::vector<MixtureComponent> localize(PlanarScanner& scanner, std::shared_ptr<PlanarData> data, int headings,
+                                         int cell_stride, int k, const LocalizeSettings& s)
+  {
+    const std::vector<bpf_pose_hit> hits = s.pruned ? searchPosesPruned(data, headings, cell_stride, k, s.block)
+                                                    : searchPoses(data, headings, cell_stride, k);
+    const std::vector<bpf_pose_refined> refined = scanner.refinePoses(
+        data, hits, s.refine_xy_radius, s.refine_xy_step, s.refine_theta_radius, s.refine_theta_step, s.refine_levels);
+    const std::vector<bpf_pose_moments> rows = scanner.poseMoments(
+        data, refined, s.moments_xy_radius, s.moments_xy_step, s.moments_theta_radius, s.moments_theta_step, s.baseline);
+    PoseMixture mix = mixtureFromHits(refined, pf_->maxSamples(), s.xy_merge, s.theta_merge, s.max_components, s.sigma);
+    mix.mixtureApplyMoments(rows, s.sigma_floor, s.sigma_cap);
+    initWithMixture(mix.components);
+    return mix.components;
+  }
   // BPF_SHARD_RESAMPLE_WINDOW (the default) or BPF_SHARD_RESAMPLE_IN_PLACE: the systematic resampler resamples this
   // rank's slice into itself (badger_pf.h, bpf_shard_set_resample_form); every rank sets the same values
   void setResampleForm(int form, double max_share = 2.0)
@@ -1171,6 +1251,62 @@ public:
     fanOut([&](int r) { ranks_[(size_t)r]->updateSensorCloud(xyz, n); });
     return true;
   }
+  // the sharded searches and localize() of every rank; the ranks' rows are compared as bytes, rank 0's come back.
+  // stats_out, when given, receives every rank's counters
+  std::vector<bpf_pose_hit> searchPoses(std::shared_ptr<PlanarData> data, int headings, int cell_stride, int k,
+                                        long long first = 0, long long count = -1)
+  {
+    return sameRows([&](int r) { return ranks_[(size_t)r]->searchPoses(data, headings, cell_stride, k, first, count); });
+  }
+  std::vector<bpf_pose_hit> searchPosesPruned(std::shared_ptr<PlanarData> data, int headings, int cell_stride, int k,
+                                              int block = 8, int first_block = 0, int block_count = -1,
+                                              std::vector<bpf_pose_search_stats>* stats_out = nullptr)
+  {
+    std::vector<bpf_pose_search_stats> st(ranks_.size());
+    auto rows = sameRows([&](int r) {
+      return ranks_[(size_t)r]->searchPosesPruned(data, headings, cell_stride, k, block, first_block, block_count,
+                                                  &st[(size_t)r]);
+    });
+    if (stats_out)
+      *stats_out = st;
+    return rows;
+  }
+  std::vector<bpf_pose_hit> searchPosesCloud(const float* xyz, int n_points, int headings, int cell_stride, int k,
+                                             long long first = 0, long long count = -1)
+  {
+    return sameRows(
+        [&](int r) { return ranks_[(size_t)r]->searchPosesCloud(xyz, n_points, headings, cell_stride, k, first, count); });
+  }
+  std::vector<bpf_pose_hit> searchPosesCloudPruned(const float* xyz, int n_points, int headings, int cell_stride,
+                                                   int k, int block = 8, int first_block = 0, int block_count = -1,
+                                                   std::vector<bpf_pose_search_stats>* stats_out = nullptr)
+  {
+    std::vector<bpf_pose_search_stats> st(ranks_.size());
+    auto rows = sameRows([&](int r) {
+      return ranks_[(size_t)r]->searchPosesCloudPruned(xyz, n_points, headings, cell_stride, k, block, first_block,
+                                                       block_count, &st[(size_t)r]);
+    });
+    if (stats_out)
+      *stats_out = st;
+    return rows;
+  }
+  // scanners[r]: rank r's scanner
+  std::vector<MixtureComponent> localize(const std::vector<std::shared_ptr<PlanarScanner>>& scanners,
+                                         std::shared_ptr<PlanarData> data, int headings, int cell_stride, int k,
+                                         const ShardedParticleFilter::LocalizeSettings& s)
+  {
+    if (scanners.size() != ranks_.size())
+      throw std::invalid_argument("LocalShardedParticleFilter::localize: one scanner per rank");
+    std::vector<std::vector<MixtureComponent>> got(ranks_.size());
+    fanOut([&](int r) {
+      got[(size_t)r] = ranks_[(size_t)r]->localize(*scanners[(size_t)r], data, headings, cell_stride, k, s);
+    });
+    for (auto& g : got)
+      if (g.size() != got[0].size() ||
+          (!g.empty() && std::memcmp(g.data(), got[0].data(), g.size() * sizeof(MixtureComponent)) != 0))
+        throw std::runtime_error("LocalShardedParticleFilter: the ranks' mixtures differ");
+    return got[0];
+  }
   void setResampleForm(int form, double max_share = 2.0)
   {
     for (auto& s : ranks_)
@@ -1304,6 +1440,17 @@ private:
       throw std::runtime_error("LocalShardedParticleFilter: the ranks' statuses differ (" + std::to_string(failed) +
                                " of " + std::to_string(workers_.size()) + " failed)");
     std::rethrow_exception(workers_[0].error);
+  }
+  // search(rank) on every rank's thread; rank 0's rows after all ranks' rows were compared as bytes
+  std::vector<bpf_pose_hit> sameRows(const std::function<std::vector<bpf_pose_hit>(int)>& search)
+  {
+    std::vector<std::vector<bpf_pose_hit>> got(ranks_.size());
+    fanOut([&](int r) { got[(size_t)r] = search(r); });
+    for (auto& g : got)
+      if (g.size() != got[0].size() ||
+          (!g.empty() && std::memcmp(g.data(), got[0].data(), g.size() * sizeof(bpf_pose_hit)) != 0))
+        throw std::runtime_error("LocalShardedParticleFilter: the ranks' search rows differ");
+    return got[0];
   }
   std::vector<std::unique_ptr<ShardedParticleFilter>> ranks_;
   std::vector<Worker> workers_;

@@ -1355,6 +1355,44 @@ int bpf_cloud_search_pooled_lut(bpf_engine* e, int block, unsigned char* bytes_o
 int bpf_cloud_search_bounds(bpf_engine* e, const float* points_xyz, int n_points, int headings, int cell_stride,
                             int block, long long first_q, long long count, double* bounds_out);
 
+/* ------------------------------------------------------------------ pose search over a sharded filter
+ * The four searches above as one collective call each: every rank of a connected world (bpf_shard_bootstrap,
+ * bpf_shard_mailbox_connect or bpf_shard_connect_local) calls with the SAME arguments and the same scan or cloud, and
+ * every rank returns the same rows -- the single engine's rows for that range, byte for byte.  NOT reference calls.
+ *
+ * Split.  The range given has T units (candidates for the exhaustive forms, blocks for the pruned ones; count /
+ * block_count = -1: to the end); rank r of W takes units [first + T r / W, first + T (r + 1) / W) in integer
+ * arithmetic.  A rank whose share is empty scores nothing and contributes an empty list.
+ * Merge.  A rank's best-k list stays on the device; it crosses between the ranks as 16 bytes per row (k rows and a
+ * header, over the engine's exchange), the W lists are folded into the best k on every rank's device in the order of
+ * the single-engine search (score descending, equal scores by candidate, NaN last), and only the k rows come down.
+ * Shared tau (pruned forms).  Behind its seed stage every rank publishes the key of the k-th score of its exact list
+ * (0 while the list is short or that score is a NaN); the largest of the W words is a floor under every rank's tau
+ * from then on.  The global k-th best score is at least every rank's tau, so a block candidate whose bound is
+ * strictly below the floor holds no row of the result.  A rank's OWN list is then no longer the best k of its range:
+ * only the merged rows are a result, and stats_out (this rank's counters, for this rank's share) depends on the
+ * other ranks' seeds.
+ *
+ * Everything the single-engine call refuses from its arguments and the configuration is refused before the first
+ * exchange, by every rank alike; the limit of 2^31 - 1 candidates applies to the whole space, the limit of 2^24 block
+ * candidates to each rank's share.  BPF_ERR_NOT_CONFIGURED without a connected world; BPF_ERR_CAPACITY when the
+ * mailbox's window region is smaller than W * (2 k + 2) words.  Read-only for the filter on every rank, as the
+ * single-engine searches are.  Nothing of this has run between two GPUs: what the split buys is counted in
+ * evaluations and bytes (profiles/pose_search_sharded.md), not measured as a speed-up. */
+int bpf_shard_search_poses(bpf_engine* e, const double* ranges, const double* angles, int range_count,
+                           double range_max, int headings, int cell_stride, long long first, long long count, int k,
+                           bpf_pose_hit* hits_out, int* n_hits_out);
+int bpf_shard_search_poses_pruned(bpf_engine* e, const double* ranges, const double* angles, int range_count,
+                                  double range_max, int headings, int cell_stride, int block, int first_block,
+                                  int block_count, int k, bpf_pose_hit* hits_out, int* n_hits_out,
+                                  bpf_pose_search_stats* stats_out /* nullable */);
+int bpf_shard_cloud_search_poses(bpf_engine* e, const float* points_xyz, int n_points, int headings, int cell_stride,
+                                 long long first, long long count, int k, bpf_pose_hit* hits_out, int* n_hits_out);
+int bpf_shard_cloud_search_poses_pruned(bpf_engine* e, const float* points_xyz, int n_points, int headings,
+                                        int cell_stride, int block, int first_block, int block_count, int k,
+                                        bpf_pose_hit* hits_out, int* n_hits_out,
+                                        bpf_pose_search_stats* stats_out /* nullable */);
+
 /* ------------------------------------------------------------------ pose refinement
  * Sub-cell, sub-degree poses from the hits of a search (or from any poses): a coarse-to-fine descent on a lattice
  * around each pose, all of it on the device.  NOT a reference call (parity unpinned by construction).
