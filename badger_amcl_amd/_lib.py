@@ -270,6 +270,17 @@ SIGNATURES = {
     "bpf_cloud_search_poses": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_longlong,
                                          C.c_longlong, C.c_int, C.POINTER(PoseHit), _ip]),
     "bpf_cloud_search_space": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _ip]),
+    "bpf_pose_search_heading_table": (C.c_int, [C.c_int, _dp, _dp]),
+    "bpf_planar_search_poses_joint": (C.c_int, [_vp, C.c_int, C.POINTER(_dp), C.POINTER(_dp), _ip, _dp, _dp, C.c_int,
+                                                C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.POINTER(PoseHit),
+                                                _ip]),
+    "bpf_cloud_search_poses_joint": (C.c_int, [_vp, C.c_int, C.POINTER(C.POINTER(C.c_float)), _ip, _dp, C.c_int,
+                                               C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.POINTER(PoseHit),
+                                               _ip]),
+    "bpf_planar_search_joint_poses": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(C.c_longlong),
+                                                C.c_int, _dp]),
+    "bpf_cloud_search_joint_poses": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(C.c_longlong),
+                                               C.c_int, _dp]),
     "bpf_cloud_search_poses_pruned": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_int, C.c_int, C.POINTER(PoseHit), _ip,
                                                 C.POINTER(PoseSearchStats)]),

@@ -518,7 +518,10 @@ bool cloud_border_form(const bpf_engine* e)
 // bound_volume (the bound pass of the pruned search, abi_pose_search_cloud_pruned.inl): a volume in the layout of
 // Map3dDev::dense that the kernel gathers from in its place, with off_map_factor taken as 1 in the epilogue.  Only the
 // BORDER form reads the volume for a sample that is off the map, so every other form is refused here.
-int launch_cloud(bpf_engine* e, ParticlesDev p, int n, int n_points, const uint8_t* bound_volume = nullptr)
+// points (the joint pose search, abi_pose_search_joint.inl): a cloud of n_points in the layout of d_points that the
+// kernel reads in its place.
+int launch_cloud(bpf_engine* e, ParticlesDev p, int n, int n_points, const uint8_t* bound_volume = nullptr,
+                 const float* points = nullptr)
 {
   if (bound_volume != nullptr && !cloud_border_form(e))
     return e->fail(BPF_ERR_UNSUPPORTED, "cloud bound pass: needs the planar dense kernel with the border codes");
@@ -529,7 +532,7 @@ int launch_cloud(bpf_engine* e, ParticlesDev p, int n, int n_points, const uint8
   CloudScoreArgs A{};
   A.n = n;
   A.affine = e->d_affine.p;
-  A.points = e->d_points.p;
+  A.points = points != nullptr ? points : e->d_points.p;
   A.n_points = n_points;
   A.map = e->map3;
   if (bound_volume != nullptr)

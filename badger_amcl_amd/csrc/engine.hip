@@ -33,6 +33,7 @@
 #include "kernels_pf.hpp"
 #include "kernels_pose_array.hpp"
 #include "kernels_pose_search.hpp"
+#include "kernels_pose_search_joint.hpp"
 #include "kernels_pose_refine.hpp"
 #include "kernels_pose_moments.hpp"
 #include "kernels_fused.hpp"
@@ -90,6 +91,7 @@ void host_buffers_release(bpf_engine* e);  // abi_hostbuf.inl
 #include "abi_pose_array.inl"
 #include "abi_pose_search.inl"
 #include "abi_pose_search_cloud.inl"
+#include "abi_pose_search_joint.inl"
 #include "abi_pose_search_pruned.inl"
 #include "abi_pose_search_cloud_pruned.inl"
 #include "abi_shard_search.inl"

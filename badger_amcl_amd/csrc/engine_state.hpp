@@ -493,6 +493,14 @@ struct bpf_engine
   DevBuf<SearchEntry> d_shard_lists;         // [K + 1] this rank's packed list, then [world][K + 1] the gathered ones
   DevBuf<unsigned long long> d_shard_floor;  // [0] this rank's K-th key, [1] the floor, [2 ...] the W gathered keys
 
+  // ---- joint pose search (kernels_pose_search_joint.hpp, abi_pose_search_joint.inl): cos / sin of the call's
+  // headings, the S clouds of a cloud call as float SoA one behind the other, and the candidates of a diagnostic call
+  DevBuf<double> d_joint_table;  // [2][H]: C_h, then S_h
+  PinnedBuf<double> h_joint_table;
+  DevBuf<float> d_joint_points;  // per scan [3][n_points_s]
+  PinnedBuf<float> h_joint_points;
+  DevBuf<long long> d_joint_ids;
+
   // ---- pruned pose search (kernels_pose_search_pruned.hpp, abi_pose_search_pruned.inl): one pooled image per
   // (map version, B) and one block list per (map version, radius, stride, B), a slot per allowed B (log2 B - 1), so
   // that calls with different B do not evict each other; then the working arrays of a call

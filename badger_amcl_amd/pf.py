@@ -568,6 +568,34 @@ class PlanarScanner:
             int(count), int(k), hits.ctypes.data_as(C.POINTER(_lib.PoseHit)), C.byref(n)))
         return hits[:n.value]
 
+    def searchPosesJoint(self, datas, offsets, headings, cell_stride, k, first=0, count=-1):
+        """NOT a reference method: searchPoses over several scans.  Scan s (datas[s], a PlanarData) is scored at the
+        candidate's pose composed with offsets[s] = (dx, dy, dth), the weight carried from scan to scan; the rows carry
+        the candidate's BASE pose.  See bpf_planar_search_poses_joint in include/badger_pf.h."""
+        if self.map is not None:
+            self.map.upload()
+        s = len(datas)
+        off = _joint_offsets(offsets, s)
+        hits = np.zeros(max(int(k), 1), dtype=POSE_HIT_DTYPE)
+        n = C.c_int()
+        dpp = C.POINTER(C.c_double) * max(s, 1)
+        ptrs = [d.pointers() for d in datas]
+        counts = np.array([d.range_count_ for d in datas] + [0], dtype=np.int32)
+        maxes = np.array([d.range_max_ for d in datas] + [0.0], dtype=np.float64)
+        self.e.check(self.e.lib.bpf_planar_search_poses_joint(
+            self.e.h, s, dpp(*[p[0] for p in ptrs]), dpp(*[p[1] for p in ptrs]),
+            counts.ctypes.data_as(C.POINTER(C.c_int)), _dp(maxes), _dp(off), int(headings), int(cell_stride),
+            int(first), int(count), int(k), hits.ctypes.data_as(C.POINTER(_lib.PoseHit)), C.byref(n)))
+        return hits[:n.value]
+
+    def searchJointPoses(self, offsets, headings, cell_stride, candidates):
+        """The composed poses searchPosesJoint scores, [n, S, 3] float64, of the candidate indices given: formed by
+        the search's own kernel (bpf_planar_search_joint_poses)."""
+        if self.map is not None:
+            self.map.upload()
+        return _joint_poses(self.e, self.e.lib.bpf_planar_search_joint_poses, offsets, headings, cell_stride,
+                            candidates)
+
     def searchBlocks(self, cell_stride=1, block=POSE_SEARCH_BLOCK):
         """Blocks of block x block cells that hold an entry of the strided free list: what a caller of
         searchPosesPruned splits into ranges."""
@@ -770,6 +798,37 @@ def pose_search_window():
     return int(_lib.load().bpf_pose_search_window())
 
 
+def pose_search_heading_table(headings):
+    """(cos, sin) of the `headings` headings of a pose search, float64 arrays: the table the joint searches compose
+    their poses with (the C library's cos / sin; needs no GPU)."""
+    h = int(headings)
+    c, s = np.zeros(max(h, 1), dtype=np.float64), np.zeros(max(h, 1), dtype=np.float64)
+    rc = _lib.load().bpf_pose_search_heading_table(h, _dp(c), _dp(s))
+    if rc != 0:
+        raise BpfError(rc, _lib.load().bpf_error_string(rc).decode())
+    return c[:h], s[:h]
+
+
+def _joint_offsets(offsets, n_scans):
+    """[S, 3] float64 offsets of a joint search, one (dx, dy, dth) per scan (one spare row, so that an empty list
+    still has an address)"""
+    off = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1, 3)
+    if off.shape[0] != n_scans:
+        raise ValueError("one offset (dx, dy, dth) per scan is needed")
+    return np.ascontiguousarray(np.vstack([off, np.zeros((1, 3))]))
+
+
+def _joint_poses(engine, call, offsets, headings, cell_stride, candidates):
+    """the marshalling both scanners' searchJointPoses share"""
+    off = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1, 3)
+    s = off.shape[0]
+    c = np.ascontiguousarray(candidates, dtype=np.int64).reshape(-1)
+    out = np.zeros((max(c.shape[0], 1), max(s, 1), 3), dtype=np.float64)
+    engine.check(call(engine.h, int(headings), int(cell_stride), _dp(_joint_offsets(off, s)), s,
+                      c.ctypes.data_as(C.POINTER(C.c_longlong)), c.shape[0], _dp(out)))
+    return out[:c.shape[0], :s]
+
+
 def merge_pose_hits(lists, k):
     """The best k rows of the hit lists of disjoint candidate ranges, in searchPoses' order (plain host code)."""
     lists = [np.ascontiguousarray(h, dtype=POSE_HIT_DTYPE) for h in lists]
@@ -905,6 +964,28 @@ class PointCloudScanner:
             self.e.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], int(headings), int(cell_stride),
             int(first), int(count), int(k), hits.ctypes.data_as(C.POINTER(_lib.PoseHit)), C.byref(n)))
         return hits[:n.value]
+
+    def searchPosesJoint(self, datas, offsets, headings, cell_stride, k, first=0, count=-1):
+        """NOT a reference method: searchPoses over several clouds.  Cloud s (datas[s], a PointCloudData) is scored
+        at the candidate's pose composed with offsets[s] = (dx, dy, dth), the weight carried from cloud to cloud; the
+        rows carry the candidate's BASE pose.  See bpf_cloud_search_poses_joint in include/badger_pf.h."""
+        s = len(datas)
+        off = _joint_offsets(offsets, s)
+        hits = np.zeros(max(int(k), 1), dtype=POSE_HIT_DTYPE)
+        n = C.c_int()
+        fp = C.POINTER(C.c_float)
+        counts = np.array([d.points_.shape[0] for d in datas] + [0], dtype=np.int32)
+        self.e.check(self.e.lib.bpf_cloud_search_poses_joint(
+            self.e.h, s, (fp * max(s, 1))(*[d.points_.ctypes.data_as(fp) for d in datas]),
+            counts.ctypes.data_as(C.POINTER(C.c_int)), _dp(off), int(headings), int(cell_stride), int(first),
+            int(count), int(k), hits.ctypes.data_as(C.POINTER(_lib.PoseHit)), C.byref(n)))
+        return hits[:n.value]
+
+    def searchJointPoses(self, offsets, headings, cell_stride, candidates):
+        """The composed poses searchPosesJoint scores, [n, S, 3] float64, of the candidate indices given: formed by
+        the search's own kernel (bpf_cloud_search_joint_poses)."""
+        return _joint_poses(self.e, self.e.lib.bpf_cloud_search_joint_poses, offsets, headings, cell_stride,
+                            candidates)
 
     def searchBlocks(self, cell_stride=1, block=POSE_SEARCH_CLOUD_BLOCK):
         """Blocks of block x block columns that hold a column of the strided rectangle: what a caller of

@@ -496,6 +496,36 @@ public:
     hits.resize((size_t)n);
     return hits;
   }
+  // NOT a reference method (bpf_planar_search_poses_joint): searchPoses over several scans.  Scan s is scored at the
+  // candidate's pose composed with offsets[s] = (dx, dy, dth) -- the robot's pose at scan s in the frame of the
+  // candidate pose, an odometry delta --, the weight carried from scan to scan; the rows carry the BASE pose.
+  std::vector<bpf_pose_hit> searchPosesJoint(const std::vector<std::shared_ptr<PlanarData>>& datas,
+                                             const std::vector<std::array<double, 3>>& offsets, int headings,
+                                             int cell_stride, int k, long long first = 0, long long count = -1)
+  {
+    if (datas.size() != offsets.size())
+      throw std::invalid_argument("searchPosesJoint: one offset per scan is needed");
+    if (map_)
+      map_->upload();
+    std::vector<const double*> ranges, angles;
+    std::vector<int> counts;
+    std::vector<double> maxes, off;
+    for (size_t s = 0; s < datas.size(); ++s)
+    {
+      ranges.push_back(datas[s]->ranges_.data());
+      angles.push_back(datas[s]->angles_.data());
+      counts.push_back(datas[s]->range_count_);
+      maxes.push_back(datas[s]->range_max_);
+      off.insert(off.end(), offsets[s].begin(), offsets[s].end());
+    }
+    std::vector<bpf_pose_hit> hits((size_t)(k > 0 ? k : 1));
+    int n = 0;
+    e_->check(bpf_planar_search_poses_joint(e_->get(), (int)datas.size(), ranges.data(), angles.data(), counts.data(),
+                                            maxes.data(), off.data(), headings, cell_stride, first, count, k,
+                                            hits.data(), &n));
+    hits.resize((size_t)n);
+    return hits;
+  }
   // NOT a reference method (bpf_planar_search_poses_pruned): the rows of searchPoses over the candidates whose cells
   // lie in blocks first_block .. first_block + block_count - 1 (block_count = -1: to the end) of the list of
   // block x block cell blocks, bit for bit, from fewer exact evaluations.  Likelihood field and Gompertz only.
@@ -762,6 +792,31 @@ public:
     int n = 0;
     e_->check(bpf_cloud_search_poses(e_->get(), data->points_.data(), data->pointCount(), headings, cell_stride, first,
                                      count, k, hits.data(), &n));
+    hits.resize((size_t)n);
+    return hits;
+  }
+  // NOT a reference method (bpf_cloud_search_poses_joint): searchPoses over several clouds.  Cloud s is scored at the
+  // candidate's pose composed with offsets[s] = (dx, dy, dth) -- the robot's pose at cloud s in the frame of the
+  // candidate pose, an odometry delta --, the weight carried from cloud to cloud; the rows carry the BASE pose.
+  std::vector<bpf_pose_hit> searchPosesJoint(const std::vector<std::shared_ptr<PointCloudData>>& datas,
+                                             const std::vector<std::array<double, 3>>& offsets, int headings,
+                                             int cell_stride, int k, long long first = 0, long long count = -1)
+  {
+    if (datas.size() != offsets.size())
+      throw std::invalid_argument("searchPosesJoint: one offset per cloud is needed");
+    std::vector<const float*> points;
+    std::vector<int> counts;
+    std::vector<double> off;
+    for (size_t s = 0; s < datas.size(); ++s)
+    {
+      points.push_back(datas[s]->points_.data());
+      counts.push_back(datas[s]->pointCount());
+      off.insert(off.end(), offsets[s].begin(), offsets[s].end());
+    }
+    std::vector<bpf_pose_hit> hits((size_t)(k > 0 ? k : 1));
+    int n = 0;
+    e_->check(bpf_cloud_search_poses_joint(e_->get(), (int)datas.size(), points.data(), counts.data(), off.data(),
+                                           headings, cell_stride, first, count, k, hits.data(), &n));
     hits.resize((size_t)n);
     return hits;
   }

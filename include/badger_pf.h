@@ -1307,6 +1307,59 @@ int bpf_cloud_search_poses(bpf_engine* e, const float* points_xyz, int n_points,
  * itself, also when it is past the limit of a search); *columns_out = |C_s| */
 int bpf_cloud_search_space(bpf_engine* e, int headings, int cell_stride, long long* candidates_out, int* columns_out);
 
+/* ------------------------------------------------------------------ joint pose search over several scans
+ * One scan cannot tell the look-alike poses of a periodic environment apart; the last few scans with the odometry
+ * between them, or two sensors at a known rigid offset, can.  Every candidate of bpf_planar_search_poses /
+ * bpf_cloud_search_poses is scored against n_scans scans, scan s taken at the candidate's pose composed with a rigid
+ * offset D_s, and the best k come back.  NOT reference calls (parity unpinned by construction).
+ *
+ * Scans: 1 <= n_scans <= 16.  Planar: scan s is (ranges[s], angles[s], range_counts[s], range_maxes[s]); counts and
+ * range_max may differ between scans.  Cloud: scan s is n_points[s] packed float xyz triples at points_xyz[s], taken as
+ * given; sizes may differ.
+ * Offsets: offsets[3 * s ...] = D_s = (dx, dy, dth), finite doubles: the robot's pose at scan s expressed in the frame
+ * of the candidate pose (an odometry delta; for a second sensor, the offset that makes pose (+) D_s (+) scanner_pose
+ * that sensor's pose).  D_0 need not be zero.
+ * Candidates: enumeration, numbering, first / count, count = -1, k <= 1024 and the 2^31 - 1 limit are those of the
+ * single-scan calls; candidate c has the base pose (x, y, theta_h) they give it.  In addition headings <= 65536
+ * (BPF_ERR_CAPACITY otherwise), because of the table below.
+ * Composed pose, as coordAdd writes it (planar_scanner.cpp:693-701), left to right, no contraction:
+ *   x_s = (x + dx * C_h) - dy * S_h,  y_s = (y + dx * S_h) + dy * C_h,  theta_s = theta_h + dth   (not normalised: the
+ *   scoring path normalises where the reference does)
+ * with C_h = cos(theta_h), S_h = sin(theta_h) from a table of `headings` entries that the host fills with the C
+ * library's cos / sin of the double theta_h, once per call: bpf_pose_search_heading_table gives the same table.  So a
+ * composed pose is bit for bit what a host model computes with the same libm.
+ * Joint score: w_0 = 1.0; w_{s+1} is the weight of the one-sample set {(x_s, y_s, theta_s), w_s} after
+ * applyModelToSampleSet (set->converged = 0) against scan s, under the model, map factors / off_map_factor and scanner
+ * pose / tf configured on the engine; the score is w_S: the un-normalised weight that a noise-free particle started at
+ * the candidate carries after the S sensor updates.  It is NOT the product of S separately rounded single-scan
+ * scores.  With max_beams < 2 every score is 1.0.
+ * Result: bpf_pose_hit rows in the order of the single-scan calls; `pose` is the BASE pose of the candidate, i, j,
+ * heading and candidate as there.  Lists of disjoint ranges merge with bpf_pose_search_merge.
+ *
+ * Status: BPF_ERR_INVALID_ARGUMENT for n_scans outside 1 .. 16, a non-finite offset, a null scan or output, a scan
+ * with range_count / n_points <= 0, and what the single-scan calls refuse; BPF_ERR_NOT_CONFIGURED without map / LUT /
+ * model; BPF_ERR_CAPACITY as above; the scoring path's own codes pass through.  Read-only for a filter, exactly as the
+ * single-scan searches are.  Per window of bpf_pose_search_window() candidates the device runs, for every scan, the
+ * composition and the scoring path, then one selection; the host waits where the single-scan searches wait (the
+ * planar form stages a scan per scoring call, so with n_scans >= 4 it also waits at the staging ring). */
+/* cos / sin of theta_h = (2.0 * pi * h) / headings - pi, h = 0 .. headings - 1, as the joint calls tabulate them;
+ * 1 <= headings <= 65536; needs no engine */
+int bpf_pose_search_heading_table(int headings, double* cos_out, double* sin_out);
+int bpf_planar_search_poses_joint(bpf_engine* e, int n_scans, const double* const* ranges,
+                                  const double* const* angles, const int* range_counts, const double* range_maxes,
+                                  const double* offsets /* [n_scans][3] */, int headings, int cell_stride,
+                                  long long first, long long count, int k, bpf_pose_hit* hits_out, int* n_hits_out);
+int bpf_cloud_search_poses_joint(bpf_engine* e, int n_scans, const float* const* points_xyz, const int* n_points,
+                                 const double* offsets /* [n_scans][3] */, int headings, int cell_stride,
+                                 long long first, long long count, int k, bpf_pose_hit* hits_out, int* n_hits_out);
+/* Diagnostic: the n_scans composed poses of the n candidates given (any order, repeats allowed), formed by the joint
+ * search's own kernel: poses_out[n][n_scans][3].  Needs the map of the space only (and its LUT, planar); a candidate
+ * outside the space is BPF_ERR_INVALID_ARGUMENT. */
+int bpf_planar_search_joint_poses(bpf_engine* e, int headings, int cell_stride, const double* offsets, int n_scans,
+                                  const long long* candidates, int n, double* poses_out);
+int bpf_cloud_search_joint_poses(bpf_engine* e, int headings, int cell_stride, const double* offsets, int n_scans,
+                                 const long long* candidates, int n, double* poses_out);
+
 /* The cloud search, pruned: the rows of bpf_cloud_search_poses, bit for bit, from fewer exact evaluations.  NOT a
  * reference call.  The structure, the stats and their invariants are those of bpf_planar_search_poses_pruned.
  *
